@@ -21,6 +21,12 @@ SECONDARY LEG in the same JSON line (`lightgcn`): BASELINE configs[2] (N = 1) / 
 the reference's full-graph propagation forward AND backward on every mini-batch, through skrec.parallel.ShardedLightGCN.
 `--workload lightgcn` makes that leg the headline instead.
 Inputs are resident in HBM before the timed regions.  One JSON line is printed by rank 0.
+
+A plain run measures the headline alone: set-up, --pre-steps + --warmup untimed steps, ONE timed region of exactly --steps
+steps (past the end of the data set the steps go on from its first user, as a next epoch would), the result line.
+`--full` adds everything else the line used to carry: 5 repeats of the timed region (`--repeats`), the whole-epoch leg,
+rooflines, large-batch legs, evaluation, CPU baselines, the LightGCN / LayerGCN and GRU4RecPlus legs, the N > 1 replica check.
+`--dump-outputs DIR` writes the model state the last timed step left (user / item tables, item bias) as .npy files.
 """
 import argparse
 import json
@@ -108,6 +114,54 @@ def shard(ds, rank, world, dev):
                 test_item=ds["test_item"][mine].contiguous()), mine.int()
 
 
+def epoch_chunks(prefix, rowptr, n_users, b, n_steps, at, memo):
+    """the slices n_steps batches of b interactions consume from user `at` on: one user prefix while the data set lasts, then
+    on from user 0 (the next epoch).  `prefix(n_need, start_user)` cuts a slice; `memo` keeps the slices already cut, so that a
+    slice met again is the same tensors (the sampler keeps a CSR's row statistics by its storage).  -> (slices, next user);
+    every slice carries the number of steps it feeds as "steps"."""
+    total = int(rowptr[-1])
+    assert total >= b, "dataset smaller than one batch"
+    chunks = []
+    while n_steps > 0:
+        avail = (total - int(rowptr[at])) // b if at < n_users else 0
+        if avail == 0:
+            at = 0
+            continue
+        k = min(n_steps, avail)
+        if (at, k) not in memo:
+            memo[(at, k)] = dict(prefix(k * b, at), steps=k)
+        sl = memo[(at, k)]
+        chunks.append(sl)
+        n_steps -= k
+        at = sl["end_user"]
+    return chunks, at
+
+
+DUMP_USER_ROWS = 32768      # --dump-outputs: at most this many user rows (8 MiB at d = 64) ...
+DUMP_ITEM_ROWS = 131072     # ... and item rows (32 MiB), a fixed sample of a larger table
+
+
+def dump_outputs(dirname, user_rows, item_rows, item_bias):
+    """--dump-outputs: what a caller of the training path receives -- the parameters the last timed step left -- as float32
+    .npy files: user_embeddings, item_embeddings, item_bias.  A table with more rows than its budget is written as a fixed
+    sample of rows (seed 0, ascending ids; `<name>_rows.npy` holds the ids, as float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def rows(n, cap):
+        return None if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+
+    def save(name, t, ids):
+        a = (t if ids is None else t[torch.from_numpy(ids).to(t.device)]).float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        if ids is not None:
+            np.save(os.path.join(dirname, name + "_rows.npy"), ids.astype(np.float64))
+    save("user_embeddings", user_rows, rows(user_rows.shape[0], DUMP_USER_ROWS))
+    item_ids = rows(item_rows.shape[0], DUMP_ITEM_ROWS)
+    save("item_embeddings", item_rows, item_ids)
+    save("item_bias", item_bias, item_ids)
+
+
 def lightgcn_leg(args, world, rank, dev, dist, full, K, W, cpu_baseline):
     """BASELINE configs[2] (N = 1) / configs[3] (N > 1).  A step is the reference's step (LightGCN.py:180-199): full-graph
     3-layer propagation forward AND backward for one global batch, fused BPR on the propagated tables, dense Adam over
@@ -176,6 +230,23 @@ def lightgcn_leg(args, world, rank, dev, dist, full, K, W, cpu_baseline):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
+    leg = {
+        "value": K * gb / dt, "unit": "train interactions/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3,
+        "scaling": "strong" if strong else "weak", "dtype": "f32", "global_batch": gb,
+        "config": {"workload": f"BASELINE configs[{2 if world == 1 else 3}]: LightGCN 3-layer d=64, synthetic {nU}-user/{nI}-item/"
+                               f"{args.interactions}-interaction graph, full-graph propagation fwd+bwd per mini-batch (reference "
+                               f"semantics), exact-stream sampler, dense Adam",
+                   "users": nU, "items": nI, "train_interactions": n_inter_total, "global_batch": gb,
+                   "sharding": f"users u%{world}; exchange = dense RCCL all-reduce of the [I, 64] item block per layer and "
+                               f"direction ({2 * 3 + 1} x {nI * 256 / 1e6:.1f} MB per step), started beside the user-side product",
+                   "not_computed": "rows of the LAST forward layer no batch reads and, in the FIRST backward hop, the products "
+                                   "with rows of dL/dE-bar that are zero (everything outside the batch): same results "
+                                   "(tests/test_gpu_fullsize.py); SKR_LIGHTGCN_DENSE=1 computes them"},
+    }
+    if not args.full:       # a plain run: the headline figure only
+        del eng
+        torch.cuda.empty_cache()
+        return leg
     run(8, True)    # untimed extra steps only to bracket the two products with events
     barrier()
     ui_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in pair_events]))
@@ -199,30 +270,17 @@ def lightgcn_leg(args, world, rank, dev, dist, full, K, W, cpu_baseline):
         traffic_note = (f"{pmc_source}: 2 x spmm_rows_kernel + {e_tasks['calls'] / pairs:.1f} x spmm_tasks_kernel + {e_red['calls'] / pairs:.1f} x "
                         "spmm_reduce_kernel launches per layer, bytes that enter or leave the L2s (fills from Infinity Cache or HBM): the "
                         "row gathers that miss an XCD's L2")
-    leg = {
-        "value": K * gb / dt, "unit": "train interactions/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3,
-        "scaling": "strong" if strong else "weak", "dtype": "f32", "global_batch": gb,
-        "config": {"workload": f"BASELINE configs[{2 if world == 1 else 3}]: LightGCN 3-layer d=64, synthetic {nU}-user/{nI}-item/"
-                               f"{args.interactions}-interaction graph, full-graph propagation fwd+bwd per mini-batch (reference "
-                               f"semantics), exact-stream sampler, dense Adam",
-                   "users": nU, "items": nI, "train_interactions": n_inter_total, "global_batch": gb,
-                   "sharding": f"users u%{world}; exchange = dense RCCL all-reduce of the [I, 64] item block per layer and "
-                               f"direction ({2 * 3 + 1} x {nI * 256 / 1e6:.1f} MB per step), started beside the user-side product",
-                   "not_computed": "rows of the LAST forward layer no batch reads and, in the FIRST backward hop, the products "
-                                   "with rows of dL/dE-bar that are zero (everything outside the batch): same results "
-                                   "(tests/test_gpu_fullsize.py); SKR_LIGHTGCN_DENSE=1 computes them"},
-        "roofline": {"kernel": "skr_spmm_plan_run: spmm_rows_kernel (short rows, 16 B per lane) + spmm_tasks_kernel (long rows, column-"
-                               "blocked tasks) + spmm_reduce_kernel; ONE layer = user-side product + item-side product",
-                     "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": layer_traffic,
-                     "traffic_source": traffic_note,
-                     "traffic_over_algorithmic": (layer_traffic / alg) if layer_traffic else None,
-                     "avg_launch_ms": ui_ms + iu_ms, "user_side_ms": ui_ms, "item_side_ms": iu_ms, "launches_averaged": len(pair_events),
-                     "algorithmic_bytes_per_launch": alg, "local_nnz": eng.a_ui.nnz,
-                     "row_gather_TBps": 2 * eng.a_ui.nnz * 256 / ((ui_ms + iu_ms) * 1e-3) / 1e12,
-                     "plan": {"user_side": eng.a_ui.plan_info(), "item_side": eng.a_iu.plan_info()},
-                     "note": "algorithmic bytes count every row of X once; the kernels move nnz * 256 B of row gathers out of L2 / "
-                             "Infinity Cache (row_gather_TBps) -- DESIGN.md 4.3"},
-    }
+    leg["roofline"] = {"kernel": "skr_spmm_plan_run: spmm_rows_kernel (short rows, 16 B per lane) + spmm_tasks_kernel (long rows, column-"
+                                 "blocked tasks) + spmm_reduce_kernel; ONE layer = user-side product + item-side product",
+                       "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": layer_traffic,
+                       "traffic_source": traffic_note,
+                       "traffic_over_algorithmic": (layer_traffic / alg) if layer_traffic else None,
+                       "avg_launch_ms": ui_ms + iu_ms, "user_side_ms": ui_ms, "item_side_ms": iu_ms, "launches_averaged": len(pair_events),
+                       "algorithmic_bytes_per_launch": alg, "local_nnz": eng.a_ui.nnz,
+                       "row_gather_TBps": 2 * eng.a_ui.nnz * 256 / ((ui_ms + iu_ms) * 1e-3) / 1e12,
+                       "plan": {"user_side": eng.a_ui.plan_info(), "item_side": eng.a_iu.plan_info()},
+                       "note": "algorithmic bytes count every row of X once; the kernels move nnz * 256 B of row gathers out of L2 / "
+                               "Infinity Cache (row_gather_TBps) -- DESIGN.md 4.3"}
     if cpu_baseline and world == 1:
         from oracle import cpu_baseline as CB
         from skrec.recommender.LightGCN import build_adjacency_device
@@ -331,7 +389,7 @@ def gru_leg(args, world, rank, dev, dist, K, W, cpu_baseline):
     state = {"s": net.zero_states(hi - lo), "step": 0}
 
     kblk = max(1, min(64, int(os.environ.get("SKR_ADAM_BLOCK", "32"))))
-    net.opt.cold_timing = cold_log = []
+    net.opt.cold_timing = cold_log = [] if args.full else None      # the roofline's HIP events (--full)
 
     def run(n_steps):
         """the steps are prepared kblk at a time, as GRU4RecPlus.train_epoch does: inputs / targets gathered for the block, the
@@ -374,7 +432,9 @@ def gru_leg(args, world, rank, dev, dist, K, W, cpu_baseline):
     loss = float(net.loss.cpu())
     opt = net.opt
     torch.cuda.synchronize()
-    if kblk > 1 and cold_log:
+    if not args.full:
+        roof = None
+    elif kblk > 1 and cold_log:
         # the optimiser's large kernel: the cold pass of the blocked TF-Adam, ONE sweep per kblk steps over every 64-float
         # block no step of the block names (20 B per cold parameter: p, m, v read, m, v written), on a side stream beside the
         # steps' launches.  The step itself is a chain of small latency-bound launches (GRU cell, logits, their gradients, the
@@ -411,8 +471,9 @@ def gru_leg(args, world, rank, dev, dist, K, W, cpu_baseline):
                       "parallel_sessions": b, "sessions_per_rank": hi - lo, "steps_per_epoch": args.sessions * (T - 1) // b,
                       "adam_block": kblk,
                       "sharding": f"the {b} parallel sessions split over {world} ranks; one compact all-gather per step "
-                                  f"({(b + n_s) * (d + 1) + b * d + 3 * 2 * d * d + 3 * d + 1} floats per rank), summed in rank order"},
-           "roofline": roof}
+                                  f"({(b + n_s) * (d + 1) + b * d + 3 * 2 * d * d + 3 * d + 1} floats per rank), summed in rank order"}}
+    if roof is not None:
+        leg["roofline"] = roof
     if cpu_baseline and world == 1:
         from oracle import gru4rec as G
         o = G.GRU4RecOracle(E_in.numpy(), [tuple(w.numpy() for w in cells[0])], E_out.numpy(), np.zeros(nI, np.float32), loss="bpr_max",
@@ -749,8 +810,8 @@ def cpu_leg(args, U, V, bias, ds, nU, nI, b, out):
 
 
 def finish(args, world, rank, dev, dist, full, V, bias, out):
-    """replica check (N > 1), the secondary LightGCN leg, the ONE JSON line"""
-    if world > 1:
+    """replica check (N > 1, --full), the secondary LightGCN leg, the ONE JSON line"""
+    if world > 1 and args.full:
         # the replicated item table must be bit-identical on every rank after the timed steps
         chk = torch.stack([V.double().sum(), bias.double().sum(), V.view(torch.int32).long().sum().double()])
         lo_, hi_ = chk.clone(), chk.clone()
@@ -789,7 +850,7 @@ def bprmf_strong(args, world, rank, dev, dist, full, ds):
     del user0
     eng.optimizer.t = int(args.start_step)
     kblk = eng.adam_block
-    timing = eng.optimizer.cold_timing = []
+    timing = eng.optimizer.cold_timing = [] if args.full else None      # the roofline's HIP events (--full)
 
     def prefix(n_need, start_user):
         lo = int(full["rowptr"][start_user])
@@ -797,11 +858,11 @@ def bprmf_strong(args, world, rank, dev, dist, full, ds):
         hi = int(full["rowptr"][end_user])
         return dict(rowptr=(full["rowptr"][start_user:end_user + 1] - lo).contiguous(), users=full["users"][lo:hi].contiguous(),
                     items=full["items"][lo:hi].contiguous(), n_users=end_user - start_user, nnz=hi - lo, end_user=end_user)
-    n_pre = max(0, min(args.pre_steps, (n_inter_total // b - K - W) // 2))
-    pre = prefix(n_pre * b, 0) if n_pre > 0 else None
-    warm = prefix(W * b, pre["end_user"] if pre else 0) if W > 0 else None
-    timed = prefix(K * b, warm["end_user"] if warm else (pre["end_user"] if pre else 0))
-    assert timed["nnz"] >= K * b, "dataset too small for --steps"
+    n_pre = max(0, min(args.pre_steps, n_inter_total // b))
+    memo = {}
+    pre, at = epoch_chunks(prefix, full["rowptr"], nUg, b, n_pre, 0, memo)
+    warm, at = epoch_chunks(prefix, full["rowptr"], nUg, b, W, at, memo)
+    timed, _ = epoch_chunks(prefix, full["rowptr"], nUg, b, K, at, memo)
     sampler = DeviceSampler(2020)
     shuffles = [0]
 
@@ -823,21 +884,24 @@ def bprmf_strong(args, world, rank, dev, dist, full, ds):
         dist.barrier()
         torch.cuda.synchronize()
     marks = [0]
-    if pre is not None:
-        run_slice(pre, n_pre)
-    marks.append(len(timing))
-    if W > 0:
-        run_slice(warm, W)
-    marks.append(len(timing))
+    for sl in pre:
+        run_slice(sl, sl["steps"])
+    marks.append(len(timing or []))
+    for sl in warm:
+        run_slice(sl, sl["steps"])
+    marks.append(len(timing or []))
     barrier()
     t0 = time.perf_counter()
-    run_slice(timed, K)
+    for sl in timed:
+        run_slice(sl, sl["steps"])
     barrier()
     dt = time.perf_counter() - t0
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
-    marks.append(len(timing))
+    marks.append(len(timing or []))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.user_rows, eng.item_rows, eng.item_bias)
     sparse = eng.exchange == "sparse" or (eng.exchange == "auto" and world * 2 * b * 66 < nI * 65)
     out = {
         "metric": "train interactions/sec + eval users/sec (HR@10/NDCG@10) at 1/2/4/8 MI355X",
@@ -967,11 +1031,24 @@ def main():
     ap.add_argument("--no-layergcn", action="store_true", help="skip the LayerGCN steps at the end of the LightGCN leg")
     ap.add_argument("--lightgcn-steps", type=int, default=10)
     ap.add_argument("--lightgcn-warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are run this many times (fresh slices of the epoch each "
-                    "time, barrier + synchronize around each); `value` is the median repeat, all of them are listed")
+    ap.add_argument("--repeats", type=int, default=None, help="the K timed steps are run this many times (fresh slices of the epoch each "
+                    "time, barrier + synchronize around each); `value` is the median repeat, all of them are listed (default: 5 with "
+                    "--full, else 1)")
     ap.add_argument("--large-batches", default="16384,65536", help="batch sizes of the separately labelled large-batch legs "
                     "(SURVEY 8d: batch_size is a config knob of the reference); empty = none")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: repeats, whole epochs, rooflines, "
+                    "large batches, evaluation, CPU baselines, the LightGCN / LayerGCN / GRU4RecPlus legs, the replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the parameters the last timed step left as DIR/*.npy "
+                    "(float32; a fixed sample of the rows of a large table)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps and the result line -- every other leg stays off
+        args.no_cpu_baseline = args.no_eval = args.no_epoch = args.no_lightgcn = args.no_layergcn = args.no_gru = True
+        args.large_batches = ""
+    if args.dump_outputs and args.workload != "bprmf":
+        ap.error("--dump-outputs covers the BPRMF headline (--workload bprmf)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher (no HIP call has been made in this process)
@@ -1072,20 +1149,29 @@ def main():
                     nnz=hi - lo, end_user=end_user)
     # --pre-steps real training steps before the W warm-up steps (untimed, own user range): every kernel and torch
     # helper of the loop has run at full queue depth, and the moments of the rows they touch are no longer all-zero
-    n_pre = max(0, min(args.pre_steps, (int(ds["rowptr"][-1]) // b - K - W) // 2))
+    n_pre = max(0, min(args.pre_steps, int(ds["rowptr"][-1]) // b))
     if world > 1:   # every step holds collectives: all ranks must run the same number (shards differ in size)
         t_pre = torch.tensor([n_pre], device=dev, dtype=torch.int64)
         dist.all_reduce(t_pre, op=dist.ReduceOp.MIN)
         n_pre = int(t_pre)
-    pre = prefix(n_pre * b, 0) if n_pre > 0 else None
-    warm = prefix(W * b, pre["end_user"] if pre else 0) if W > 0 else None
+    # the slices the steps consume: user prefixes, on from user 0 again past the end of the shard (the next epoch)
+    memo = {}
+    pre_chunks, at = epoch_chunks(prefix, ds["rowptr"], nU, b, n_pre, 0, memo)
+    warm_chunks, at = epoch_chunks(prefix, ds["rowptr"], nU, b, W, at, memo)
     R = max(1, args.repeats)
-    timed_slices, at = [], (warm["end_user"] if warm else (pre["end_user"] if pre else 0))
-    for _ in range(R):          # every repeat trains on interactions of its own (its sampler call is inside its timed region)
-        timed_slices.append(prefix(K * b, at))
-        at = timed_slices[-1]["end_user"]
-        assert timed_slices[-1]["nnz"] >= K * b, "dataset too small for --steps x --repeats"
-    timed = timed_slices[0]
+    timed_chunks = []
+    for _ in range(R):          # every repeat trains on interactions of its own (its sampler calls are inside its timed region)
+        chunks, at = epoch_chunks(prefix, ds["rowptr"], nU, b, K, at, memo)
+        timed_chunks.append(chunks)
+    if world > 1:   # ... and the same slices' lengths (an epoch boundary ends a slice): compared in two fixed-size rounds
+        groups = [pre_chunks, warm_chunks] + timed_chunks
+        for vals in ([len(c) for c in groups], [sl["steps"] for c in groups for sl in c]):
+            v = torch.tensor(vals, device=dev, dtype=torch.int64)
+            v_lo, v_hi = v.clone(), v.clone()
+            dist.all_reduce(v_lo, op=dist.ReduceOp.MIN)
+            dist.all_reduce(v_hi, op=dist.ReduceOp.MAX)
+            assert torch.equal(v_lo, v_hi), "the ranks' shards reach an epoch boundary at different steps: use fewer --steps"
+    timed = timed_chunks[0][0]
     sampler = DeviceSampler(2020)
     def sample_slice(sl, smp=None):
         neg = torch.empty(sl["nnz"], dtype=torch.int32, device=dev)
@@ -1113,7 +1199,7 @@ def main():
         if exchange == "sparse":   # per step: the distinct item ids its 2*b gradient rows belong to (-1 = duplicate)
             step_ids = unique_padded_rows(torch.cat([ii.view(n_steps, b), jj.view(n_steps, b)], dim=1))
             pids = step_ids.data_ptr()
-        ev = event_pool[:n_steps] if (phase == "timed" and kblk <= 1) else None    # created outside the timed region
+        ev = event_pool[:n_steps] if (phase == "timed" and kblk <= 1 and event_pool) else None    # created outside the timed region
         if kblk > 1:
             # Temporally blocked dense Adam (csrc/train.hip K2b; at N = 1 what skrec.recommender.BPRMF.train_epoch does).
             # Per block of kblk steps: rows no batch of the block touches get their kblk zero-gradient updates in ONE
@@ -1329,21 +1415,26 @@ def main():
     # size the sampler's scratch for the timed slices outside the timed regions (consumes stream words), and let it take every
     # slice's row statistics here: they are a property of the CSR, read back ONCE per CSR (in fit() the CSR is the same every
     # epoch, so only the first epoch pays that round trip) -- a timed region must not contain the first sight of its slice
-    for sl_ in timed_slices[1:]:
+    seen = {id(timed)}          # the first timed slice comes last: its negatives feed the preparation below
+    for sl_ in [c for chunks in timed_chunks[1:] for c in chunks] + timed_chunks[0][1:] + [timed]:
+        if id(sl_) in seen and sl_ is not timed:
+            continue
+        seen.add(id(sl_))
         _scratch = torch.empty(sl_["nnz"], dtype=torch.int32, device=dev)
         sampler.sample_epoch_exact(nI, sl_["n_users"], sl_["rowptr"], sl_["items"], sl_["nnz"], 1, _scratch)
-    _scratch = torch.empty(timed["nnz"], dtype=torch.int32, device=dev)
-    sampler.sample_epoch_exact(nI, timed["n_users"], timed["rowptr"], timed["items"], timed["nnz"], 1, _scratch)
     # ... and run the slice preparation once at the timed slice's size (first use of a kernel loads its code object)
-    _cols = _hip.shuffle_gather([timed["users"], timed["items"], _scratch], None, seed=1, n_out=K * b)
+    k0 = timed["steps"]
+    _cols = _hip.shuffle_gather([timed["users"], timed["items"], _scratch], None, seed=1, n_out=k0 * b)
     if exchange == "sparse":
-        unique_padded_rows(torch.cat([_cols[1].view(K, b), _cols[2].view(K, b)], dim=1))
+        unique_padded_rows(torch.cat([_cols[1].view(k0, b), _cols[2].view(k0, b)], dim=1))
     del _scratch, _cols
-    # HIP-event pairs around the Adam launches of the timed steps (the roofline's per-launch time).  Created HERE:
+    # HIP-event pairs around the Adam launches of the timed steps (the roofline's per-launch time; --full only).  Created HERE:
     # building 2K timing events costs ~30 us each once a pool of ~1000 is used up (+56 ms inside the region at K = 960)
     mk_pair = lambda: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))   # noqa: E731
-    event_pool = [mk_pair() for _ in range(K)] if kblk <= 1 else []
-    cold_pool = [mk_pair() for _ in range((n_pre + W) // max(kblk, 1) + R * (K // max(kblk, 1) + 1) + 6)] if kblk > 1 else []
+    n_chunks = len(pre_chunks) + len(warm_chunks) + sum(len(c) for c in timed_chunks)
+    event_pool = [mk_pair() for _ in range(K)] if (kblk <= 1 and args.full) else []
+    cold_pool = [mk_pair() for _ in range((n_pre + W) // max(kblk, 1) + R * (K // max(kblk, 1)) + n_chunks + 6)] \
+        if (kblk > 1 and args.full) else []
     # the third whole epoch: 512 of its blocks (from the 257th on) get their cold pass and their step launches bracketed
     epoch_cold_pool = [mk_pair() for _ in range(512)] if (kblk > 1 and world == 1 and not args.no_epoch) else []
     mk_trip = lambda: tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))   # noqa: E731
@@ -1356,15 +1447,16 @@ def main():
     cold_log, step_events = [], []
     # SKR_BENCH_EPOCH_PROBE=1: HIP events around the cold pass and around the step launches of 200 blocks of each whole epoch
     epoch_probe = [] if os.environ.get("SKR_BENCH_EPOCH_PROBE") == "1" else None
-    if pre is not None:
-        run_slice(pre, n_pre, "pre")
-    if W > 0:
-        run_slice(warm, W, "warmup")
+    for sl_ in pre_chunks:
+        run_slice(sl_, sl_["steps"], "pre")
+    for sl_ in warm_chunks:
+        run_slice(sl_, sl_["steps"], "warmup")
     dts = []
     for r_ in range(R):         # EXACTLY K steps per repeat, barrier + synchronize on both sides, max over the ranks
         barrier()
         t0 = time.perf_counter()
-        run_slice(timed_slices[r_], K, "timed")
+        for sl_ in timed_chunks[r_]:
+            run_slice(sl_, sl_["steps"], "timed")
         barrier()
         dt_r = time.perf_counter() - t0
         if world > 1:
@@ -1373,21 +1465,23 @@ def main():
             dt_r = float(tmax)
         dts.append(dt_r)
     dt = float(np.median(dts))
-    if kblk > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, U, V, bias)
+    if args.full and kblk > 1:
         n_fresh_log = len(cold_log)              # what follows in the log belongs to the whole-epoch leg
         cold_ms = [(a.elapsed_time(z), kk, ph) for (a, z), kk, ph in cold_log]
         adam_ms = float(np.mean([t for t, _, _ in cold_ms]))
         steps_per_launch = float(np.mean([kk for _, kk, _ in cold_ms]))
-    else:
+    elif args.full:
         adam_ms = float(np.mean([a.elapsed_time(z) for a, z in step_events]))
     value = K * b * world / dt
     if fused:       # the tags of the last block FusedBlocks ran
         blk_tag, run_slice.serial = fb.tags[fb.last_q], fb.serial
-    n_hot_blocks = int((blk_tag == run_slice.serial).sum()) if kblk > 1 else 0     # hot blocks of the last timed k-step block
+    n_hot_blocks = int((blk_tag == run_slice.serial).sum()) if (kblk > 1 and args.full) else 0     # hot blocks of the last timed k-step block
     # the same pass ALONE on the chip (copies of the buffers, same tags, same step count): what the kernel does when it
     # does not share HBM and CUs with the step kernels -- its own quality, next to the live (overlapped) figure
     cold_alone_ms = None
-    if kblk > 1 and world == 1:
+    if kblk > 1 and world == 1 and args.full:
         cp, cm, cv = flat.clone(), m1.clone(), m2.clone()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ts = []
@@ -1497,45 +1591,46 @@ def main():
     }
     if epoch_leg is not None:
         out["full_epoch"] = epoch_leg
-    pmc_traffic, pmc_source = pmc_lookup()
-    if world > 1:
-        pmc_traffic = None       # the recorded counters belong to the N = 1 command: a shard's pass moves other bytes
-    # ---- roofline of the dominant kernel (adam_kernel over the flat parameter buffer) ---------------
-    # 7 fp32 per parameter per step (p,g,m,v in; p,m,v out).  For N > 1 the timed launch is the
-    # replicated [V | b] part (the user part overlaps the all-reduce and is not bracketed by the events).
-    if kblk > 1:
-        # dominant train kernel in blocked mode: adam_cold_rows_kernel, ONE pass per kblk steps over every 64-float block no
-        # batch of the k-step block touches.  Algorithmic bytes per LAUNCH: p, m, v read (12 B) and m, v
-        # written (8 B) per cold parameter = 20 B; blocks not at rest also write p (4 B more -- not counted: their share
-        # depends on the state of the moments).  The launch applies kblk optimiser steps.  SURVEY 8(d)'s per-step figure
-        # (28 B per parameter and step) is what this pass replaces kblk times over: `dense_equivalent_GBps`, not `achieved`.
-        fresh = cold_roofline(n_par, n_hot_blocks, kblk, cold_ms, cold_alone_ms, side != torch.cuda.current_stream(),
-                              pmc_traffic("adam_cold_rows_kernel") if args.users == 1_000_000 else None, pmc_source)
-        aged_ms = [(a.elapsed_time(z), kk, ph) for (a, z), kk, ph in cold_log[n_fresh_log:] if ph == "epoch3"]
-        if aged_ms:
-            # THE roofline entry: the cold passes of the third whole epoch (blocks 257..768) -- every row's moments aged by two
-            # epochs of real training, nothing skipped because a moment is still zero: the state an epoch runs in
-            out["roofline"] = cold_roofline(n_par, n_hot_epoch, kblk, aged_ms, None, True,
-                                            pmc_traffic("adam_cold_rows_kernel@epoch3") if args.users == 1_000_000 else None, pmc_source)
-            out["roofline"]["state"] = ("third consecutive whole epoch (full_epoch leg), cold passes of blocks 257-768, every one "
-                                        "bracketed by HIP events on the side stream it runs on, underneath the block's step launches")
-            fresh["state"] = ("fresh model: the passes of this run's pre-steps, warm-up and timed steps -- most rows' moments are still "
-                              "zero and are not written back, which flatters the pass; kept for comparison with rounds 1-2")
-            out["roofline_fresh_model"] = fresh
+    if args.full:       # rooflines of the dominant kernels: HIP events of the timed steps and of the whole-epoch leg
+        pmc_traffic, pmc_source = pmc_lookup()
+        if world > 1:
+            pmc_traffic = None       # the recorded counters belong to the N = 1 command: a shard's pass moves other bytes
+        # ---- roofline of the dominant kernel (adam_kernel over the flat parameter buffer) ---------------
+        # 7 fp32 per parameter per step (p,g,m,v in; p,m,v out).  For N > 1 the timed launch is the
+        # replicated [V | b] part (the user part overlaps the all-reduce and is not bracketed by the events).
+        if kblk > 1:
+            # dominant train kernel in blocked mode: adam_cold_rows_kernel, ONE pass per kblk steps over every 64-float block no
+            # batch of the k-step block touches.  Algorithmic bytes per LAUNCH: p, m, v read (12 B) and m, v
+            # written (8 B) per cold parameter = 20 B; blocks not at rest also write p (4 B more -- not counted: their share
+            # depends on the state of the moments).  The launch applies kblk optimiser steps.  SURVEY 8(d)'s per-step figure
+            # (28 B per parameter and step) is what this pass replaces kblk times over: `dense_equivalent_GBps`, not `achieved`.
+            fresh = cold_roofline(n_par, n_hot_blocks, kblk, cold_ms, cold_alone_ms, side != torch.cuda.current_stream(),
+                                  pmc_traffic("adam_cold_rows_kernel") if args.users == 1_000_000 else None, pmc_source)
+            aged_ms = [(a.elapsed_time(z), kk, ph) for (a, z), kk, ph in cold_log[n_fresh_log:] if ph == "epoch3"]
+            if aged_ms:
+                # THE roofline entry: the cold passes of the third whole epoch (blocks 257..768) -- every row's moments aged by two
+                # epochs of real training, nothing skipped because a moment is still zero: the state an epoch runs in
+                out["roofline"] = cold_roofline(n_par, n_hot_epoch, kblk, aged_ms, None, True,
+                                                pmc_traffic("adam_cold_rows_kernel@epoch3") if args.users == 1_000_000 else None, pmc_source)
+                out["roofline"]["state"] = ("third consecutive whole epoch (full_epoch leg), cold passes of blocks 257-768, every one "
+                                            "bracketed by HIP events on the side stream it runs on, underneath the block's step launches")
+                fresh["state"] = ("fresh model: the passes of this run's pre-steps, warm-up and timed steps -- most rows' moments are still "
+                                  "zero and are not written back, which flatters the pass; kept for comparison with rounds 1-2")
+                out["roofline_fresh_model"] = fresh
+            else:
+                fresh["state"] = "fresh model (no whole-epoch leg in this run): flattering, see DESIGN.md 5"
+                out["roofline"] = fresh
+            if epoch_block_log:
+                out["roofline_step"] = step_roofline(b, kblk, epoch_block_log, alone_block_log,
+                                                     pmc_traffic("bpr_fused_step_kernel@epoch3") if args.users == 1_000_000 else None, pmc_source)
         else:
-            fresh["state"] = "fresh model (no whole-epoch leg in this run): flattering, see DESIGN.md 5"
-            out["roofline"] = fresh
-        if epoch_block_log:
-            out["roofline_step"] = step_roofline(b, kblk, epoch_block_log, alone_block_log,
-                                                 pmc_traffic("bpr_fused_step_kernel@epoch3") if args.users == 1_000_000 else None, pmc_source)
-    else:
-        adam_bytes = float(n_par if world == 1 else n_par - nU * D) * 28.0
-        ach = adam_bytes / (adam_ms * 1e-3) / 1e9
-        out["roofline"] = {"kernel": "adam_kernel<true> (dense Adam over the flat [U|V|b] buffer, one launch per step)", "bound": "hbm",
-                           "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                           "traffic": pmc_traffic("adam_kernel") if world == 1 and args.users == 1_000_000 else None,
-                           "traffic_source": pmc_source, "avg_launch_ms": adam_ms, "launches_averaged": len(step_events),
-                           "algorithmic_bytes_per_launch": adam_bytes}
+            adam_bytes = float(n_par if world == 1 else n_par - nU * D) * 28.0
+            ach = adam_bytes / (adam_ms * 1e-3) / 1e9
+            out["roofline"] = {"kernel": "adam_kernel<true> (dense Adam over the flat [U|V|b] buffer, one launch per step)", "bound": "hbm",
+                               "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic("adam_kernel") if world == 1 and args.users == 1_000_000 else None,
+                               "traffic_source": pmc_source, "avg_launch_ms": adam_ms, "launches_averaged": len(step_events),
+                               "algorithmic_bytes_per_launch": adam_bytes}
 
     if world == 1 and args.large_batches:
         out["large_batch"] = {str(bl): bprmf_large_batch_leg(bl, dev, nU, nI, prefix, sample_slice)

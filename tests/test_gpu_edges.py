@@ -94,7 +94,7 @@ def test_score_matrix_predict_surface():
 
 def test_bench_contract_on_a_small_workload():
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "8", "--warmup", "2", "--users", "60000",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--users", "60000",
                         "--items", "5000", "--interactions", "1500000", "--eval-users", "4096"],
                        capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -111,6 +111,38 @@ def test_bench_contract_on_a_small_workload():
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
     assert d["value"] > 20 * cb["value"]
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """a plain run (no --full) is the headline alone: one timed region of exactly --steps steps -- here more than the small data
+    set's epoch holds, so the steps go on from its first user --, ms_per_step of that region, and --dump-outputs writes the
+    parameters the last step left as float32 .npy files within 64 MB (the user table a fixed sample of its rows)"""
+    from conftest import REPO
+    steps, out = 3000, tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "3",
+                        "--users", "60000", "--items", "5000", "--interactions", "1500000", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=500)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1
+    d = json.loads(line[0])
+    assert d["steps"] == steps and d["warmup"] == 3 and d["repeats"]["n"] == 1
+    assert steps * 1024 > d["config"]["train_interactions"]           # the region crosses an epoch boundary
+    assert d["unit"] == "train interactions/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * 1e-3 * steps - d["repeats"]["seconds"][0]) < 1e-9
+    assert abs(d["value"] - steps * 1024 / d["repeats"]["seconds"][0]) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "eval", "full_epoch", "large_batch", "lightgcn", "gru4rec"):
+        assert k not in d, k
+    got = {p.name: np.load(p) for p in out.iterdir()}
+    assert sorted(got) == ["item_bias.npy", "item_embeddings.npy", "user_embeddings.npy", "user_embeddings_rows.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    assert got["user_embeddings.npy"].shape == (32768, 64) and got["item_embeddings.npy"].shape == (5000, 64)
+    assert got["item_bias.npy"].shape == (5000,)
+    rows = got["user_embeddings_rows.npy"]
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.sort(np.random.default_rng(0).choice(60000, 32768, replace=False)))
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    assert float(np.abs(got["item_embeddings.npy"]).max()) > 0
 
 
 def test_dataset_csr_gpu_sort_equals_numpy(monkeypatch):

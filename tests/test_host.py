@@ -268,6 +268,39 @@ def test_bench_roofline_arithmetic():
     assert r2["traffic"] is None and r2["achieved_by_traffic"] is None and r2["traffic_source"] is None and "alone" not in r2
 
 
+def test_bench_epoch_chunks_cover_any_step_count():
+    """bench.py's slices of the steps: exactly n_steps batches, each slice holds the interactions of its steps, one user prefix
+    while the data set lasts and on from user 0 past its end (a next epoch); a slice met again is the same object"""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(4)
+    n_users, b = 300, 64
+    lens = rng.integers(0, 40, n_users)
+    rowptr = torch.zeros(n_users + 1, dtype=torch.long)
+    rowptr[1:] = torch.cumsum(torch.from_numpy(lens), 0)
+    total = int(rowptr[-1])
+
+    def prefix(n_need, start_user):
+        lo = int(rowptr[start_user])
+        end_user = min(int(torch.searchsorted(rowptr, torch.tensor(lo + n_need))) + 1, n_users)
+        return dict(n_users=end_user - start_user, nnz=int(rowptr[end_user]) - lo, end_user=end_user, start=start_user)
+    memo = {}
+    one, at = bench.epoch_chunks(prefix, rowptr, n_users, b, 20, 0, memo)
+    assert len(one) == 1 and one[0]["steps"] == 20 and one[0]["start"] == 0 and at == one[0]["end_user"]
+    for n_steps in (1, 7, total // b, total // b + 1, 5 * (total // b) + 3):
+        chunks, at2 = bench.epoch_chunks(prefix, rowptr, n_users, b, n_steps, at, memo)
+        assert sum(c["steps"] for c in chunks) == n_steps
+        assert all(c["steps"] >= 1 and c["nnz"] >= c["steps"] * b for c in chunks)
+        for c, d in zip(chunks, chunks[1:]):     # consecutive: the next slice starts where this one ended, or at user 0
+            assert d["start"] == (c["end_user"] if c["end_user"] < n_users and total - int(rowptr[c["end_user"]]) >= b else 0)
+        if n_steps > total // b:
+            assert any(c["start"] == 0 for c in chunks)
+    whole = [c for c in memo.values() if c["start"] == 0 and c["steps"] == total // b]
+    assert len(whole) == 1                       # every whole epoch is the same slice
+    assert bench.epoch_chunks(prefix, rowptr, n_users, b, 0, 5, memo) == ([], 5)
+
+
 def test_fused_step_words_on_the_host():
     """The words of the one-launch BPRMF step (include/skrec_hip.h, skr_bpr_fused_step) as skrec.recommender.fused.build_fused_meta
     derives them with sorts and scans (the GPU suite compares skr_bpr_fused_plan with it), against a literal walk over the

@@ -1,6 +1,6 @@
 # usage: bash tools/epoch_leg.sh -- bench.py's whole-epoch leg by block length of the blocked Adam
 for k in 8 16; do
-  SKR_ADAM_BLOCK=$k python bench.py --no-cpu-baseline --no-eval 2>/dev/null | python -c "
+  SKR_ADAM_BLOCK=$k python bench.py --full --no-cpu-baseline --no-eval 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 e=d['full_epoch']

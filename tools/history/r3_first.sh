@@ -2,14 +2,14 @@
 # round 3, first GPU call: the suite, the driver's bench line, the self-launching N = 2 rehearsal (gloo, one card)
 R=$GRAFT_REPO_ROOT
 cd $R
-mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/r3_tests.log 2>&1; echo "tests exit $?"; tail -3 gpurun_out/r3_tests.log
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r3_bench_n1.json 2> gpurun_out/r3_bench_n1.err; echo "bench exit $?"
-tail -c 600 gpurun_out/r3_bench_n1.err
+mkdir -p tools_out
+timeout -k 10 900 python -m pytest tests -m gpu -x -q > tools_out/r3_tests.log 2>&1; echo "tests exit $?"; tail -3 tools_out/r3_tests.log
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > tools_out/r3_bench_n1.json 2> tools_out/r3_bench_n1.err; echo "bench exit $?"
+tail -c 600 tools_out/r3_bench_n1.err
 python3 - <<'PY'
 import json
 try:
-    d = json.loads(open("gpurun_out/r3_bench_n1.json").read().strip().splitlines()[-1])
+    d = json.loads(open("tools_out/r3_bench_n1.json").read().strip().splitlines()[-1])
     print("value", d["value"], "ms/step", d["ms_per_step"], "repeats", d["repeats"]["seconds"])
     print("epoch", d.get("full_epoch", {}).get("epochs_seconds"))
     for k in ("roofline", "roofline_fresh_model"):
@@ -24,6 +24,6 @@ try:
 except Exception as e:
     print("parse failed", e)
 PY
-env -u WORLD_SIZE -u RANK -u LOCAL_RANK SKR_DIST_BACKEND=gloo timeout -k 10 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-epoch > gpurun_out/r3_bench_n2_gloo.json 2> gpurun_out/r3_bench_n2_gloo.err; echo "n2 exit $?"
-tail -c 400 gpurun_out/r3_bench_n2_gloo.err
-head -c 700 gpurun_out/r3_bench_n2_gloo.json
+env -u WORLD_SIZE -u RANK -u LOCAL_RANK SKR_DIST_BACKEND=gloo timeout -k 10 900 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-epoch > tools_out/r3_bench_n2_gloo.json 2> tools_out/r3_bench_n2_gloo.err; echo "n2 exit $?"
+tail -c 400 tools_out/r3_bench_n2_gloo.err
+head -c 700 tools_out/r3_bench_n2_gloo.json

@@ -1,13 +1,13 @@
 #!/bin/bash
 # the whole GPU suite + smoke + the driver's bench line
 cd $GRAFT_REPO_ROOT
-timeout -k 10 1000 python -m pytest tests -m gpu -q > gpurun_out/r3_full_tests.log 2>&1; echo "tests exit $?"; tail -8 gpurun_out/r3_full_tests.log
-timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r3_smoke.log 2>&1; echo "smoke exit $?"; tail -2 gpurun_out/r3_smoke.log
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r3_bench_n1.json 2> gpurun_out/r3_bench_n1.err; echo "bench exit $?"
-tail -c 300 gpurun_out/r3_bench_n1.err
+timeout -k 10 1000 python -m pytest tests -m gpu -q > tools_out/r3_full_tests.log 2>&1; echo "tests exit $?"; tail -8 tools_out/r3_full_tests.log
+timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > tools_out/r3_smoke.log 2>&1; echo "smoke exit $?"; tail -2 tools_out/r3_smoke.log
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > tools_out/r3_bench_n1.json 2> tools_out/r3_bench_n1.err; echo "bench exit $?"
+tail -c 300 tools_out/r3_bench_n1.err
 python3 - <<'PY'
 import json
-d = json.loads(open("gpurun_out/r3_bench_n1.json").read().strip().splitlines()[-1])
+d = json.loads(open("tools_out/r3_bench_n1.json").read().strip().splitlines()[-1])
 print("value", d["value"], "ms/step", d["ms_per_step"], "epochs", d.get("full_epoch", {}).get("epochs_seconds"))
 for k in ("roofline", "roofline_fresh_model"):
     r = d.get(k, {}); print(k, r.get("frac"), r.get("avg_launch_ms"), r.get("traffic"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # whole bench line with the compute stream = the null stream (0) or a stream of its own (1), same box
 for p in ${@:-0 1}; do
-  SKR_COMPUTE_STREAM=$p timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2> gpurun_out/r3_priofull_$p.err | python3 -c "
+  SKR_COMPUTE_STREAM=$p timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2> tools_out/r3_priofull_$p.err | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 lg = d.get('lightgcn', {}); g = d.get('gru4rec', {})

@@ -6,10 +6,10 @@ for cfg in "$@"; do
   mode=${cfg%%:*}; abl=${cfg##*:}
   export SKR_FUSED_MODE=$mode SKR_FUSED_ABLATE=$abl
   rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE \
-    --output-format csv -d $R/gpurun_out/prof_evalpmc_${mode}_$abl -o evalpmc -- python3 $R/bench.py --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --no-epoch --no-lightgcn --no-gru --large-batches= --eval-users 262144 > $R/gpurun_out/prof_evalpmc_${mode}_$abl.log 2>&1 || { echo "rocprof failed for $cfg"; exit 1; }
+    --output-format csv -d $R/tools_out/prof_evalpmc_${mode}_$abl -o evalpmc -- python3 $R/bench.py --full --steps 5 --warmup 1 --repeats 1 --no-cpu-baseline --no-epoch --no-lightgcn --no-gru --large-batches= --eval-users 262144 > $R/tools_out/prof_evalpmc_${mode}_$abl.log 2>&1 || { echo "rocprof failed for $cfg"; exit 1; }
   python3 - <<PY
 import csv, collections
-rows=list(csv.DictReader(open("$R/gpurun_out/prof_evalpmc_${mode}_$abl/evalpmc_counter_collection.csv")))
+rows=list(csv.DictReader(open("$R/tools_out/prof_evalpmc_${mode}_$abl/evalpmc_counter_collection.csv")))
 agg=collections.defaultdict(dict)
 for r in rows:
     if ("fused_topk_kernel_v7" if "$mode" == "f16x2" else "fused_topk_kernel_v3" if "$mode" == "fp32" else "fused_topk_kernel_v") in r["Kernel_Name"] and not ("$mode" != "fp32" and "kernel_v3" in r["Kernel_Name"]):

@@ -1,4 +1,4 @@
-"""Condense the rocprofv3 output of tools/profile_epoch.sh (gpurun_out/prof_epoch_<tag>/) into profiles/<tag>_epoch_kernel_stats.csv
+"""Condense the rocprofv3 output of tools/profile_epoch.sh (tools_out/prof_epoch_<tag>/) into profiles/<tag>_epoch_kernel_stats.csv
 and the `...@epoch3` entries of profiles/<tag>_pmc_summary.json: per kernel, the launches of the THIRD whole epoch -- the state
 bench.py's `roofline` / `roofline_step` are measured in -- are the last third of the whole-epoch launches."""
 import collections
@@ -8,8 +8,8 @@ import os
 import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-COMMAND = "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-lightgcn --no-gru --no-cpu-baseline --no-eval --large-batches="
-src = f"gpurun_out/prof_epoch_{tag}"
+COMMAND = "python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-lightgcn --no-gru --no-cpu-baseline --no-eval --large-batches="
+src = f"tools_out/prof_epoch_{tag}"
 os.makedirs("profiles", exist_ok=True)
 
 

@@ -1,5 +1,5 @@
 """Condense the rocprofv3 CSVs that tools/profile_bench.sh / profile_eval.sh left under
-gpurun_out/prof_<tag>/ into the small, tracked files under profiles/."""
+tools_out/prof_<tag>/ into the small, tracked files under profiles/."""
 import collections
 import csv
 import json
@@ -7,8 +7,8 @@ import os
 import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
-COMMAND = "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-epoch"
-src = f"gpurun_out/prof_{tag}"
+COMMAND = "python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-epoch"
+src = f"tools_out/prof_{tag}"
 os.makedirs("profiles", exist_ok=True)
 
 
