@@ -641,6 +641,52 @@ int skr_pop_sample(const double* d_cumsum, int n_items, const double* d_uniform,
 int skr_scatter_add_rows(const float* d_src, const int32_t* d_index, int n, int dim, const float* d_table, float reg,
                          float* d_g_table, uint8_t* d_touch, const float* d_touch_base, void* stream);
 
+/* ============================================================================================
+ * Q -- sequential pairwise recommenders: FPMC and TransRec (csrc/seq.hip)
+ * replaces: _FPMC.forward / predict and FPMC.fit's step (recommender/FPMC.py:71-86,118-128),
+ *           _TransRec.forward / predict and TransRec.fit's step (recommender/TransRec.py:75-93,125-135),
+ *           inner_product / l2_distance / bpr_loss / l2_loss (utils/torch.py:20-29,62-74).
+ * Rows are `dim` floats (64, 128, 192 or 256: narrower embeddings zero-padded by the caller, as for skr_bpr_step_dim).
+ * A triple (u, l = last item, p = positive, n = negative) with an id outside [0, n_users) / [0, n_items) is skipped.
+ * d_loss: float[2 * loss_slots], loss_slots 1 or SKR_LOSS_SLOTS, as skr_bpr_step_dim: the batch's
+ * sum of -logsigmoid(y_p - y_n) and its un-normalised l2 (0.5 * sum of squares of the gathered rows; a repeated id
+ * counts once per occurrence) are ADDED to the pairs, spread over the workgroups.
+ * ========================================================================================== */
+/* FPMC: y_i = <UI[u], IU[i]> + <LI[l], IL[i]> (the two inner products reduced separately, then added).  With
+ * c = -sigmoid(-(y_p - y_n)) the gradients are scatter-added (atomically) into the four gradient tables:
+ *   gUI[u] += c (IU[p] - IU[n]) + reg UI[u];   gLI[l] += c (IL[p] - IL[n]) + reg LI[l];
+ *   gIU[p|n] += +-c UI[u] + reg IU[p|n];       gIL[p|n] += +-c LI[l] + reg IL[p|n].
+ * l2 rows: UI[u], LI[l], IU[p], IU[n], IL[p], IL[n]. */
+int skr_fpmc_step(const float* d_UI, const float* d_IU, const float* d_IL, const float* d_LI, const int32_t* d_u,
+                  const int32_t* d_l, const int32_t* d_p, const int32_t* d_n, int n, int n_users, int n_items, int dim,
+                  float reg, float* d_gUI, float* d_gIU, float* d_gIL, float* d_gLI, float* d_loss, int loss_slots,
+                  void* stream);
+/* TransRec: t = (U[u] + T) + V[l], y_i = -||t - V[i]||_2 + b[i]; T is the one global transition row (d_T: dim floats).
+ * dy_i/dt = -(t - V[i]) / ||t - V[i]|| (0 at distance 0, torch's norm subgradient); dL/dt goes to U[u], V[l] and T,
+ * the mirrored terms to V[p], V[n], +-c to b[p], b[n]; each row also gets reg * itself, T once per batch.
+ * l2 rows: U[u], V[l], V[p], V[n], b[p], b[n] per triple and T once.  Row gradients are atomic scatters; T's gradient is
+ * summed in a FIXED order (per wavefront, per workgroup, then the workgroups in order, in a second launch), so two
+ * calls on the same inputs give the same bits.  d_work: float[SKR_TRANSREC_MAX_BLOCKS * dim] scratch, no initial
+ * contents, not to be shared by calls that may run at the same time. */
+#define SKR_TRANSREC_MAX_BLOCKS 1024
+int skr_transrec_step(const float* d_U, const float* d_V, const float* d_bias, const float* d_T, const int32_t* d_u,
+                      const int32_t* d_l, const int32_t* d_p, const int32_t* d_n, int n, int n_users, int n_items, int dim,
+                      float reg, float* d_gU, float* d_gV, float* d_gb, float* d_gT, float* d_work, float* d_loss,
+                      int loss_slots, void* stream);
+/* Dense score rows d_out[b * ld + i], b < B, i < n_items, of the users d_users[b]; d_last_item: int32[n_users], the last
+ * training item of every user (-1: none).  A user out of range or without a last item gets a row of NaN (callers raise
+ * before they ask: the reference raises KeyError, FPMC.py:147).
+ *   SKR_SEQ_FPMC      <user_table[u], item_table[i]> + <last_table[last], item_table2[i]>, the two sums kept apart
+ *                     (UI, LI, IU, IL; d_transition and d_item_bias unused)
+ *   SKR_SEQ_TRANSREC  -sqrt(sum_k (t_k - item_table[i]_k)^2) + d_item_bias[i], t = (user_table[u] + d_transition) +
+ *                     last_table[last], from the differences, never from |t|^2 - 2 t.v + |v|^2 (U, V, V; item_table2 unused)
+ * Item tables 16-byte aligned; B <= 65535 * 16. */
+enum { SKR_SEQ_FPMC = 0, SKR_SEQ_TRANSREC = 1 };
+int skr_seq_scores(int mode, const float* d_user_table, const float* d_last_table, const float* d_item_table,
+                   const float* d_item_table2, const float* d_transition, const float* d_item_bias, const int32_t* d_users,
+                   int B, const int32_t* d_last_item, int n_users, int n_items, int dim, float* d_out, int64_t ld,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,9 @@ SIGNATURES = {
     "skr_axpy": (i32, [f32, vp, vp, i64, vp]),
     "skr_scale_copy": (i32, [f32, vp, vp, i64, vp]),
     "skr_scale": (i32, [f32, vp, i64, vp]),
+    "skr_fpmc_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32, vp]),
+    "skr_transrec_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "skr_seq_scores": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i64, vp]),
 }
 
 class SpmmEpilogue(C.Structure):
@@ -117,6 +120,8 @@ EPI_PLAIN, EPI_REFINE_FWD, EPI_REFINE_BWD = 0, 1, 2
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
+SKR_TRANSREC_MAX_BLOCKS = 1024   # skr_transrec_step: d_work holds this many rows of dim floats
+SKR_SEQ_FPMC, SKR_SEQ_TRANSREC = 0, 1     # skr_seq_scores modes
 
 
 class HipError(RuntimeError):

@@ -404,6 +404,18 @@ class SequentialPairwiseIterator(object):
             neg = neg.view(-1, self.num_next)
         return _device_batches(self._cols + [neg], self.batch_size, self.shuffle, self.drop_last)
 
+    def epoch_columns(self):
+        """One epoch as whole device columns (users, item_seqs, pos_next, neg_next) after sampling and shuffling, plus
+        the batch boundaries that iter_device() would walk; consumes the sampler stream and numpy's permutation exactly
+        like one ``iter_device()`` pass (PairwiseIterator.epoch_columns)."""
+        neg = self._g.sample()
+        if self.num_next > 1:
+            neg = neg.view(-1, self.num_next)
+        cols = _shuffled_columns(self._cols + [neg], self.shuffle)
+        n, b = cols[0].shape[0], self.batch_size
+        bounds = [(s, min(s + b, n)) for s in range(0, n, b) if not (self.drop_last and s + b > n)]
+        return cols, bounds
+
     def __iter__(self):
         for cols in self.iter_device():
             yield tuple(c.cpu().numpy() for c in cols)

@@ -1,0 +1,171 @@
+"""Shared engine of the sequential pairwise recommenders (FPMC, TransRec): the reference's training loop over
+``SequentialPairwiseIterator(num_previous=1, num_next=1)`` batches of (user, last item, positive, negative), one fused
+step launch per batch (csrc/seq.hip) on ONE flat fp32 parameter buffer stepped by ``DenseAdam`` -- the reference's
+dense ``torch.optim.Adam`` over every parameter -- and ``skr_seq_scores`` for predict() and the evaluator.
+
+Optimiser stepping, as BPRMF's: at row width 64 the temporally blocked Adam (``SKR_ADAM_BLOCK`` batches per block,
+default 32; bit-identical to one dense ``skr_adam_step`` per batch); ``SKR_ADAM_BLOCK=1`` or wider rows: one dense launch
+per batch.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import _hip
+from ..io import SequentialPairwiseIterator
+from ..utils.py import EarlyStopping
+from .base import AbstractRecommender, DenseAdam, on_compute_stream
+
+__all__ = ["SeqPairwiseRecommender"]
+
+
+class SeqPairwiseRecommender(AbstractRecommender):
+    """Subclasses name their ``config_class`` and provide ``_build`` (sets ``self.dp``, hands the flat parameter buffer
+    to ``_setup`` and sets ``_step_launch``, one batch of the step kernel on cached addresses), ``_block_id_parts`` (the
+    64-float blocks of the flat buffer a batch touches) and ``_score_launch`` (skr_seq_scores)."""
+
+    def __init__(self, run_config, config):
+        super().__init__(run_config, config)
+        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
+        from ..parallel import init_from_env
+        self.dist = init_from_env()
+        if self.dist.world > 1:
+            raise NotImplementedError(f"{type(self).__name__} runs on one GPU: there is no sharded engine for it")
+        self.device = _hip.require_gpu()
+        self.user_pos_dict = self.dataset.train_data.to_user_dict_by_time()
+        last = np.full(self.num_users, -1, np.int32)
+        for u, items in self.user_pos_dict.items():
+            if len(items):
+                last[int(u)] = int(items[-1])
+        self._set_last_items(last)
+        self.step_losses = None  # device [n_steps, 2]: (bpr sum, l2) per step of the last epoch
+        self._build()
+
+    @classmethod
+    def detached(cls, num_users, num_items, model_config, last_items=None):
+        """the model's parameters, training step and scoring without a data set, logger or evaluator (timing tools);
+        ``last_items``: int32 [num_users], every user's last training item (default: item 0)"""
+        self = cls.__new__(cls)
+        self.config = cls.config_class(**model_config)
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.device = _hip.require_gpu()
+        self._set_last_items(np.zeros(self.num_users, np.int32) if last_items is None else last_items)
+        self.step_losses = None
+        self._build()
+        return self
+
+    def _set_last_items(self, last):
+        self._last_host = np.ascontiguousarray(last, dtype=np.int32)
+        self._last = torch.from_numpy(self._last_host).to(self.device)
+
+    def _setup(self, flat):
+        """``flat``: the model's parameters, one contiguous device buffer"""
+        self._flat = flat
+        # SKR_ADAM_BLOCK = k: the dense Adam blocked over k batches (1: one dense launch per batch); rows wider than one
+        # 64-float block take the dense launch per batch (the blocked forms name rows by their 64-float block)
+        self.adam_block = max(1, min(64, int(os.environ.get("SKR_ADAM_BLOCK", "32")))) if self.dp == 64 else 1
+        self.optimizer = DenseAdam(flat, lr=self.config.lr)
+
+    # ---- training --------------------------------------------------------------------------------
+    def _block_ids(self, cols, n_steps, bsz):
+        """int32 [n_steps * per_step]: step-major, the blocks of every batch; a short last batch is padded with -1 (an
+        id the blocked Adam skips), so every step has the same number of entries"""
+        parts = self._block_id_parts(*cols)
+        n = cols[0].numel()
+        ids = torch.full((len(parts), n_steps * bsz), -1, dtype=torch.int32, device=self.device)
+        for r, p in enumerate(parts):
+            ids[r, :n] = p
+        ids = ids.view(len(parts), n_steps, bsz).permute(1, 0, 2).reshape(n_steps, -1)
+        extra = self._block_ids_per_step()
+        if extra:
+            ids = torch.cat([ids, torch.tensor(extra, dtype=torch.int32, device=self.device).expand(n_steps, -1)], dim=1)
+        return ids.contiguous().view(-1), ids.shape[1]
+
+    def _block_ids_per_step(self):
+        return []
+
+    @on_compute_stream
+    def train_epoch(self, data_iter):
+        """one epoch; the per-step host work is one or two ctypes calls on cached integer addresses"""
+        L, opt, st = _hip.lib(), self.optimizer, _hip.stream()
+        S = _hip.SKR_LOSS_SLOTS
+        (cu, cl, cp, cn), bounds = data_iter.epoch_columns()
+        spread = torch.zeros((len(bounds), S, 2), dtype=torch.float32, device=self.device)
+        ploss = spread.data_ptr()
+        pcu, pcl, pcp, pcn = (c.data_ptr() for c in (cu, cl, cp, cn))
+        step = self._step_launch
+        kblk = self.adam_block
+        if kblk <= 1:
+            pflat, pgrad, pm, pv = (t.data_ptr() for t in (opt.flat, opt.grad, opt.m, opt.v))
+            n_par = opt.flat.numel()
+            for k, (a, b) in enumerate(bounds):
+                rc = step(pcu + 4 * a, pcl + 4 * a, pcp + 4 * a, pcn + 4 * a, b - a, ploss + 8 * S * k, st)
+                opt.t += 1
+                rc |= L.skr_adam_step(pflat, pgrad, pm, pv, n_par, opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.t, 1,
+                                      None, st)
+                if rc:
+                    _hip.check(rc)
+            self.step_losses = spread.sum(1)
+            return
+        # temporally blocked dense Adam (DenseAdam.begin_block): the rows no batch of a block touches get their k
+        # zero-gradient updates in one pass, the touched rows are stepped batch by batch -- the same updates in the same
+        # arithmetic as the loop above
+        ids, per = self._block_ids((cu, cl, cp, cn), len(bounds), data_iter.batch_size)
+        for s0 in range(0, len(bounds), kblk):
+            blk = bounds[s0:s0 + kblk]
+            opt.begin_block(ids[s0 * per:(s0 + len(blk)) * per], len(blk), per_step=per)
+            rc = 0
+            for k, (a, b) in enumerate(blk, start=s0):
+                rc |= step(pcu + 4 * a, pcl + 4 * a, pcp + 4 * a, pcn + 4 * a, b - a, ploss + 8 * S * k, st)
+                opt.hot_step()
+            if rc:
+                _hip.check(rc)
+        opt.end_blocks()
+        self.step_losses = spread.sum(1)
+
+    @on_compute_stream
+    def fit(self):
+        data_iter = SequentialPairwiseIterator(self.dataset.train_data, num_previous=1, num_next=1,
+                                               batch_size=self.config.batch_size, shuffle=True, drop_last=False)
+        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
+        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
+        for epoch in range(self.config.epochs):
+            self.train_epoch(data_iter)
+            cur_result = self.evaluate()
+            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
+            if early_stopping(cur_result):
+                self.logger.info("early stop")
+                break
+        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
+        return early_stopping.best_result
+
+    # ---- ranking ---------------------------------------------------------------------------------
+    def _require_history(self, users):
+        """the reference looks every user's last training item up and raises KeyError(user) for a user without one
+        (FPMC.py:147): the first such user, before anything is launched"""
+        u = np.asarray(users, dtype=np.int64).reshape(-1)
+        bad = (u < 0) | (u >= self.num_users)
+        bad[~bad] = self._last_host[u[~bad]] < 0
+        if bad.any():
+            raise KeyError(int(u[np.argmax(bad)]))
+
+    @on_compute_stream
+    def evaluate(self, test_users=None):
+        ev = self.evaluator
+        users = ev.user_pos_test.keys() if test_users is None else [u for u in test_users if u in ev.user_pos_test]
+        self._require_history(np.fromiter(users, dtype=np.int64))
+        return ev.evaluate(self, test_users)
+
+    def score_rows(self, d_users, out):
+        """evaluator hook: dense score rows of the int32 device users into ``out`` [B, num_items] (fp32, device)"""
+        _hip.check(self._score_launch(d_users, d_users.numel(), out, out.stride(0)))
+
+    def predict(self, users) -> np.ndarray:
+        """dense [len(users), num_items] scores (the reference's predict: FPMC.py:145-149, TransRec.py:156-160)"""
+        users = list(users)
+        self._require_history(users)
+        du = torch.as_tensor(np.asarray(users, dtype=np.int32)).to(self.device)
+        out = torch.empty((len(users), self.num_items), dtype=torch.float32, device=self.device)
+        _hip.check(self._score_launch(du, len(users), out, self.num_items))
+        return out.cpu().numpy()

@@ -1,12 +1,15 @@
 """``RankingEvaluator`` on the GPU (reference: skrec/utils/py/evaluator.py).
 
 Same constructor, same ``evaluate(model, test_users=None) -> MetricReport``, same metric names and
-column order.  Two device paths, both through libskrec_hip.so:
+column order.  Three device paths, all through libskrec_hip.so:
 
 * **fused** -- taken when the model exposes ``predict_factors() -> (user_table, item_table, bias|None)``
   (fp32 device tensors, 64 columns): ``skr_eval_fused_topk`` scores every test user against the whole
   catalogue on FP32 MFMA, masks train items and keeps the top-K without ever forming the [B, I]
   score matrix; ``skr_rank_metrics`` turns the lists into metric rows.
+* **device scores** -- taken when the model exposes ``score_rows(d_users, out)`` (FPMC, TransRec): the model
+  writes dense fp32 score rows of a chunk of users into a device buffer of about 256 MB, which is then masked and
+  ranked in place by the generic path's tail.
 * **generic** -- any object with ``predict(users) -> ndarray [B, I]`` (the reference's contract,
   evaluator.py:180-193): the scores are uploaded, train items masked (``skr_mask_train``) and
   ranked by ``skr_eval_scores``, the drop-in for ``cpp_evaluate_matrix``.
@@ -27,6 +30,7 @@ __all__ = ["MetricReport", "RankingEvaluator", "EarlyStopping"]
 
 _HOST_MEAN_MAX = 1 << 18
 _FUSED_CHUNK = 1 << 18     # users per fused launch (512 MB of candidate scratch): 4 workgroups per CU
+_SCORE_CHUNK_BYTES = 256 << 20   # one chunk of device score rows (models with a score_rows hook)
 
 
 class MetricReport(object):
@@ -205,6 +209,23 @@ class RankingEvaluator(object):
                                          _hip.ptr(fixed), None, _hip.stream()))
             ids[sel] = fixed
 
+    def _rank_score_rows(self, st, d_sc, du, margs, d_sums, host_rows):
+        """dense device scores [b, I] of the users ``du`` (modified in place): train items masked, ranked, metric rows
+        added to ``d_sums`` (and appended to ``host_rows`` unless it is None)"""
+        import torch
+        K, nm = self.max_top, self.metrics_num
+        b, n_items = d_sc.shape
+        _hip.check(_hip.lib().skr_mask_train(_hip.ptr(d_sc), b, n_items, n_items, _hip.ptr(du),
+                                             _hip.ptr(st["tr_ptr"]), _hip.ptr(st["tr_items"]), _hip.stream()))
+        # gather the truth rows of this batch into a compact CSR so that row b <-> user du[b]
+        rows = torch.empty((b, nm * K), dtype=torch.float32, device=d_sc.device)
+        te_ptr, te_items = _batch_truth(st, du)
+        _hip.check(_hip.lib().skr_eval_scores(_hip.ptr(d_sc), b, n_items, n_items, _hip.ptr(te_ptr),
+                                              _hip.ptr(te_items), margs, nm, K, _hip.ptr(rows), None,
+                                              _hip.ptr(d_sums), _hip.stream()))
+        if host_rows is not None:
+            host_rows.append(rows.cpu().numpy())
+
     def per_user_rows(self, model, test_users):
         """-> (rows float32 [n, n_metric*max_top] on the host or None, fp64 column sums, n)."""
         import torch
@@ -253,6 +274,18 @@ class RankingEvaluator(object):
                     margs, nm, _hip.ptr(rows), _hip.ptr(d_sums), _hip.stream()))
                 if keep_rows:
                     host_rows.append(rows[:b].cpu().numpy())
+        elif hasattr(model, "score_rows"):
+            # device score rows (FPMC, TransRec): model.score_rows(d_users, out) fills a [b, I] chunk of about
+            # _SCORE_CHUNK_BYTES in place, and the chunk is ranked where it lies -- no host round trip of the scores
+            n_items = int(model.num_items)
+            d_users = torch.from_numpy(users).to(dev)
+            chunk = max(1, min(n, _SCORE_CHUNK_BYTES // (4 * max(n_items, 1))))
+            d_sc = torch.empty((chunk, n_items), dtype=torch.float32, device=dev)
+            for s in range(0, n, chunk):
+                b = min(chunk, n - s)
+                du = d_users[s:s + b]
+                model.score_rows(du, d_sc[:b])
+                self._rank_score_rows(st, d_sc[:b], du, margs, d_sums, host_rows if keep_rows else None)
         else:
             # generic contract of the reference: predict() returns a dense [B, I] ndarray
             bs = max(int(self.batch_size), 1)
@@ -262,17 +295,7 @@ class RankingEvaluator(object):
                 assert isinstance(score, np.ndarray), "'ranking_score' must be an np.ndarray"
                 d_sc = torch.from_numpy(np.ascontiguousarray(score, np.float32)).to(dev)
                 du = torch.from_numpy(bu).to(dev)
-                b, n_items = d_sc.shape
-                _hip.check(_hip.lib().skr_mask_train(_hip.ptr(d_sc), b, n_items, n_items, _hip.ptr(du),
-                                                     _hip.ptr(st["tr_ptr"]), _hip.ptr(st["tr_items"]), _hip.stream()))
-                # gather the truth rows of this batch into a compact CSR so that row b <-> user bu[b]
-                rows = torch.empty((b, nm * K), dtype=torch.float32, device=dev)
-                te_ptr, te_items = _batch_truth(st, du)
-                _hip.check(_hip.lib().skr_eval_scores(_hip.ptr(d_sc), b, n_items, n_items, _hip.ptr(te_ptr),
-                                                      _hip.ptr(te_items), margs, nm, K, _hip.ptr(rows), None,
-                                                      _hip.ptr(d_sums), _hip.stream()))
-                if keep_rows:
-                    host_rows.append(rows.cpu().numpy())
+                self._rank_score_rows(st, d_sc, du, margs, d_sums, host_rows if keep_rows else None)
         sums = d_sums.cpu().numpy()
         rows = np.concatenate(host_rows, axis=0) if keep_rows and host_rows else None
         return rows, sums, n
