@@ -70,6 +70,17 @@ int skr_sampler_draws(skr_sampler* s, uint64_t* n);
  * exact-epoch call reports it as an error).  handed_over 1 = the slab path met a case it leaves to the serial kernel and
  * that kernel finished the stream. */
 int skr_sampler_last_epoch(skr_sampler* s, int64_t* h_info4);
+/* The slab path's resolver in the last exact epoch (test / measurement hook; synchronises): h_info2 = {most fixed-point rounds
+ * one slab took, slabs the rounds did not settle within their cap (32; SKR_SLAB_ROUNDS lowers it) and the one-lane walk
+ * decided}.  Both 0 when no slab was resolved by rounds (the serial path, SKR_SLAB_WALK=1). */
+int skr_sampler_slab_stats(skr_sampler* s, int64_t* h_info2);
+/* The next n tempered words of the stream (what std::mt19937's operator() returns, in order) to d_out (uint32[n], device);
+ * the stream moves past them.  Queues work only.  Long stretches take the jump-ahead generator (SKR_MT_JUMP=0: the
+ * one-workgroup generator, same words). */
+int skr_sampler_words(skr_sampler* s, int64_t n, uint32_t* d_out, void* stream);
+/* Host only, no GPU: the MT19937 state n words after (words624, pos), by jump-ahead polynomial (test hook of the generator
+ * above).  The result is the block that holds the next word and the position in it (out_pos < 624 unless n + pos <= 624). */
+int skr_mt_jump_host(const uint32_t* words624, int pos, int64_t n, uint32_t* out624, int* out_pos);
 
 /* One call of c_randint_choice (randint.h:75): `size` draws from [0, high), written to d_result.
  *   replace      as the reference's bool;

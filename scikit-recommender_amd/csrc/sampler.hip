@@ -15,8 +15,11 @@
 //   3. fast epoch              sample_fast_kernel: slot-keyed xoshiro128++ + rejection against
 //                              LDS-staged CSR positives; HBM-bound (8 B per sampled negative).
 #include "skr_common.h"
+#include "mt_jump.h"
 
+#include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 
 namespace {
@@ -134,6 +137,37 @@ __global__ void randint_serial_kernel(uint32_t* state, int* pos, unsigned long l
 // ------------------------------------------------------------------------------------------------
 constexpr int GEN_T = 256;
 
+// n words from position p of the block in mt2[cur] on, tempered, to raw[0 .. n); the state moves with them
+__device__ __forceinline__ void mt_gen_run(uint32_t (&mt2)[2][MT_N], int& cur, int& p, uint32_t* __restrict__ raw, int64_t n) {
+    const int tid = threadIdx.x;
+    int64_t k = 0;
+    while (k < n) {
+        if (p >= MT_N) {
+            const uint32_t* __restrict__ old = mt2[cur];
+            uint32_t* __restrict__ nw = mt2[cur ^ 1];
+            // new[i] = old[i+397] ^ mix(old[i], old[i+1])                     i in [0, 227)
+            if (tid < MT_N - MT_M) nw[tid] = old[tid + MT_M] ^ mt_mix(old[tid], old[tid + 1]);
+            __syncthreads();
+            // new[i] = new[i-227] ^ mix(old[i], old[i+1])                     i in [227, 454)
+            if (tid < MT_N - MT_M) nw[tid + 227] = nw[tid] ^ mt_mix(old[tid + 227], old[tid + 228]);
+            __syncthreads();
+            // new[i] = new[i-227] ^ mix(old[i], old[i+1])                     i in [454, 623);  new[623] = new[396] ^ mix(old[623], new[0])
+            if (tid < 169) nw[tid + 454] = nw[tid + 227] ^ mt_mix(old[tid + 454], old[tid + 455]);
+            if (tid == 169) nw[623] = nw[396] ^ mt_mix(old[623], nw[0]);
+            __syncthreads();
+            cur ^= 1;
+            p = 0;
+        }
+        const uint32_t* __restrict__ mt = mt2[cur];
+        const int64_t left = n - k;
+        const int m = static_cast<int>(left < (MT_N - p) ? left : (MT_N - p));
+        for (int t = tid; t < m; t += GEN_T) raw[k + t] = mt_temper(mt[p + t]);
+        k += m;
+        p += m;
+        // no barrier here: the next twist writes the OTHER copy, whose last readers passed the three barriers above
+    }
+}
+
 // n >= 0: generate exactly n words.  n < 0: generate at least -n words and stop on a block boundary of the generator
 // (the host does not know the stream position without a read-back); the count goes to *n_out.
 // `piece` / `piece_words`: the stretch may be produced in pieces (piece p = words [p * piece_words, (p + 1) * piece_words) of
@@ -168,32 +202,7 @@ __global__ __launch_bounds__(GEN_T) void mt_generate_kernel(const uint32_t* __re
         n = n - beg < piece_words ? n - beg : piece_words;
         if (n < 0) n = 0;
     }
-    int64_t k = 0;
-    while (k < n) {
-        if (p >= MT_N) {
-            const uint32_t* __restrict__ old = mt2[cur];
-            uint32_t* __restrict__ nw = mt2[cur ^ 1];
-            // new[i] = old[i+397] ^ mix(old[i], old[i+1])                     i in [0, 227)
-            if (tid < MT_N - MT_M) nw[tid] = old[tid + MT_M] ^ mt_mix(old[tid], old[tid + 1]);
-            __syncthreads();
-            // new[i] = new[i-227] ^ mix(old[i], old[i+1])                     i in [227, 454)
-            if (tid < MT_N - MT_M) nw[tid + 227] = nw[tid] ^ mt_mix(old[tid + 227], old[tid + 228]);
-            __syncthreads();
-            // new[i] = new[i-227] ^ mix(old[i], old[i+1])                     i in [454, 623);  new[623] = new[396] ^ mix(old[623], new[0])
-            if (tid < 169) nw[tid + 454] = nw[tid + 227] ^ mt_mix(old[tid + 454], old[tid + 455]);
-            if (tid == 169) nw[623] = nw[396] ^ mt_mix(old[623], nw[0]);
-            __syncthreads();
-            cur ^= 1;
-            p = 0;
-        }
-        const uint32_t* __restrict__ mt = mt2[cur];
-        const int64_t left = n - k;
-        const int m = static_cast<int>(left < (MT_N - p) ? left : (MT_N - p));
-        for (int t = tid; t < m; t += GEN_T) raw[k + t] = mt_temper(mt[p + t]);
-        k += m;
-        p += m;
-        // no barrier here: the next twist writes the OTHER copy, whose last readers passed the three barriers above
-    }
+    mt_gen_run(mt2, cur, p, raw, n);
     __syncthreads();
     if (carry) {
         for (int i = tid; i < MT_N; i += GEN_T) carry[i] = mt2[cur][i];
@@ -201,13 +210,131 @@ __global__ __launch_bounds__(GEN_T) void mt_generate_kernel(const uint32_t* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// 2e. the same stretch on the whole chip: jump-ahead pieces (host half and the argument: mt_jump.hip)
+// ------------------------------------------------------------------------------------------------
+// Stream indices count from the first word x_0 of the block the call starts in (the stored state; the call's first word is
+// x_pos).  The HEAD -- words up to x_{MT_HEAD-1}, one workgroup -- holds x_1 .. x_{19936+624}, the basis of every jump: the
+// block array that starts at word e + 1 is  XOR over the set coefficients c_i of x^e mod phi  of x_{1+i} .. x_{1+i+623}.
+// Piece g >= 1 starts at word MT_HEAD + (g - 1) J (a block boundary): the correlation kernel builds its first block from
+// x^(MT_HEAD - 1 + (g - 1) J) mod phi in JMP_NCH partial sums, and the piece kernel generates all pieces at once, one
+// workgroup each, with the one-workgroup generator's loop.  The words are the ones that generator writes, bit for bit.
+constexpr int MT_HEAD = 33 * MT_N;                                   // 20 592 >= 19 937 + 623 words of basis
+constexpr int JMP_CI = 1024;                                         // coefficients per correlation workgroup
+constexpr int JMP_NCH = (skr::MT_JUMP_DEG + JMP_CI - 1) / JMP_CI;    // 20 partial sums per piece
+constexpr int JMP_MAX_PIECES = 127;                                  // pieces after the head
+constexpr int JMP_MIN_WORDS = 16 * MT_N;                             // shortest piece: each piece adds a correlation
+
+// n as in mt_generate_kernel; the count goes to *n_out.  Writes the words before x_{MT_HEAD} (raw[0 .. MT_HEAD - pos)).
+__global__ __launch_bounds__(GEN_T) void mt_jump_head_kernel(const uint32_t* __restrict__ state, const int* __restrict__ pos_p,
+                                                             uint32_t* __restrict__ raw, int64_t n, int64_t* __restrict__ n_out) {
+    __shared__ uint32_t mt2[2][MT_N];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < MT_N; i += GEN_T) mt2[0][i] = state[i];
+    __syncthreads();
+    int cur = 0, p = *pos_p;
+    if (n < 0) {
+        const int64_t want = -n, r0 = MT_N - p;
+        n = want <= r0 ? r0 : r0 + ((want - r0 + MT_N - 1) / MT_N) * MT_N;
+    }
+    if (tid == 0) *n_out = n;
+    const int64_t head = MT_HEAD - p;
+    mt_gen_run(mt2, cur, p, raw, n < head ? n : head);
+}
+
+// grid (JMP_NCH, pieces): part[g][c][j] = XOR over the set coefficients i in chunk c of poly g of tempered x_{1+i+j}
+__global__ __launch_bounds__(256) void mt_jump_corr_kernel(const uint32_t* __restrict__ state, const int* __restrict__ pos_p,
+                                                           const uint32_t* __restrict__ raw, const uint32_t* __restrict__ polys,
+                                                           uint32_t* __restrict__ part) {
+    __shared__ uint32_t l_x[JMP_CI + MT_N - 1];
+    __shared__ uint16_t l_i[JMP_CI];                     // the chunk's set coefficients, ascending
+    __shared__ int l_off[JMP_CI / 32 + 1];
+    const int tid = threadIdx.x, c = blockIdx.x, g = blockIdx.y;
+    const int pos = *pos_p;
+    const int i0 = c * JMP_CI;
+    const int ni = skr::MT_JUMP_DEG - i0 < JMP_CI ? skr::MT_JUMP_DEG - i0 : JMP_CI;
+    for (int k = tid; k < ni + MT_N - 1; k += 256) {     // words x_{1+i0} .. x_{i0+ni+623} (all below x_{MT_HEAD})
+        const int w = 1 + i0 + k;
+        l_x[k] = w < pos ? mt_temper(state[w]) : raw[w - pos];
+    }
+    const int nw = (ni + 31) / 32;                       // coefficient bits from DEG on are zero
+    uint32_t cw = 0;
+    if (tid < nw) {
+        cw = polys[static_cast<size_t>(g) * MT_N + i0 / 32 + tid];
+        l_off[tid] = __popc(cw);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int w = 0; w < nw; ++w) {
+            const int k = l_off[w];
+            l_off[w] = run;
+            run += k;
+        }
+        l_off[nw] = run;
+    }
+    __syncthreads();
+    if (tid < nw) {
+        int o = l_off[tid];
+        for (uint32_t m = cw; m; m &= m - 1) l_i[o++] = static_cast<uint16_t>(32 * tid + __ffs(m) - 1);
+    }
+    __syncthreads();
+    // the same coefficients on every lane (no divergence), four per step so that twelve LDS reads are in flight: a loop
+    // over the bits one at a time waited out the latency of each read (40 us for the 22 pieces of bench.py's call)
+    const int cnt = l_off[nw];
+    const bool has2 = tid + 512 < MT_N;
+    const int t2 = has2 ? tid + 512 : tid;               // lanes without a third word re-read their first one, unused
+    uint32_t a0 = 0, a1 = 0, a2 = 0;
+    int k = 0;
+    for (; k + 4 <= cnt; k += 4) {
+        const int i0_ = l_i[k], i1 = l_i[k + 1], i2 = l_i[k + 2], i3 = l_i[k + 3];
+        a0 ^= l_x[i0_ + tid] ^ l_x[i1 + tid] ^ l_x[i2 + tid] ^ l_x[i3 + tid];
+        a1 ^= l_x[i0_ + tid + 256] ^ l_x[i1 + tid + 256] ^ l_x[i2 + tid + 256] ^ l_x[i3 + tid + 256];
+        a2 ^= l_x[i0_ + t2] ^ l_x[i1 + t2] ^ l_x[i2 + t2] ^ l_x[i3 + t2];
+    }
+    for (; k < cnt; ++k) {
+        const int i = l_i[k];
+        a0 ^= l_x[i + tid];
+        a1 ^= l_x[i + tid + 256];
+        a2 ^= l_x[i + t2];
+    }
+    uint32_t* o = part + (static_cast<size_t>(g) * JMP_NCH + c) * MT_N;
+    o[tid] = a0;
+    o[tid + 256] = a1;
+    if (has2) o[tid + 512] = a2;
+}
+
+// one workgroup per piece g + 1: words [MT_HEAD + g J, MT_HEAD + (g + 1) J) of the stretch, clipped to its end
+__global__ __launch_bounds__(GEN_T) void mt_jump_piece_kernel(const int* __restrict__ pos_p, uint32_t* __restrict__ raw,
+                                                              const int64_t* __restrict__ n_p, const uint32_t* __restrict__ part,
+                                                              int64_t piece_words) {
+    __shared__ uint32_t mt2[2][MT_N];
+    const int tid = threadIdx.x, g = blockIdx.x;
+    const int pos = *pos_p;
+    const int64_t n = *n_p;
+    const int64_t beg = MT_HEAD + g * piece_words;
+    int64_t end = beg + piece_words;
+    if (end > pos + n) end = pos + n;
+    if (end <= beg) return;
+    const uint32_t* pp = part + static_cast<size_t>(g) * JMP_NCH * MT_N;
+    for (int j = tid; j < MT_N; j += GEN_T) {
+        uint32_t acc = 0;
+        for (int c = 0; c < JMP_NCH; ++c) acc ^= pp[c * MT_N + j];
+        mt2[0][j] = mt_untemper(acc);
+    }
+    __syncthreads();
+    int cur = 0, p = 0;
+    mt_gen_run(mt2, cur, p, raw + (beg - pos), end - beg);
+}
+
 // 2c. advance the stored state by `consumed` words of the buffer generated above.
 // The tempered words of a whole block ARE that block's state (tempering is a bijection).
+// ctl == nullptr: `consumed_n` words.
 __global__ void mt_commit_kernel(uint32_t* state, int* pos_p, unsigned long long* draws,
                                  const uint32_t* __restrict__ raw, int64_t n_raw, const int64_t* ctl,
-                                 const int64_t* __restrict__ n_raw_dev) {
+                                 const int64_t* __restrict__ n_raw_dev, int64_t consumed_n = 0) {
     if (n_raw_dev) n_raw = *n_raw_dev;
-    const int64_t consumed = ctl[1];
+    const int64_t consumed = ctl ? ctl[1] : consumed_n;
     const int p0 = *pos_p;
     const int64_t r0 = MT_N - p0;  // words of the current block that were still unread
     __shared__ int64_t kb_s;
@@ -251,6 +378,9 @@ constexpr int SL_NRAW = 5;      // words generated
 constexpr int SL_SLAB_S = 6;    // S at the start of the slab being scattered
 constexpr int SL_SLAB_N = 7;    // draws of that slab that were consumed (0: nothing to scatter)
 constexpr int SL_STATUS = 8;    // 1 = the last exact epoch ended with every slot filled
+constexpr int SL_GEN_N = 9;     // words generated (the one-workgroup path and skr_sampler_words)
+constexpr int SL_RES_ROUNDS = 10;   // most fixed-point rounds a slab's resolve took in the last exact epoch
+constexpr int SL_RES_WALKS = 11;    // slabs of it that the rounds did not settle: the one-lane walk decided
 
 constexpr int AS_T = 1024;
 constexpr int AS_PER = 16;
@@ -566,6 +696,8 @@ constexpr int SLAB_ROWS = 1024;        // row offsets staged per detect workgrou
 constexpr int SLAB_EV = 1024;          // events per slab the resolver holds
 constexpr int SLAB_BND = 8;            // candidate owners per event the resolver looks at
 constexpr int32_t EV_LEMIRE = -2, EV_UNKNOWN = -1;
+constexpr int RES_PER = SLAB_EV / 256;  // events per resolver lane in the fixed-point rounds
+constexpr int RES_ROUNDS = 32;          // rounds before the resolver falls back to the one-lane walk
 
 struct SlabArgs {
     const uint32_t* raw;
@@ -586,6 +718,8 @@ struct SlabArgs {
     int32_t* ev_uhi;             // [SLAB_B]
     unsigned long long* rej_bits;// [SLAB_B / 64]
     int32_t* out;
+    int walk;                    // 1: the resolver walks the events on one lane only (SKR_SLAB_WALK=1)
+    int max_rounds;              // fixed-point rounds before the walk decides (RES_ROUNDS; SKR_SLAB_ROUNDS lowers it)
 };
 
 __device__ __forceinline__ int slab_window(const SlabArgs& a, int j) {
@@ -683,6 +817,7 @@ __global__ __launch_bounds__(256) void slab_resolve_kernel(SlabArgs a) {
     __shared__ int32_t l_bnd[SLAB_EV][SLAB_BND];          // optr[uhi] - optr[uhi - i]  (>= 0; INT32_MAX: no such user)
     __shared__ int l_cnt[256];
     __shared__ int s_total;
+    __shared__ int l_wave[4], s_end, s_r;
     constexpr int32_t EV_REJECTED = -3;
     const int tid = threadIdx.x;
     const int len = slab_len(a);
@@ -736,13 +871,96 @@ __global__ __launch_bounds__(256) void slab_resolve_kernel(SlabArgs a) {
         }
     }
     __syncthreads();
-    // the serial chain: one lane, everything it reads is in LDS
+    const int64_t S = a.ctl[SL_S];
+    const int64_t remaining = a.n_slots - S;
+    // The chain over the events as a fixed-point iteration on every lane (the argument of exact_assign_kernel): with r(e) =
+    // the rejections before event e under the current flags, every event is decided again at its slot S + j - r(e), until
+    // no flag before the first event that ends the walk changes.  The flags are then the walk's: an event's r is right once
+    // the flags before it are, so every round settles at least one more event (two or three rounds settle a slab of sparse
+    // data).  Past RES_ROUNDS rounds the one-lane walk below decides.  s_end = 4 * (first event that ends the walk, E if
+    // none) + how it ends: 1 every slot is filled before its draw, 2 the walk gives up (SL_FALLBACK).
+    bool settled = false;
+    int rounds = 0;
+    if (!too_many && !a.walk) {
+        const int lane = tid & 63, wv = tid >> 6;
+        uint32_t rej = 0;        // bit q: event tid * RES_PER + q is rejected
+        for (int q = 0; q < RES_PER; ++q) {
+            const int e = tid * RES_PER + q;
+            if (e < E && l_uhi[e] == EV_LEMIRE) rej |= 1u << q;
+        }
+        for (int round = 0; round < a.max_rounds && !settled; ++round) {
+            ++rounds;
+            const int cnt = __popc(rej);
+            const int incl = skr::wave_incl_scan(cnt);
+            if (lane == 63) l_wave[wv] = incl;
+            if (tid == 0) s_end = E << 2;
+            __syncthreads();
+            int r = incl - cnt;
+            for (int w = 0; w < wv; ++w) r += l_wave[w];
+            uint32_t nrej = 0;
+            int my_end = E << 2, my_r = 0;
+            for (int q = 0; q < RES_PER; ++q) {
+                const int e = tid * RES_PER + q;
+                if (e >= E) break;
+                const int j = l_j[e];
+                int kind = 0;
+                bool rejected = false;
+                if (j - r >= remaining) {
+                    kind = 1;
+                } else if (r > slab_window(a, j)) {
+                    kind = 2;
+                } else {
+                    const int32_t uhi = l_uhi[e];
+                    if (uhi == EV_LEMIRE) {
+                        rejected = true;
+                    } else if (uhi < 0) {
+                        kind = 2;
+                    } else {
+                        const int64_t need = l_q0[e] - (S + j - r) / a.num_neg;
+                        int i = 0;
+                        while (i < SLAB_BND && static_cast<int64_t>(l_bnd[e][i]) < need) ++i;
+                        if (i == SLAB_BND) kind = 2;
+                        else rejected = (l_mask[e] >> i) & 1u;
+                    }
+                }
+                if (kind) {
+                    my_end = (e << 2) | kind;
+                    my_r = r;
+                    break;
+                }
+                if (rejected) {
+                    nrej |= 1u << q;
+                    ++r;
+                }
+            }
+            if (my_end < (E << 2)) atomicMin(&s_end, my_end);
+            __syncthreads();
+            const int e_end = s_end >> 2;
+            const int before = e_end - tid * RES_PER;    // this lane's events before the end
+            const uint32_t pmask = before <= 0 ? 0u : before >= RES_PER ? (1u << RES_PER) - 1u : (1u << before) - 1u;
+            const bool changed = ((nrej ^ rej) & pmask) != 0;
+            rej = nrej;
+            if (!__syncthreads_or(changed)) {
+                settled = true;
+                if (e_end < E && tid == e_end / RES_PER) s_r = my_r;
+                if (e_end == E && tid == 0) s_r = l_wave[0] + l_wave[1] + l_wave[2] + l_wave[3];
+                for (int q = 0; q < RES_PER; ++q)
+                    if (q < before && ((rej >> q) & 1u)) l_uhi[tid * RES_PER + q] = EV_REJECTED;
+            }
+        }
+        __syncthreads();
+    }
     if (tid == 0) {
-        const int64_t S = a.ctl[SL_S];
-        const int64_t remaining = a.n_slots - S;
         int r = 0;
         bool give_up = too_many;
-        for (int e = 0; e < E && !give_up; ++e) {
+        if (settled) {
+            r = s_r;
+            give_up = (s_end & 3) == 2;
+        }
+        if (rounds > a.ctl[SL_RES_ROUNDS]) a.ctl[SL_RES_ROUNDS] = rounds;
+        if (rounds && !settled) a.ctl[SL_RES_WALKS] += 1;
+        // the serial chain: one lane, everything it reads is in LDS
+        for (int e = 0; e < E && !give_up && !settled; ++e) {
             const int j = l_j[e];
             if (j - r >= remaining) break;                       // every slot is filled before this draw is reached
             if (r > slab_window(a, j)) { give_up = true; break; }  // more rejections than the detector allowed for
@@ -817,6 +1035,7 @@ __global__ __launch_bounds__(SLAB_T) void slab_scatter_kernel(SlabArgs a) {
 
 __global__ void slab_begin_kernel(int64_t* ctl) {
     ctl[SL_S] = 0; ctl[SL_D] = 0; ctl[SL_FALLBACK] = 0; ctl[SL_NRAW] = 0; ctl[SL_SLAB_S] = 0; ctl[SL_SLAB_N] = 0; ctl[SL_STATUS] = 0;
+    ctl[SL_RES_ROUNDS] = 0; ctl[SL_RES_WALKS] = 0;
 }
 __global__ void slab_end_kernel(int64_t* ctl, int64_t n_slots) { ctl[SL_STATUS] = (ctl[SL_S] >= n_slots) ? 1 : 2; }
 
@@ -971,6 +1190,10 @@ struct skr_sampler {
     unsigned long long* d_rej_bits = nullptr;
     uint32_t* d_ev_mask = nullptr;
     int32_t* d_ev_uhi = nullptr;
+    // jump-ahead generator (2e): per piece length J, x^(MT_HEAD - 1 + k J) mod phi on the device (JMP_MAX_PIECES slots) and how
+    // many are there; the correlation's partial sums
+    std::map<int64_t, std::pair<uint32_t*, int>> jump_polys;
+    uint32_t* d_jpart = nullptr;
 };
 
 namespace skr {
@@ -1025,6 +1248,8 @@ int skr_sampler_destroy(skr_sampler* s) {
     (void)hipFree(s->d_rej_bits);
     (void)hipFree(s->d_ev_mask);
     (void)hipFree(s->d_ev_uhi);
+    for (auto& kv : s->jump_polys) (void)hipFree(kv.second.first);
+    (void)hipFree(s->d_jpart);
     delete s;
     return SKR_OK;
 }
@@ -1068,6 +1293,13 @@ int skr_sampler_last_epoch(skr_sampler* s, int64_t* h_info4) {
     return SKR_OK;
 }
 
+int skr_sampler_slab_stats(skr_sampler* s, int64_t* h_info2) {
+    SKR_REQUIRE(s && h_info2, "skr_sampler_slab_stats: NULL argument");
+    SKR_HIP(hipDeviceSynchronize());
+    SKR_HIP(hipMemcpy(h_info2, s->d_ctl + SL_RES_ROUNDS, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SKR_OK;
+}
+
 int skr_randint_choice(skr_sampler* s, int high, int size, int replace, const float* d_prob,
                        const int32_t* d_exclusion, int n_exclusion, int32_t* d_result, void* stream) {
     SKR_REQUIRE(s && d_result, "skr_randint_choice: NULL argument");
@@ -1089,11 +1321,45 @@ int skr_randint_choice(skr_sampler* s, int high, int size, int replace, const fl
     return SKR_OK;
 }
 
+static bool env_is(const char* name, const char* value) {
+    const char* v = getenv(name);
+    return v && !strcmp(v, value);
+}
+
+// Long stretches of the word stream take the jump-ahead form (2e); SKR_MT_JUMP=0 keeps the one-workgroup generator.
+static bool jump_applies(int64_t want) { return want >= 2 * MT_HEAD && !env_is("SKR_MT_JUMP", "0"); }
+
+// Queues the stretch into s->d_raw in the jump-ahead form: n >= 0 exactly n words, n < 0 at least -n words ending on a block
+// boundary; the count goes to *d_n.  Only queues work: the polynomials of a piece length seen before are on the device already.
+static int queue_jump_generate(skr_sampler* s, int64_t n, int64_t* d_n, hipStream_t st) {
+    const int64_t want = n < 0 ? -n : n;
+    const int64_t rest = want + 2 * MT_N - MT_HEAD;        // the stretch ends below word want + 2 * 624 (from x_0)
+    int64_t J = JMP_MIN_WORDS;
+    while ((rest + J - 1) / J > JMP_MAX_PIECES) J <<= 1;
+    const int np = static_cast<int>((rest + J - 1) / J);
+    auto& dp = s->jump_polys[J];
+    if (dp.second < np) {
+        std::vector<const uint32_t*> h;
+        if (!skr::mt_jump_polys(MT_HEAD - 1, J, np, h)) return skr::fail(SKR_EHIP, "MT19937: characteristic polynomial not found");
+        if (!dp.first) SKR_HIP(hipMalloc(&dp.first, static_cast<size_t>(JMP_MAX_PIECES) * MT_N * sizeof(uint32_t)));
+        for (int k = dp.second; k < np; ++k)     // the host copies live as long as the process
+            SKR_HIP(hipMemcpyAsync(dp.first + static_cast<size_t>(k) * MT_N, h[k], MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        dp.second = np;
+    }
+    if (!s->d_jpart) SKR_HIP(hipMalloc(&s->d_jpart, static_cast<size_t>(JMP_MAX_PIECES) * JMP_NCH * MT_N * sizeof(uint32_t)));
+    hipLaunchKernelGGL(mt_jump_head_kernel, dim3(1), dim3(GEN_T), 0, st, s->d_state, s->d_pos, s->d_raw, n, d_n);
+    hipLaunchKernelGGL(mt_jump_corr_kernel, dim3(JMP_NCH, np), dim3(256), 0, st, s->d_state, s->d_pos, s->d_raw, dp.first, s->d_jpart);
+    hipLaunchKernelGGL(mt_jump_piece_kernel, dim3(np), dim3(GEN_T), 0, st, s->d_pos, s->d_raw, d_n, s->d_jpart, J);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
 // the exact epoch on ONE workgroup: generate a stretch of the word stream, assign, commit, repeat (dense data, tiny calls,
 // SKR_EXACT_PATH=serial)
 static int run_exact_epoch_serial(skr_sampler* s, int num_items, int n_users, const int64_t* d_rowptr,
                            const int32_t* d_pos_sorted, const int64_t* d_drawptr, int num_neg, int64_t n_slots,
                            int32_t* d_out, hipStream_t st) {
+    SKR_HIP(hipMemsetAsync(s->d_ctl + SL_RES_ROUNDS, 0, 2 * sizeof(int64_t), st));     // no slab is resolved here
     int64_t filled = 0;
     int pos = 0;
     while (filled < n_slots) {
@@ -1111,9 +1377,13 @@ static int run_exact_epoch_serial(skr_sampler* s, int num_items, int n_users, co
             SKR_HIP(hipMalloc(&s->d_raw, static_cast<size_t>(n_gen) * sizeof(uint32_t)));
             s->raw_cap = static_cast<size_t>(n_gen);
         }
-        hipLaunchKernelGGL(mt_generate_kernel, dim3(1), dim3(GEN_T), 0, st, s->d_state, s->d_pos, s->d_raw, n_gen,
-                           static_cast<int64_t*>(nullptr));
-        SKR_LAUNCH_CHECK();
+        if (jump_applies(n_gen)) {
+            if (int rc = queue_jump_generate(s, n_gen, s->d_ctl + SL_GEN_N, st)) return rc;
+        } else {
+            hipLaunchKernelGGL(mt_generate_kernel, dim3(1), dim3(GEN_T), 0, st, s->d_state, s->d_pos, s->d_raw, n_gen,
+                               static_cast<int64_t*>(nullptr));
+            SKR_LAUNCH_CHECK();
+        }
         if (d_drawptr)
             hipLaunchKernelGGL(exact_assign_kernel<true>, dim3(1), dim3(AS_T), 0, st, s->d_raw, n_gen,
                                static_cast<uint32_t>(num_items), d_rowptr, n_users, d_pos_sorted, 1, n_slots, filled,
@@ -1165,39 +1435,48 @@ static int run_exact_epoch_slabs(skr_sampler* s, int num_items, int n_users, con
         SKR_HIP(hipMalloc(&s->d_ev_mask, SLAB_B * sizeof(uint32_t)));
         SKR_HIP(hipMalloc(&s->d_ev_uhi, SLAB_B * sizeof(int32_t)));
     }
-    // the word stream is a serial chain on one workgroup (~0.8 G words/s): it is produced in pieces on a stream of the
-    // sampler's own, and the slabs of the caller's stream start as soon as the piece they read is there
     constexpr int64_t PIECE = int64_t{1} << 21;
-    const int n_pieces = static_cast<int>((want + MT_N + PIECE - 1) / PIECE);
-    if (!s->gen_stream) {
-        SKR_HIP(hipStreamCreateWithFlags(&s->gen_stream, hipStreamNonBlocking));
-        SKR_HIP(hipEventCreateWithFlags(&s->start_event, hipEventDisableTiming));
-        SKR_HIP(hipMalloc(&s->d_carry, (MT_N + 1) * sizeof(uint32_t)));
-    }
-    while (static_cast<int>(s->gen_events.size()) < n_pieces) {
-        hipEvent_t e;
-        SKR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s->gen_events.push_back(e);
-    }
+    int n_pieces = 0, pieces_awaited = 0;
     hipLaunchKernelGGL(slab_begin_kernel, dim3(1), dim3(1), 0, st, s->d_ctl);
-    // SKR_SAMPLER_ONE_STREAM=1: everything on the caller's stream (several processes sharing ONE GPU -- rehearsals of the
-    // multi-rank paths -- oversubscribe the hardware queues, and cross-queue waits then cost milliseconds)
-    static const bool env_one_stream = getenv("SKR_SAMPLER_ONE_STREAM") && !strcmp(getenv("SKR_SAMPLER_ONE_STREAM"), "1");
-    // a call of one piece has nothing to generate BESIDE: the first slab waits for the whole stretch either way, and the two
-    // stream hand-offs (~25 us) would be all the side stream adds
-    const bool one_stream = env_one_stream || n_pieces == 1;
-    hipStream_t gst = one_stream ? st : s->gen_stream;
-    if (!one_stream) {
-        SKR_HIP(hipEventRecord(s->start_event, st));
-        SKR_HIP(hipStreamWaitEvent(gst, s->start_event, 0));
+    if (jump_applies(want)) {
+        // in line: the pieces run side by side in one launch and end together, and the first slab needs its words from the head
+        // and the first piece, so a side stream would start no slab earlier (it would add two stream hand-offs).  What the
+        // slabs wait for: the head (~26 us), the correlation and one piece -- at most 16 blocks (~12 us) for calls up to
+        // 1.27 M words, 1 024 blocks (~0.8 ms) for the 56 M words of a whole epoch of bench.py's data
+        if (int rc = queue_jump_generate(s, -want, s->d_ctl + SL_NRAW, st)) return rc;
+    } else {
+        // the one-workgroup generator (~0.8 G words/s) in pieces on a stream of the sampler's own: the slabs of the caller's
+        // stream start as soon as the piece they read is there
+        n_pieces = static_cast<int>((want + MT_N + PIECE - 1) / PIECE);
+        if (!s->gen_stream) {
+            SKR_HIP(hipStreamCreateWithFlags(&s->gen_stream, hipStreamNonBlocking));
+            SKR_HIP(hipEventCreateWithFlags(&s->start_event, hipEventDisableTiming));
+            SKR_HIP(hipMalloc(&s->d_carry, (MT_N + 1) * sizeof(uint32_t)));
+        }
+        while (static_cast<int>(s->gen_events.size()) < n_pieces) {
+            hipEvent_t e;
+            SKR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            s->gen_events.push_back(e);
+        }
+        // SKR_SAMPLER_ONE_STREAM=1: everything on the caller's stream (several processes sharing ONE GPU -- rehearsals of the
+        // multi-rank paths -- oversubscribe the hardware queues, and cross-queue waits then cost milliseconds)
+        static const bool env_one_stream = env_is("SKR_SAMPLER_ONE_STREAM", "1");
+        // a call of one piece has nothing to generate BESIDE: the first slab waits for the whole stretch either way, and the two
+        // stream hand-offs (~25 us) would be all the side stream adds
+        const bool one_stream = env_one_stream || n_pieces == 1;
+        hipStream_t gst = one_stream ? st : s->gen_stream;
+        if (!one_stream) {
+            SKR_HIP(hipEventRecord(s->start_event, st));
+            SKR_HIP(hipStreamWaitEvent(gst, s->start_event, 0));
+        }
+        for (int pc = 0; pc < n_pieces; ++pc) {
+            hipLaunchKernelGGL(mt_generate_kernel, dim3(1), dim3(GEN_T), 0, gst, s->d_state, s->d_pos, s->d_raw, -want,
+                               s->d_ctl + SL_NRAW, s->d_carry, pc, PIECE);
+            if (!one_stream) SKR_HIP(hipEventRecord(s->gen_events[pc], gst));
+        }
+        SKR_LAUNCH_CHECK();
+        pieces_awaited = one_stream ? n_pieces : 0;
     }
-    for (int pc = 0; pc < n_pieces; ++pc) {
-        hipLaunchKernelGGL(mt_generate_kernel, dim3(1), dim3(GEN_T), 0, gst, s->d_state, s->d_pos, s->d_raw, -want,
-                           s->d_ctl + SL_NRAW, s->d_carry, pc, PIECE);
-        if (!one_stream) SKR_HIP(hipEventRecord(s->gen_events[pc], gst));
-    }
-    SKR_LAUNCH_CHECK();
-    int pieces_awaited = one_stream ? n_pieces : 0;
     SlabArgs a{};
     a.raw = s->d_raw;
     a.high = static_cast<uint32_t>(num_items);
@@ -1218,6 +1497,12 @@ static int run_exact_epoch_slabs(skr_sampler* s, int num_items, int n_users, con
     a.ev_mask = s->d_ev_mask;
     a.ev_uhi = s->d_ev_uhi;
     a.out = d_out;
+    a.walk = env_is("SKR_SLAB_WALK", "1") ? 1 : 0;
+    a.max_rounds = RES_ROUNDS;
+    if (const char* r = getenv("SKR_SLAB_ROUNDS")) {
+        const int v = atoi(r);
+        a.max_rounds = v < 1 ? 1 : v > RES_ROUNDS ? RES_ROUNDS : v;
+    }
     // slab length: about 256 expected rejections per slab (each shows up as a few events, the resolver holds SLAB_EV)
     int slab_b = SLAB_B;
     while (slab_b > 4096 && reject_rate * slab_b > 256.0) slab_b >>= 1;
@@ -1374,6 +1659,33 @@ int skr_sample_epoch_exact_counts(skr_sampler* s, int num_items, int n_users, co
     if (n_draws == 0) return SKR_OK;
     return run_exact_epoch(s, num_items, n_users, d_rowptr, d_excl_sorted, d_drawptr, 1, n_draws, nnz, d_out, st,
                            "skr_sample_epoch_exact_counts");
+}
+
+int skr_sampler_words(skr_sampler* s, int64_t n, uint32_t* d_out, void* stream) {
+    SKR_REQUIRE(s && d_out, "skr_sampler_words: NULL argument");
+    SKR_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "skr_sampler_words: n = %lld outside [0, 2^31)", static_cast<long long>(n));
+    if (n == 0) return SKR_OK;
+    hipStream_t st = skr::as_stream(stream);
+    const size_t cap = static_cast<size_t>(n) + 2 * MT_N;
+    if (cap > s->raw_cap) {
+        if (s->d_raw) SKR_HIP(hipFree(s->d_raw));
+        s->d_raw = nullptr;
+        s->raw_cap = 0;
+        SKR_HIP(hipMalloc(&s->d_raw, cap * sizeof(uint32_t)));
+        s->raw_cap = cap;
+    }
+    int64_t* d_n = s->d_ctl + SL_GEN_N;
+    if (jump_applies(n)) {
+        if (int rc = queue_jump_generate(s, -n, d_n, st)) return rc;
+    } else {
+        hipLaunchKernelGGL(mt_generate_kernel, dim3(1), dim3(GEN_T), 0, st, s->d_state, s->d_pos, s->d_raw, -n, d_n);
+    }
+    SKR_LAUNCH_CHECK();
+    SKR_HIP(hipMemcpyAsync(d_out, s->d_raw, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(mt_commit_kernel, dim3(1), dim3(256), 0, st, s->d_state, s->d_pos, s->d_draws, s->d_raw,
+                       static_cast<int64_t>(0), static_cast<const int64_t*>(nullptr), d_n, n);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
 }
 
 int skr_sample_epoch_fast(uint64_t seed, uint64_t epoch, int64_t slot_offset, int num_items, int n_users,
