@@ -471,6 +471,20 @@ int skr_adam_block_hot_tf(float* d_p, float* d_g, float* d_m, float* d_v, int64_
                           float eps, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids,
                           int64_t offset_floats, int stride_floats, int32_t* d_claim, void* stream);
 
+/* The same three entry points with torch.optim.Adam(weight_decay=...)'s arithmetic (HGN.py:182): every element's gradient
+ * becomes g' = fmaf(weight_decay, p, g) -- ONE rounding, as torch's grad.add(param, alpha=weight_decay) -- with the p the
+ * step starts from, then the update of skr_adam_step.  A block without a gradient is therefore not at rest: the cold pass
+ * runs its k updates, each with g' = weight_decay * p of the current p, back to back in registers, and so do the hot
+ * step's catch-up updates; only elements whose p, m and v are all +0 (padded columns, padding rows) are left alone,
+ * which is what the arithmetic gives for them (eps > 0).  Blocked == one skr_adam_step_wd per step, bit for bit. */
+int skr_adam_step_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t step_t, int zero_grad, uint8_t* d_touch, void* stream);
+int skr_adam_block_cold_wd(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream);
+int skr_adam_block_hot_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids,
+                          int64_t offset_floats, int stride_floats, int32_t* d_claim, void* stream);
+
 /* One training step of BPRMF in ONE launch: skr_bpr_step (score rows == regulariser rows, loss_scale 1) and the hot rows'
  * part of the blocked dense Adam together, for a k-step block whose batches are known (replaces, per step, the pair
  * skr_bpr_step_spread + skr_adam_block_hot; BPRMF.py:108-127).  Hot rows are evaluated lazily: the wavefronts that read a
@@ -697,6 +711,47 @@ int skr_seq_scores(int mode, const float* d_user_table, const float* d_last_tabl
                    const float* d_item_table2, const float* d_transition, const float* d_item_bias, const int32_t* d_users,
                    int B, const int32_t* d_last_item, int n_users, int n_items, int dim, float* d_out, int64_t ld,
                    void* stream);
+
+/* ============================================================================================
+ * R -- HGN, Hierarchical Gating Networks (csrc/hgn.hip)
+ * replaces: _HGN._forward_user / forward / predict and HGN.fit's step (recommender/HGN.py:101-163,194-207).
+ * Rows are 64 floats (dim must be 64: narrower embeddings zero-padded by the caller; the two gate matrices have to fit
+ * LDS).  Tables: d_U [n_users, 64]; d_E (item_embeddings), d_W2 [n_rows, 64] and d_b2 [n_rows] with n_rows = items + 1,
+ * row pad_idx being the padding row (-1: none): it reads as zeros in a window and never receives a gradient.
+ * d_gates: the shared parameters, SKR_HGN_GATE_FLOATS(L) floats, 16-byte aligned:
+ *   feature_gate_item.weight [64][64] (out, in) | feature_gate_user.weight [64][64] | feature_gate_item.bias [64] |
+ *   feature_gate_user.bias [64] | instance_gate_item [64] | instance_gate_user TRANSPOSED, [L][64]
+ * Per instance (u, window s_1..s_L, positives t_1..t_T, negatives t_T+1..t_2T), with p = U[u], e_l = E[s_l]:
+ *   gate_l = sigmoid(Wi e_l + bi + Wu p + bu), g_l = e_l * gate_l, a_l = sigmoid(<g_l, w_item> + (p^T W_user)_l),
+ *   union = sum_l a_l g_l / sum_l a_l (padding positions have g_l = 0 and count in the denominator),
+ *   q = p + union + sum_l e_l,   y_t = b2[t] + <W2[t], q>.
+ * Limits: 1 <= seq_L <= SKR_HGN_MAX_L, 1 <= seq_T <= SKR_HGN_MAX_T (the window, the instance gates and the targets of
+ * an instance are held one per lane of a wavefront).
+ * ========================================================================================== */
+#define SKR_HGN_MAX_L 32
+#define SKR_HGN_MAX_T 16
+#define SKR_HGN_MAX_BLOCKS 256
+#define SKR_HGN_GATE_FLOATS(L) (2 * 64 * 64 + 3 * 64 + 64 * (L))
+/* One training batch, forward and backward: d_u int32[n], d_seq int32[n][seq_L], d_pos / d_neg int32[n][seq_T].  The
+ * batch's sum over instances and pairs of -logsigmoid(y_pos_k - y_neg_k) is ADDED to word 0 of the d_loss pairs (float
+ * [2 * loss_slots], loss_slots 1 or SKR_LOSS_SLOTS, spread over the workgroups as skr_fpmc_step; word 1 is left alone:
+ * there is no l2 term, the regulariser is the optimiser's weight decay).  Row gradients (d_gU, d_gE, d_gW2, d_gb2) are
+ * atomic scatter-adds; the padding row gets none.  The gate parameters' gradients are named by every instance and are
+ * summed in a FIXED order (per wavefront, per workgroup, then the workgroups in order in a second launch) and ADDED to
+ * d_ggates (layout of d_gates): two calls on the same inputs give the same bits for them.  An instance with an id
+ * outside [0, n_users) / [0, n_rows) is skipped.  d_work: float[SKR_HGN_MAX_BLOCKS * SKR_HGN_GATE_FLOATS(seq_L)] scratch,
+ * no initial contents, not to be shared by calls that may run at the same time. */
+int skr_hgn_step(const float* d_U, const float* d_E, const float* d_W2, const float* d_b2, const float* d_gates,
+                 const int32_t* d_u, const int32_t* d_seq, const int32_t* d_pos, const int32_t* d_neg, int n, int n_users,
+                 int n_rows, int pad_idx, int dim, int seq_L, int seq_T, float* d_gU, float* d_gE, float* d_gW2, float* d_gb2,
+                 float* d_ggates, float* d_work, float* d_loss, int loss_slots, void* stream);
+/* Query rows: d_Q[u][0..63] = q of user u = d_users[i] (d_users NULL: u = i) from the window d_windows[i][0..seq_L), so
+ * that the model's score of item t is <d_Q[u], W2[t]> + b2[t] (skr_eval_fused_topk, skr_score_matrix).  A window with an
+ * entry outside [0, n_rows) -- by convention a negative first entry marks a user without training history -- gives a row
+ * of NaN (callers raise before they ask: the reference raises KeyError, HGN.py:223).  Users out of range are skipped. */
+int skr_hgn_queries(const float* d_U, const float* d_E, const float* d_gates, const int32_t* d_users, int n,
+                    const int32_t* d_windows, int n_users, int n_rows, int pad_idx, int dim, int seq_L, float* d_Q,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -924,6 +924,188 @@ __global__ __launch_bounds__(256) void adam_hot_kernel(float* __restrict__ p, fl
 }
 
 // ------------------------------------------------------------------------------------------------
+// K2w: the dense Adam and its blocked form with torch.optim.Adam(weight_decay=...): g' = fmaf(wd, p, g), ONE rounding
+// (torch's grad.add(param, alpha=weight_decay)), written identically in the three kernels, then adam_elem.  A block
+// without a gradient still moves (g' = wd * p of the current p), so the cold pass and the hot step's catch-up run the
+// full update k times in registers; the only shortcut is for elements whose p, m and v are all +0 (padded columns,
+// padding rows, filler between tables), which the arithmetic leaves exactly as they are when eps > 0:
+// g' = +0, m = +0, v = +0, p + (nss * 0) / eps = p.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void adam_elem_wd(float& p, float g, float& m, float& v, const AdamArgs& a, float wd) {
+    adam_elem(p, fmaf(wd, p, g), m, v, a);
+}
+
+__global__ __launch_bounds__(256) void adam_wd_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, int64_t n, AdamArgs a, float wd, int zero_grad,
+                                                      uint8_t* __restrict__ touch) {
+    constexpr int UNROLL = 4;
+    const int64_t n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto ld = [](const float4* q) -> float4 {
+        float4 r;
+        r.x = __builtin_nontemporal_load(&q->x); r.y = __builtin_nontemporal_load(&q->y);
+        r.z = __builtin_nontemporal_load(&q->z); r.w = __builtin_nontemporal_load(&q->w);
+        return r;
+    };
+    auto stv = [](float4* q, const float4& r) {
+        __builtin_nontemporal_store(r.x, &q->x); __builtin_nontemporal_store(r.y, &q->y);
+        __builtin_nontemporal_store(r.z, &q->z); __builtin_nontemporal_store(r.w, &q->w);
+    };
+    for (int64_t i0 = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i0 < n4; i0 += stride * UNROLL) {
+        float4 pp[UNROLL], mm[UNROLL], vv[UNROLL], gg[UNROLL];
+        uint8_t flag[UNROLL];
+#pragma unroll
+        for (int k = 0; k < UNROLL; ++k) {   // issue every load of this trip before the first use
+            const int64_t i = i0 + k * stride;
+            gg[k] = zero4;
+            flag[k] = 0;
+            if (i < n4) {
+                pp[k] = ld(&p4[i]);
+                mm[k] = ld(&m4[i]);
+                vv[k] = ld(&v4[i]);
+                flag[k] = touch ? touch[i >> 4] : 2;      // as adam_kernel: a zero byte = the block's gradient is zero
+                if (flag[k]) gg[k] = g4[i];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < UNROLL; ++k) {
+            const int64_t i = i0 + k * stride;
+            if (i < n4) {
+                adam_elem_wd(pp[k].x, gg[k].x, mm[k].x, vv[k].x, a, wd);
+                adam_elem_wd(pp[k].y, gg[k].y, mm[k].y, vv[k].y, a, wd);
+                adam_elem_wd(pp[k].z, gg[k].z, mm[k].z, vv[k].z, a, wd);
+                adam_elem_wd(pp[k].w, gg[k].w, mm[k].w, vv[k].w, a, wd);
+                stv(&p4[i], pp[k]);
+                stv(&m4[i], mm[k]);
+                stv(&v4[i], vv[k]);
+                if (flag[k]) {
+                    if (zero_grad) g4[i] = zero4;
+                    if (touch && flag[k] == 1 && (i & 15) == 0) touch[i >> 4] = 0;
+                }
+            }
+        }
+    }
+    // tail (n not a multiple of 4): always read
+    for (int64_t i = (n4 << 2) + blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_elem_wd(pp, g[i], mm, vv, a, wd);
+        p[i] = pp;
+        m[i] = mm;
+        v[i] = vv;
+        if (zero_grad) g[i] = 0.f;
+        if (touch && touch[i >> 6] == 1) touch[i >> 6] = 0;
+    }
+}
+
+// cold pass: every float4 whose 64-float block is not tagged gets its k updates, each with g' = wd * p of the current p
+__global__ __launch_bounds__(256) void adam_cold_wd_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                           int64_t n, AdamBlockArgs a, float wd, const int32_t* __restrict__ tag,
+                                                           int32_t hot_value) {
+    constexpr int UNROLL = 2;
+    const int64_t n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const bool skip_zero = a.eps > 0.0f;
+    auto ld = [](const float4* q) -> float4 {
+        float4 r;
+        r.x = __builtin_nontemporal_load(&q->x); r.y = __builtin_nontemporal_load(&q->y);
+        r.z = __builtin_nontemporal_load(&q->z); r.w = __builtin_nontemporal_load(&q->w);
+        return r;
+    };
+    auto stv = [](float4* q, const float4& r) {
+        __builtin_nontemporal_store(r.x, &q->x); __builtin_nontemporal_store(r.y, &q->y);
+        __builtin_nontemporal_store(r.z, &q->z); __builtin_nontemporal_store(r.w, &q->w);
+    };
+    auto all_zero = [](const float4& x) { return (__float_as_uint(x.x) | __float_as_uint(x.y) | __float_as_uint(x.z) | __float_as_uint(x.w)) == 0; };
+    for (int64_t i0 = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i0 < n4; i0 += stride * UNROLL) {
+        float4 pp[UNROLL], mm[UNROLL], vv[UNROLL];
+        bool cold[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int64_t i = i0 + u * stride;
+            cold[u] = i < n4 && tag[i >> 4] != hot_value;
+            if (cold[u]) {
+                pp[u] = ld(&p4[i]);
+                mm[u] = ld(&m4[i]);
+                vv[u] = ld(&v4[i]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            if (!cold[u] || (skip_zero && all_zero(pp[u]) && all_zero(mm[u]) && all_zero(vv[u]))) continue;
+            for (int s = 0; s < a.k; ++s) {      // step-major: the four independent chains of one step side by side
+                AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+                adam_elem_wd(pp[u].x, 0.0f, mm[u].x, vv[u].x, one, wd);
+                adam_elem_wd(pp[u].y, 0.0f, mm[u].y, vv[u].y, one, wd);
+                adam_elem_wd(pp[u].z, 0.0f, mm[u].z, vv[u].z, one, wd);
+                adam_elem_wd(pp[u].w, 0.0f, mm[u].w, vv[u].w, one, wd);
+            }
+            const int64_t i = i0 + u * stride;
+            stv(&p4[i], pp[u]);
+            stv(&m4[i], mm[u]);
+            stv(&v4[i], vv[u]);
+        }
+    }
+    // tail (n not a multiple of 4)
+    for (int64_t i = (n4 << 2) + blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+        if (tag[i >> 6] == hot_value) continue;
+        float pp = p[i], mm = m[i], vv = v[i];
+        for (int s = 0; s < a.k; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            adam_elem_wd(pp, 0.0f, mm, vv, one, wd);
+        }
+        p[i] = pp;
+        m[i] = mm;
+        v[i] = vv;
+    }
+}
+
+// hot step, as adam_hot_kernel: the claiming wavefront advances the block to step t -- the steps it is behind with
+// g' = wd * p, then step t's with the accumulated gradient, which is consumed
+__global__ __launch_bounds__(256) void adam_hot_wd_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, int64_t n, AdamBlockArgs a, float wd, int32_t t0,
+                                                          int32_t t, const int32_t* __restrict__ ids, int64_t n_ids,
+                                                          int64_t offset, int stride, int32_t* __restrict__ claim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_ids) return;
+    const int32_t id = ids[e];
+    if (id < 0) return;                            // an empty slot of a de-duplicated list
+    const int64_t blk = (offset + static_cast<int64_t>(id) * stride) >> 6;
+    const int64_t i = blk * 64 + lane;
+    float pp = 0.0f, mm = 0.0f, vv = 0.0f, gg = 0.0f;
+    if (i < n) {
+        pp = p[i];
+        mm = m[i];
+        vv = v[i];
+        gg = g[i];
+    }
+    int old = 0;
+    if (lane == 0) old = atomicExch(&claim[blk], t);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old >= t) return;
+    if (old < t0) old = t0;
+    const int s_grad = t - t0 - 1;                 // the step that takes the gradient
+    if (i < n) {
+        for (int s = old - t0; s < t - t0; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            adam_elem_wd(pp, (s == s_grad) ? gg : 0.0f, mm, vv, one, wd);
+        }
+        p[i] = pp;
+        m[i] = mm;
+        v[i] = vv;
+    }
+    if (__builtin_amdgcn_ballot_w64(gg != 0.0f) != 0 && i < n) g[i] = 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2c: the BPR batch and the hot rows' Adam in ONE launch per step (single GPU).
 //
 // With bpr_step_kernel + adam_hot_kernel a training step is a chain of two dependent launches (6-8 us + 13 us): the
@@ -1921,6 +2103,73 @@ int skr_adam_block_hot_tf(float* d_p, float* d_g, float* d_m, float* d_v, int64_
                           int stride_floats, int32_t* d_claim, void* stream) {
     return adam_block_hot_impl(d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, step_t, d_ids, n_ids, offset_floats, stride_floats,
                                d_claim, true, stream);
+}
+
+int skr_adam_step_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t step_t, int zero_grad, uint8_t* d_touch, void* stream) {
+    SKR_REQUIRE(d_p && d_g && d_m && d_v, "skr_adam_step_wd: NULL argument");
+    SKR_REQUIRE(n >= 0 && step_t >= 1, "skr_adam_step_wd: n must be >= 0 and step_t >= 1");
+    SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_g) | reinterpret_cast<uintptr_t>(d_m) |
+                  reinterpret_cast<uintptr_t>(d_v)) & 15) == 0, "skr_adam_step_wd: buffers must be 16-byte aligned");
+    if (n == 0) return SKR_OK;
+    AdamArgs a;
+    a.one_minus_b1 = static_cast<float>(1.0 - static_cast<double>(beta1));
+    a.b2 = beta2;
+    a.one_minus_b2 = static_cast<float>(1.0 - static_cast<double>(beta2));
+    adam_scalars(lr, beta1, beta2, step_t, &a.neg_step_size, &a.bc2_sqrt);
+    a.eps = eps;
+    int64_t blocks = ((n >> 2) + 255) / 256;       // skr_adam_step's measured launch shape: 2 workgroups per CU
+    if (blocks > 512) blocks = 512;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(adam_wd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, skr::as_stream(stream), d_p, d_g, d_m,
+                       d_v, n, a, weight_decay, zero_grad, d_touch);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+int skr_adam_block_cold_wd(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {
+    SKR_REQUIRE(d_p && d_m && d_v && d_tag, "skr_adam_block_cold_wd: NULL argument");
+    SKR_REQUIRE(n >= 0 && step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "skr_adam_block_cold_wd: need 1 <= k <= %d", AB_KMAX);
+    SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_m) | reinterpret_cast<uintptr_t>(d_v)) & 15) == 0,
+                "skr_adam_block_cold_wd: buffers must be 16-byte aligned");
+    if (n == 0) return SKR_OK;
+    AdamBlockArgs a{};
+    a.one_minus_b1 = static_cast<float>(1.0 - static_cast<double>(beta1));
+    a.b2 = beta2;
+    a.one_minus_b2 = static_cast<float>(1.0 - static_cast<double>(beta2));
+    a.eps = eps;
+    a.k = k;
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, k, false);
+    int64_t blocks = ((n >> 2) + 255) / 256;       // the pass is ALU-bound (k dependent updates per element): fill the CUs
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(adam_cold_wd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, skr::as_stream(stream), d_p, d_m,
+                       d_v, n, a, weight_decay, d_tag, hot_value);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+int skr_adam_block_hot_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids,
+                          int64_t offset_floats, int stride_floats, int32_t* d_claim, void* stream) {
+    SKR_REQUIRE(d_p && d_g && d_m && d_v && d_ids && d_claim, "skr_adam_block_hot_wd: NULL argument");
+    SKR_REQUIRE(n >= 0 && step_t0 >= 0 && step_t > step_t0 && step_t - step_t0 <= AB_KMAX && step_t < INT32_MAX,
+                "skr_adam_block_hot_wd: need step_t0 < step_t <= step_t0 + %d", AB_KMAX);
+    SKR_REQUIRE(n_ids >= 0 && offset_floats >= 0 && stride_floats >= 1, "skr_adam_block_hot_wd: bad shape");
+    if (n_ids == 0) return SKR_OK;
+    AdamBlockArgs a{};
+    a.one_minus_b1 = static_cast<float>(1.0 - static_cast<double>(beta1));
+    a.b2 = beta2;
+    a.one_minus_b2 = static_cast<float>(1.0 - static_cast<double>(beta2));
+    a.eps = eps;
+    a.k = static_cast<int>(step_t - step_t0);
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, a.k, false);
+    hipLaunchKernelGGL(adam_hot_wd_kernel, dim3(static_cast<unsigned>((n_ids + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_p,
+                       d_g, d_m, d_v, n, a, weight_decay, static_cast<int32_t>(step_t0), static_cast<int32_t>(step_t), d_ids,
+                       n_ids, offset_floats, stride_floats, d_claim);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
 }
 
 // scalars and thresholds of a k-step block, kept between the k + 1 launches of the block (2k pow() calls otherwise)

@@ -44,6 +44,9 @@ SIGNATURES = {
     "skr_adam_step_tf": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, vp]),
     "skr_adam_block_cold_tf": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, i32, vp]),
     "skr_adam_block_hot_tf": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i64, vp, i64, i64, i32, vp, vp]),
+    "skr_adam_step_wd": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, i32, vp, vp]),
+    "skr_adam_block_cold_wd": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, i32, vp, i32, vp]),
+    "skr_adam_block_hot_wd": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, i64, vp, i64, i64, i32, vp, vp]),
     "skr_bpr_fused_plan": (i32, [vp, vp, vp, i32, i32, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
     "skr_bpr_fused_step": (i32, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, i64, i64, i64, f32, f32, f32, f32, i64, i32, i32,
                                  f32, vp, vp]),
@@ -110,6 +113,9 @@ SIGNATURES = {
     "skr_fpmc_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32, vp]),
     "skr_transrec_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "skr_seq_scores": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i64, vp]),
+    "skr_hgn_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32,
+                           vp]),
+    "skr_hgn_queries": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 class SpmmEpilogue(C.Structure):
@@ -125,6 +131,12 @@ SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
 SKR_TRANSREC_MAX_BLOCKS = 1024   # skr_transrec_step: d_work holds this many rows of dim floats
 SKR_SEQ_FPMC, SKR_SEQ_TRANSREC = 0, 1     # skr_seq_scores modes
+SKR_HGN_MAX_L, SKR_HGN_MAX_T, SKR_HGN_MAX_BLOCKS = 32, 16, 256   # skr_hgn_step limits; d_work holds MAX_BLOCKS partials
+
+
+def hgn_gate_floats(L):
+    """SKR_HGN_GATE_FLOATS(L): floats of HGN's shared gate parameters (and of one partial of their gradient)"""
+    return 2 * 64 * 64 + 3 * 64 + 64 * int(L)
 
 
 class HipError(RuntimeError):

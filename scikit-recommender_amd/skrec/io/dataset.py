@@ -115,6 +115,18 @@ class ImplicitFeedback(object):
                 out[int(chunk_u[0])] = chunk_i
         return out
 
+    def to_truncated_seq_dict(self, max_len: int, pad_value: int = 0, padding="pre", truncating="pre") -> Dict[int, np.ndarray]:
+        """user -> int32 [max_len]: the last ``max_len`` items of the user's time-ordered history, padded with
+        ``pad_value`` (reference: dataset.py:182-193; users in ``to_user_dict_by_time`` order; ``max_len=None``: the
+        longest history)"""
+        from ..utils.py import pad_sequences
+        seqs = self.to_user_dict_by_time()
+        if max_len is None:
+            max_len = max(len(s) for s in seqs.values())
+        arr = pad_sequences([s[-max_len:] for s in seqs.values()], value=pad_value, max_len=max_len, padding=padding,
+                            truncating=truncating, dtype=np.int32)
+        return OrderedDict((user, row) for user, row in zip(seqs.keys(), arr))
+
     def to_user_item_pairs_by_time(self) -> np.ndarray:
         if _TIME not in self._data:
             raise ValueError("This dataset do not contain timestamp.")

@@ -1,7 +1,9 @@
-"""Shared engine of the sequential pairwise recommenders (FPMC, TransRec): the reference's training loop over
-``SequentialPairwiseIterator(num_previous=1, num_next=1)`` batches of (user, last item, positive, negative), one fused
-step launch per batch (csrc/seq.hip) on ONE flat fp32 parameter buffer stepped by ``DenseAdam`` -- the reference's
-dense ``torch.optim.Adam`` over every parameter -- and ``skr_seq_scores`` for predict() and the evaluator.
+"""Shared engine of the sequential pairwise recommenders (FPMC, TransRec, HGN): the reference's training loop over
+``SequentialPairwiseIterator`` batches of (user, previous items, positives, negatives) -- one previous and one next item
+for FPMC and TransRec, a window [n, L] and [n, T] targets for HGN: the columns are taken as the iterator hands them
+over -- one fused step launch per batch (csrc/seq.hip, csrc/hgn.hip) on ONE flat fp32 parameter buffer stepped by
+``DenseAdam`` -- the reference's dense ``torch.optim.Adam`` over every parameter, with ``_weight_decay`` where the
+reference passes one -- and ``skr_seq_scores`` for predict() and the evaluator (HGN overrides the ranking half).
 
 Optimiser stepping, as BPRMF's: at row width 64 the temporally blocked Adam (``SKR_ADAM_BLOCK`` batches per block,
 default 32; bit-identical to one dense ``skr_adam_step`` per batch); ``SKR_ADAM_BLOCK=1`` or wider rows: one dense launch
@@ -23,7 +25,10 @@ __all__ = ["SeqPairwiseRecommender"]
 class SeqPairwiseRecommender(AbstractRecommender):
     """Subclasses name their ``config_class`` and provide ``_build`` (sets ``self.dp``, hands the flat parameter buffer
     to ``_setup`` and sets ``_step_launch``, one batch of the step kernel on cached addresses), ``_block_id_parts`` (the
-    64-float blocks of the flat buffer a batch touches) and ``_score_launch`` (skr_seq_scores)."""
+    64-float blocks of the flat buffer a batch touches: int32 tensors [n] or [n, w], negative entries are skipped) and
+    ``_score_launch`` (skr_seq_scores).  ``_make_iterator`` names the iterator's shape, ``_weight_decay`` the optimiser's."""
+
+    _weight_decay = 0.0
 
     def __init__(self, run_config, config):
         super().__init__(run_config, config)
@@ -65,14 +70,16 @@ class SeqPairwiseRecommender(AbstractRecommender):
         # SKR_ADAM_BLOCK = k: the dense Adam blocked over k batches (1: one dense launch per batch); rows wider than one
         # 64-float block take the dense launch per batch (the blocked forms name rows by their 64-float block)
         self.adam_block = max(1, min(64, int(os.environ.get("SKR_ADAM_BLOCK", "32")))) if self.dp == 64 else 1
-        self.optimizer = DenseAdam(flat, lr=self.config.lr)
+        self.optimizer = DenseAdam(flat, lr=self.config.lr, weight_decay=self._weight_decay)
 
     # ---- training --------------------------------------------------------------------------------
     def _block_ids(self, cols, n_steps, bsz):
         """int32 [n_steps * per_step]: step-major, the blocks of every batch; a short last batch is padded with -1 (an
         id the blocked Adam skips), so every step has the same number of entries"""
-        parts = self._block_id_parts(*cols)
-        n = cols[0].numel()
+        parts = []
+        for p in self._block_id_parts(*cols):
+            parts.extend(p.unbind(1) if p.dim() == 2 else [p])
+        n = cols[0].shape[0]
         ids = torch.full((len(parts), n_steps * bsz), -1, dtype=torch.int32, device=self.device)
         for r, p in enumerate(parts):
             ids[r, :n] = p
@@ -94,16 +101,19 @@ class SeqPairwiseRecommender(AbstractRecommender):
         spread = torch.zeros((len(bounds), S, 2), dtype=torch.float32, device=self.device)
         ploss = spread.data_ptr()
         pcu, pcl, pcp, pcn = (c.data_ptr() for c in (cu, cl, cp, cn))
+        n_all = max(cu.shape[0], 1)
+        bl, bp, bn = (4 * (c.numel() // n_all) for c in (cl, cp, cn))      # bytes per instance of the three item columns
         step = self._step_launch
         kblk = self.adam_block
         if kblk <= 1:
             pflat, pgrad, pm, pv = (t.data_ptr() for t in (opt.flat, opt.grad, opt.m, opt.v))
             n_par = opt.flat.numel()
+            head = (pflat, pgrad, pm, pv, n_par, opt.lr, opt.betas[0], opt.betas[1], opt.eps)
+            dense, wd = (L.skr_adam_step_wd, (opt.weight_decay,)) if opt.weight_decay else (L.skr_adam_step, ())
             for k, (a, b) in enumerate(bounds):
-                rc = step(pcu + 4 * a, pcl + 4 * a, pcp + 4 * a, pcn + 4 * a, b - a, ploss + 8 * S * k, st)
+                rc = step(pcu + 4 * a, pcl + bl * a, pcp + bp * a, pcn + bn * a, b - a, ploss + 8 * S * k, st)
                 opt.t += 1
-                rc |= L.skr_adam_step(pflat, pgrad, pm, pv, n_par, opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.t, 1,
-                                      None, st)
+                rc |= dense(*head, *wd, opt.t, 1, None, st)
                 if rc:
                     _hip.check(rc)
             self.step_losses = spread.sum(1)
@@ -117,17 +127,20 @@ class SeqPairwiseRecommender(AbstractRecommender):
             opt.begin_block(ids[s0 * per:(s0 + len(blk)) * per], len(blk), per_step=per)
             rc = 0
             for k, (a, b) in enumerate(blk, start=s0):
-                rc |= step(pcu + 4 * a, pcl + 4 * a, pcp + 4 * a, pcn + 4 * a, b - a, ploss + 8 * S * k, st)
+                rc |= step(pcu + 4 * a, pcl + bl * a, pcp + bp * a, pcn + bn * a, b - a, ploss + 8 * S * k, st)
                 opt.hot_step()
             if rc:
                 _hip.check(rc)
         opt.end_blocks()
         self.step_losses = spread.sum(1)
 
+    def _make_iterator(self):
+        return SequentialPairwiseIterator(self.dataset.train_data, num_previous=1, num_next=1,
+                                          batch_size=self.config.batch_size, shuffle=True, drop_last=False)
+
     @on_compute_stream
     def fit(self):
-        data_iter = SequentialPairwiseIterator(self.dataset.train_data, num_previous=1, num_next=1,
-                                               batch_size=self.config.batch_size, shuffle=True, drop_last=False)
+        data_iter = self._make_iterator()
         self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
         early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
         for epoch in range(self.config.epochs):

@@ -87,12 +87,14 @@ class AbstractRecommender(object):
 
 class DenseAdam(object):
     """State of ``torch.optim.Adam(params, lr)`` for ONE flat fp32 buffer holding every parameter of the
-    model, stepped by a single ``skr_adam_step`` launch per training step (betas 0.9/0.999, eps 1e-8,
-    no weight decay: the reference's defaults, BPRMF.py:99).  Every element is updated every step,
+    model, stepped by a single ``skr_adam_step`` launch per training step (betas 0.9/0.999, eps 1e-8: the
+    reference's defaults, BPRMF.py:99).  ``weight_decay`` > 0 is torch's ``Adam(weight_decay=...)``: every element's
+    gradient becomes ``g + weight_decay * p`` (one rounding) before the update -- the ``skr_adam_*_wd`` entry points
+    (HGN.py:182); it does not combine with ``tf_epsilon``.  Every element is updated every step,
     like the reference's dense Adam; with ``track_touch`` a byte per 64-float block lets the kernel
     skip READING gradients that are known to be zero (same result, 24 instead of 32 B/param)."""
 
-    def __init__(self, flat, lr, betas=(0.9, 0.999), eps=1e-8, track_touch=False, tf_epsilon=False):
+    def __init__(self, flat, lr, betas=(0.9, 0.999), eps=1e-8, track_touch=False, tf_epsilon=False, weight_decay=0.0):
         import torch
         assert flat.dim() == 1 and flat.is_contiguous()
         self.flat = flat
@@ -104,6 +106,8 @@ class DenseAdam(object):
         # tf.train.AdamOptimizer puts epsilon outside the bias correction: p -= lr_t * m / (sqrt(v) + eps) with
         # lr_t = lr * sqrt(1-b2^t) / (1-b1^t)   (GRU4RecPlus.py:192): the skr_adam_*_tf entry points
         self.tf_epsilon = bool(tf_epsilon)
+        self.weight_decay = float(weight_decay)
+        assert self.weight_decay >= 0.0 and not (self.weight_decay and self.tf_epsilon)
         self.t = 0
 
     # ---- temporally blocked stepping (bit-identical to step() after every batch) -----------------------------
@@ -136,7 +140,13 @@ class DenseAdam(object):
         self._ev_marked.record(cur)
         self._side.wait_event(self._ev_marked)
         self.launch_cold(self._blk_tag, self._blk_serial, int(k))
-        self._hot = (L.skr_adam_block_hot_tf if self.tf_epsilon else L.skr_adam_block_hot, self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+        hot = L.skr_adam_block_hot_tf if self.tf_epsilon else L.skr_adam_block_hot
+        if self.weight_decay:
+            wd = self.weight_decay
+
+            def hot(pp, pg, pm, pv, n, lr, b1, b2, eps, *rest):
+                return L.skr_adam_block_hot_wd(pp, pg, pm, pv, n, lr, b1, b2, eps, wd, *rest)
+        self._hot = (hot, self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                      self.flat.numel(), block_ids.data_ptr(), block_ids.numel(), self._blk_claim.data_ptr(), st,
                      self.t, int(k), None if per_step is None else int(per_step))
 
@@ -167,9 +177,13 @@ class DenseAdam(object):
             e0, e1 = pool.pop() if pool is not None else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             e0.record(self._side)
         L = _hip.lib()
-        _hip.check((L.skr_adam_block_cold_tf if self.tf_epsilon else L.skr_adam_block_cold)(
-            _hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
-            self.betas[0], self.betas[1], self.eps, self.t, int(k), _hip.ptr(tag), int(serial), self._side.cuda_stream))
+        head = (_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
+                self.eps)
+        tail = (self.t, int(k), _hip.ptr(tag), int(serial), self._side.cuda_stream)
+        if self.weight_decay:
+            _hip.check(L.skr_adam_block_cold_wd(*head, self.weight_decay, *tail))
+        else:
+            _hip.check((L.skr_adam_block_cold_tf if self.tf_epsilon else L.skr_adam_block_cold)(*head, *tail))
         if timing is not None:
             e1.record(self._side)
             timing.append((e0, e1, int(k)))
@@ -203,6 +217,10 @@ class DenseAdam(object):
         from .. import _hip
         self.t += 1
         L = _hip.lib()
-        _hip.check((L.skr_adam_step_tf if self.tf_epsilon else L.skr_adam_step)(
-            _hip.ptr(self.flat), _hip.ptr(self.grad), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr, self.betas[0],
-            self.betas[1], self.eps, self.t, 1, _hip.ptr(self.touch), _hip.stream()))
+        head = (_hip.ptr(self.flat), _hip.ptr(self.grad), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
+                self.betas[0], self.betas[1], self.eps)
+        tail = (self.t, 1, _hip.ptr(self.touch), _hip.stream())
+        if self.weight_decay:
+            _hip.check(L.skr_adam_step_wd(*head, self.weight_decay, *tail))
+        else:
+            _hip.check((L.skr_adam_step_tf if self.tf_epsilon else L.skr_adam_step)(*head, *tail))
