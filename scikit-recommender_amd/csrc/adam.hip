@@ -1,0 +1,685 @@
+// adam.hip -- the dense Adam every model trains through (torch.optim.Adam's single-tensor path on ONE flat buffer):
+//   K2   one launch per step (skr_adam_step)
+//   K2b  temporally blocked: mark / cold pass / hot step (skr_adam_block_*), bit-identical to K2 after every step
+//   K2w  both with torch.optim.Adam(weight_decay=...) (the *_wd entry points): the WD instantiations of the same kernels
+// *_tf: tf.train.AdamOptimizer's placement of the second bias correction (adam_scalars).  The arithmetic is in adam_math.h,
+// which the fused BPR step (bpr_fused.hip, K2c) shares.
+#include "adam_math.h"
+
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+
+using namespace skr;
+
+namespace {
+
+// non-temporal 16-byte accesses (NT = false: plain ones)
+template <bool NT>
+__device__ __forceinline__ float4 ld4(const float4* q) {
+    if (NT) {
+        float4 r;
+        r.x = __builtin_nontemporal_load(&q->x); r.y = __builtin_nontemporal_load(&q->y);
+        r.z = __builtin_nontemporal_load(&q->z); r.w = __builtin_nontemporal_load(&q->w);
+        return r;
+    }
+    return *q;
+}
+template <bool NT>
+__device__ __forceinline__ void st4(float4* q, const float4& r) {
+    if (NT) {
+        __builtin_nontemporal_store(r.x, &q->x); __builtin_nontemporal_store(r.y, &q->y);
+        __builtin_nontemporal_store(r.z, &q->z); __builtin_nontemporal_store(r.w, &q->w);
+    } else {
+        *q = r;
+    }
+}
+
+// WD: torch.optim.Adam(weight_decay=wd).  The gradient becomes g' = fmaf(wd, p, g), ONE rounding (torch's
+// grad.add(param, alpha=weight_decay)), written identically in the three kernels, then adam_elem.  A block without a
+// gradient still moves (g' = wd * p of the current p), so the cold pass and the hot step's catch-up run the full update in
+// registers; the only shortcut is for elements whose p, m and v are all +0 (padded columns, padding rows, filler
+// between tables), which the arithmetic leaves exactly as they are when eps > 0: g' = +0, m = +0, v = +0,
+// p + (nss * 0) / eps = p.  The WD instantiations take adam_elem at every step: the scalar test for adam_elem_unit_bc2 costs
+// the ALU-bound cold pass 7 % before step ~16 600 (2.93 against 2.73 ms per 32-step pass of 76.9 M parameters) and
+// saves 15 % after it (profiles/adam_unify_timing.json): which of the two matters is a question of how long a run is.
+template <bool WD>
+__device__ __forceinline__ float grad_wd(float g, float p, float wd) { return WD ? fmaf(wd, p, g) : g; }
+
+// ------------------------------------------------------------------------------------------------
+// K2: dense Adam (torch.optim.Adam single-tensor path), 16-byte vectors, grid-stride
+// ------------------------------------------------------------------------------------------------
+template <bool TOUCH, int UNROLL, bool NT, bool WD>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n, AdamArgs a, float wd, int zero_grad,
+                                                   uint8_t* __restrict__ touch) {
+    const int64_t n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // WD has ONE instantiation (TOUCH = true) and tests the pointer at run time: with touch == NULL that form is the faster
+    // one (0.453 against 0.474 ms for the TOUCH = false instantiation on 76.9 M parameters, profiles/adam_unify_timing.json)
+    const bool use_touch = TOUCH && (!WD || touch != nullptr);
+    for (int64_t i0 = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i0 < n4; i0 += stride * UNROLL) {
+        float4 pp[UNROLL], mm[UNROLL], vv[UNROLL], gg[UNROLL];
+        uint8_t flag[UNROLL];
+#pragma unroll
+        for (int k = 0; k < UNROLL; ++k) {   // issue every load of this trip before the first use
+            const int64_t i = i0 + k * stride;
+            gg[k] = zero4;
+            flag[k] = 0;
+            if (i < n4) {
+                pp[k] = ld4<NT>(&p4[i]);
+                mm[k] = ld4<NT>(&m4[i]);
+                vv[k] = ld4<NT>(&v4[i]);
+                // 16 consecutive lanes share one 64-float block and its byte; they all read it in this
+                // instruction, before the lane with (i & 15) == 0 clears it further down
+                flag[k] = use_touch ? touch[i >> 4] : 2;
+                if (flag[k]) gg[k] = g4[i];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < UNROLL; ++k) {
+            const int64_t i = i0 + k * stride;
+            if (i < n4) {
+                adam_elem(pp[k].x, grad_wd<WD>(gg[k].x, pp[k].x, wd), mm[k].x, vv[k].x, a);
+                adam_elem(pp[k].y, grad_wd<WD>(gg[k].y, pp[k].y, wd), mm[k].y, vv[k].y, a);
+                adam_elem(pp[k].z, grad_wd<WD>(gg[k].z, pp[k].z, wd), mm[k].z, vv[k].z, a);
+                adam_elem(pp[k].w, grad_wd<WD>(gg[k].w, pp[k].w, wd), mm[k].w, vv[k].w, a);
+                st4<NT>(&p4[i], pp[k]);
+                st4<NT>(&m4[i], mm[k]);
+                st4<NT>(&v4[i], vv[k]);
+                if (flag[k]) {
+                    if (zero_grad) g4[i] = zero4;
+                    if (use_touch && flag[k] == 1 && (i & 15) == 0) touch[i >> 4] = 0;
+                }
+            }
+        }
+    }
+    // tail (n not a multiple of 4): always read
+    for (int64_t i = (n4 << 2) + blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+        float pp = p[i], mm = m[i], vv = v[i];
+        adam_elem(pp, grad_wd<WD>(g[i], pp, wd), mm, vv, a);
+        p[i] = pp;
+        m[i] = mm;
+        v[i] = vv;
+        if (zero_grad) g[i] = 0.f;
+        if (use_touch && touch[i >> 6] == 1) touch[i >> 6] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K2b: the same dense Adam, temporally blocked.  The reference's optimiser moves EVERY parameter at EVERY
+// step, but a BPR step puts a non-zero gradient into at most 3*batch of the ~1.1 M rows, and the batches of an
+// epoch are known in advance.  For a block of k consecutive steps the 64-float blocks of the flat buffer
+// are split into HOT (touched by at least one of the k steps) and COLD.  A cold block sees k zero-gradient
+// updates: they are applied in ONE pass (p, m, v read and written once instead of k times), each of the k
+// updates evaluated exactly as adam_elem does with g = 0 and that step's bias corrections.  Hot blocks get
+// the ordinary update at every step, through the id lists of the block (each block claimed once per step).
+// Every parameter still receives every update, in the same arithmetic: results are bit-identical to calling
+// skr_adam_step after every step (tests/test_gpu_train.py::test_blocked_adam_is_bit_identical).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void adam_mark_kernel(const int32_t* __restrict__ ids, int64_t n, int64_t offset,
+                                                        int stride, int32_t* __restrict__ tag, int32_t value,
+                                                        int32_t* __restrict__ claim, int32_t claim_value) {
+    const int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (g < n && ids[g] >= 0) {   // negative id: an empty slot of a de-duplicated list
+        const int64_t blk = (offset + static_cast<int64_t>(ids[g]) * stride) >> 6;
+        tag[blk] = value;
+        if (claim) claim[blk] = claim_value;
+    }
+}
+
+// cold pass: every float4 whose 64-float block is not tagged gets k zero-gradient updates (WD: each with g' = wd * p of
+// the current p)
+template <int UNROLL, bool WD>
+__global__ __launch_bounds__(256) void adam_cold_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                        int64_t n, AdamBlockArgs a, float wd, const int32_t* __restrict__ tag,
+                                                        int32_t hot_value) {
+    const int64_t n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const bool skip_zero = WD && a.eps > 0.0f;
+    auto all_zero = [](const float4& x) { return (__float_as_uint(x.x) | __float_as_uint(x.y) | __float_as_uint(x.z) | __float_as_uint(x.w)) == 0; };
+    auto steps = [&](float& pp, float& mm, float& vv) {
+        for (int s = 0; s < a.k; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            adam_elem(pp, grad_wd<WD>(0.0f, pp, wd), mm, vv, one);
+        }
+    };
+    // the same k updates for the four lanes of a float4, step-major: the four independent chains of one step sit
+    // next to each other, which lets the compiler pair them into packed fp32 instructions
+    auto steps4 = [&](float4& pp, float4& mm, float4& vv) {
+        for (int s = 0; s < a.k; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            if (!WD && __builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000) {   // scalar branch, not a select
+                adam_elem_unit_bc2(pp.x, grad_wd<WD>(0.0f, pp.x, wd), mm.x, vv.x, one);
+                adam_elem_unit_bc2(pp.y, grad_wd<WD>(0.0f, pp.y, wd), mm.y, vv.y, one);
+                adam_elem_unit_bc2(pp.z, grad_wd<WD>(0.0f, pp.z, wd), mm.z, vv.z, one);
+                adam_elem_unit_bc2(pp.w, grad_wd<WD>(0.0f, pp.w, wd), mm.w, vv.w, one);
+            } else {
+                adam_elem(pp.x, grad_wd<WD>(0.0f, pp.x, wd), mm.x, vv.x, one);
+                adam_elem(pp.y, grad_wd<WD>(0.0f, pp.y, wd), mm.y, vv.y, one);
+                adam_elem(pp.z, grad_wd<WD>(0.0f, pp.z, wd), mm.z, vv.z, one);
+                adam_elem(pp.w, grad_wd<WD>(0.0f, pp.w, wd), mm.w, vv.w, one);
+            }
+        }
+    };
+    for (int64_t i0 = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i0 < n4; i0 += stride * UNROLL) {
+        float4 pp[UNROLL], mm[UNROLL], vv[UNROLL];
+        bool cold[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int64_t i = i0 + u * stride;
+            cold[u] = i < n4 && tag[i >> 4] != hot_value;
+            if (cold[u]) {
+                pp[u] = ld4<true>(&p4[i]);
+                mm[u] = ld4<true>(&m4[i]);
+                vv[u] = ld4<true>(&v4[i]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            if (cold[u] && !(skip_zero && all_zero(pp[u]) && all_zero(mm[u]) && all_zero(vv[u]))) {
+                const int64_t i = i0 + u * stride;
+                steps4(pp[u], mm[u], vv[u]);
+                st4<true>(&p4[i], pp[u]);
+                st4<true>(&m4[i], mm[u]);
+                st4<true>(&v4[i], vv[u]);
+            }
+        }
+    }
+    // tail (n not a multiple of 4)
+    for (int64_t i = (n4 << 2) + blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride)
+        if (tag[i >> 6] != hot_value) steps(p[i], m[i], v[i]);
+}
+
+__global__ __launch_bounds__(256) void selftest_cold_math_kernel(uint32_t lo, uint32_t hi, uint64_t n_pairs,
+                                                                 unsigned long long* __restrict__ bad) {
+    const uint64_t tid = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    const uint64_t nth = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    unsigned long long bs = 0, bd = 0, b1 = 0, b2 = 0;
+    for (uint64_t b = lo + tid; b <= hi; b += nth) {
+        const float x = __uint_as_float(static_cast<uint32_t>(b));
+        const uint32_t want = __float_as_uint(sqrtf(x));
+        bs += __float_as_uint(sqrt_ordinary(x)) != want;
+        b1 += __float_as_uint(__builtin_amdgcn_sqrtf(x)) != want;   // control
+        b2 += 1;
+    }
+    for (uint64_t i = tid; i < n_pairs; i += nth) {
+        uint64_t h = (i + 1) * 0x9E3779B97F4A7C15ull;   // splitmix64
+        h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+        h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+        h ^= h >> 31;
+        // d: exponent in [-48, 21], n: exponent in [-100, 40], random mantissas and signs
+        const uint32_t hd = static_cast<uint32_t>(h), hn = static_cast<uint32_t>(h >> 32);
+        const uint32_t ed = 127 - 48 + (hd >> 23) % 70, en = 127 - 100 + ((hn >> 23) & 0xff) % 141;
+        const float d = __uint_as_float((hd & 0x807fffffu) | (ed << 23)), n = __uint_as_float((hn & 0x807fffffu) | (en << 23));
+        bd += __float_as_uint(div_ordinary(n, d)) != __float_as_uint(n / d);
+    }
+    if (bs) atomicAdd(&bad[0], bs);
+    if (bd) atomicAdd(&bad[1], bd);
+    if (b1) atomicAdd(&bad[2], b1);
+    if (b2) atomicAdd(&bad[3], b2);
+}
+
+// cold pass, one wavefront per 64-float block (= one embedding row), with a cheap exact path for rows AT REST.
+//
+// A zero-gradient update is p += (nss*m') / (sqrt(v')/bc2 + eps) with m' = m + c1*(0 - m), v' = v*b2.  A row that
+// no batch has touched for a few hundred steps has |m| decayed so far that the quotient q is below a quarter of
+// the spacing of the floats around p: then fl(p + q) == p and the correctly rounded sqrt and divisions (about 36 of
+// the ~41 issue slots of an update) decide nothing.  A block is AT REST for all k updates of the pass when every lane
+// passes, on the values the pass starts from,
+//     sign(v) = +, v not NaN;  |p| >= 2^-60;
+//     |nss[0]*m| < 2^-28 * |p| * eps            or    |nss[0]*m|^2 < 2^-58 * p^2 * v * lb(b2^k)   (and that bound is normal)
+// Proof sketch: |m| and |nss[s]| never grow over the pass and v never drops below v*b2^k, so for every
+// update |n| = |fl(nss[s]*m')| <= |fl(nss[0]*m)| and d = fl(fl(sqrt(v')/bc2) + eps) >= max(eps, sqrt(v*b2^k))*(1 - 2^-22);
+// hence |fl(n/d)| < 2^-27 |p| < spacing(p)/4 and p is unchanged, bit for bit, by each of the k updates.  m and v still get
+// their k decays in the arithmetic of adam_elem (v*b2 + (c2*0)*0 == v*b2 because v*b2 carries a + sign).  The thresholds
+// are zero (tests off) unless 0 < beta1, beta2 < 1, lr > 0, eps >= 0.  Blocks not at rest take adam_elem as before.
+template <int U>
+__global__ __launch_bounds__(256) void adam_cold_rows_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                             float* __restrict__ v, int64_t n, AdamBlockArgs a,
+                                                             const int32_t* __restrict__ tag, int32_t hot_value) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nb = n >> 6;
+    const int64_t n_waves = static_cast<int64_t>(gridDim.x) * 4;
+    const int64_t wave0 = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    auto general = [&](float& pp, float& mm, float& vv) {
+        for (int s = 0; s < a.k; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)   // scalar branch, not a select
+                adam_elem_unit_bc2(pp, 0.0f, mm, vv, one);
+            else
+                adam_elem(pp, 0.0f, mm, vv, one);
+        }
+    };
+    // two rows of ordinary magnitudes advance together (packed fp32 for the element-wise parts, the two square
+    // root / division chains interleaved): the first waits in `held` until the wavefront meets the second
+    auto ordinary2 = [&](f32x2& p2, f32x2& m2, f32x2& v2) {
+        for (int s = 0; s < a.k; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+                adam_pair_ordinary<true>(p2, m2, v2, one);
+            else
+                adam_pair_ordinary<false>(p2, m2, v2, one);
+        }
+    };
+    bool have = false;
+    float hp = 0.0f, hm = 0.0f, hv = 0.0f;
+    int64_t hi = 0;
+    for (int64_t b0 = wave0; b0 < nb; b0 += n_waves * U) {
+        float pp[U], mm[U], vv[U];
+        bool cold[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t b = b0 + u * n_waves;
+            cold[u] = b < nb && tag[b] != hot_value;
+            if (cold[u]) {
+                const int64_t i = (b << 6) + lane;
+                pp[u] = __builtin_nontemporal_load(&p[i]);
+                mm[u] = __builtin_nontemporal_load(&m[i]);
+                vv[u] = __builtin_nontemporal_load(&v[i]);
+            }
+        }
+        // rows at rest (4 of 5 cold rows): only the moments decay, 3 vector instructions per element and step -- as much
+        // vector-ALU time over the pass as the rows of ordinary magnitudes.  Neighbours (u, u + 1) that are both at rest
+        // decay together in packed fp32 (the same multiply and add on each half); a row whose moments are all zero
+        // (never touched) has nothing to decay.
+        bool rest[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            rest[u] = cold[u] && __builtin_amdgcn_ballot_w64(!lane_at_rest(pp[u], mm[u], vv[u], a.nss_bound[0], a)) == 0;
+        auto store_rest = [&](int64_t i, float m0, float v0, float m1, float v1) {
+            if (__builtin_amdgcn_ballot_w64(__float_as_uint(m1) != __float_as_uint(m0)) != 0) __builtin_nontemporal_store(m1, &m[i]);
+            if (__builtin_amdgcn_ballot_w64(__float_as_uint(v1) != __float_as_uint(v0)) != 0) __builtin_nontemporal_store(v1, &v[i]);
+        };
+#pragma unroll
+        for (int u = 0; u + 1 < U; u += 2) {
+            if (!(rest[u] && rest[u + 1])) continue;
+            if (a.stats && lane == 0) atomicAdd(&a.stats[0], 2ull);
+            f32x2 m2{mm[u], mm[u + 1]}, v2{vv[u], vv[u + 1]};
+            if (__builtin_amdgcn_ballot_w64((__float_as_uint(m2.x) | __float_as_uint(m2.y) | __float_as_uint(v2.x) |
+                                             __float_as_uint(v2.y)) != 0) != 0) {
+                for (int s = 0; s < a.k; ++s) {
+                    // -m for (0 - m): a sign modifier on the multiply instead of an instruction.  They differ for m = +-0
+                    // only (+0 vs -0 into the product), and m + (+-0) is m, resp. +0 for m = +-0, either way
+                    m2 = m2 + a.one_minus_b1 * (-m2);
+                    v2 = v2 * a.b2;
+                }
+                store_rest(((b0 + u * n_waves) << 6) + lane, mm[u], vv[u], m2.x, v2.x);
+                store_rest(((b0 + (u + 1) * n_waves) << 6) + lane, mm[u + 1], vv[u + 1], m2.y, v2.y);
+            }
+            cold[u] = cold[u + 1] = false;      // done
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!cold[u]) continue;
+            const int64_t i = ((b0 + u * n_waves) << 6) + lane;
+            if (rest[u]) {
+                if (a.stats && lane == 0) atomicAdd(&a.stats[0], 1ull);
+                float m1 = mm[u], v1 = vv[u];
+                for (int s = 0; s < a.k; ++s) {
+                    m1 = m1 + a.one_minus_b1 * (0.0f - m1);
+                    v1 = v1 * a.b2;
+                }
+                store_rest(i, mm[u], vv[u], m1, v1);
+                continue;
+            }
+            const bool lane_ord = lane_ordinary(mm[u], vv[u], a);
+            if (__builtin_amdgcn_ballot_w64(!lane_ord) == 0) {
+                if (a.stats && lane == 0) atomicAdd(&a.stats[1], 1ull);
+                if (!have) {
+                    hp = pp[u], hm = mm[u], hv = vv[u], hi = i;
+                    have = true;
+                    continue;
+                }
+                f32x2 p2{hp, pp[u]}, m2{hm, mm[u]}, v2{hv, vv[u]};
+                ordinary2(p2, m2, v2);
+                __builtin_nontemporal_store(p2.x, &p[hi]);
+                __builtin_nontemporal_store(m2.x, &m[hi]);
+                __builtin_nontemporal_store(v2.x, &v[hi]);
+                __builtin_nontemporal_store(p2.y, &p[i]);
+                __builtin_nontemporal_store(m2.y, &m[i]);
+                __builtin_nontemporal_store(v2.y, &v[i]);
+                have = false;
+                continue;
+            }
+            if (a.stats && lane == 0) atomicAdd(&a.stats[2], 1ull);
+            general(pp[u], mm[u], vv[u]);
+            __builtin_nontemporal_store(pp[u], &p[i]);
+            __builtin_nontemporal_store(mm[u], &m[i]);
+            __builtin_nontemporal_store(vv[u], &v[i]);
+        }
+    }
+    if (have) {   // an odd one out
+        general(hp, hm, hv);
+        __builtin_nontemporal_store(hp, &p[hi]);
+        __builtin_nontemporal_store(hm, &m[hi]);
+        __builtin_nontemporal_store(hv, &v[hi]);
+    }
+    // tail (n not a multiple of 64)
+    const int64_t i = (nb << 6) + blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i < n && tag[nb] != hot_value) general(p[i], m[i], v[i]);
+}
+
+// hot step: one wavefront per id.  claim[block] holds the optimiser step the block has been advanced to (the mark
+// kernel sets it to the step count the k-step block starts from).  The wavefront that raises it to step_t owns the
+// block for this launch and ADVANCES it: zero-gradient updates for the steps it has not seen yet, then step_t's update
+// with the accumulated gradient, which is consumed.  A caller that names every hot block at every step gets one
+// update per launch; a caller that names only the rows of batch t and of batch t+1 (the next batch must READ current
+// rows) visits a row when it matters and catches up there -- the same updates in the same order, fewer passes over
+// HBM.  The last step of a k-step block must name every hot block, so that all of them end at the same step.
+template <bool WD>
+__global__ __launch_bounds__(256) void adam_hot_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, int64_t n, AdamBlockArgs a, float wd, int32_t t0,
+                                                       int32_t t, const int32_t* __restrict__ ids, int64_t n_ids,
+                                                       int64_t offset, int stride, int32_t* __restrict__ claim) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_ids) return;
+    const int32_t id = ids[e];
+    if (id < 0) return;                            // an empty slot of a de-duplicated list
+    const int64_t blk = (offset + static_cast<int64_t>(id) * stride) >> 6;
+    // the row is loaded while the claim is in flight (one memory round trip less on a latency-bound kernel); a
+    // wavefront that loses the claim drops what it loaded.  Nobody writes the row during this launch but its owner.
+    const int64_t i = blk * 64 + lane;
+    float pp = 1.0f, mm = 0.0f, vv = 0.0f, gg = 0.0f;   // lanes beyond n: values that pass every wavefront-wide test
+    if (i < n) {
+        pp = p[i];
+        mm = m[i];
+        vv = v[i];
+        gg = g[i];
+    }
+    int old = 0;
+    if (lane == 0) old = atomicExch(&claim[blk], t);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old >= t) return;
+    if (old < t0) old = t0;
+    // The steps the block is behind are zero-gradient updates, and they sit on the critical path of the training step
+    // (the slowest wavefront of this launch is one with a row that is 20 steps behind).  The same three exact evaluations
+    // as in the cold pass: AT REST (a row no batch has touched for long -- most user rows when their turn comes: only the
+    // moments decay), ORDINARY MAGNITUDES (scaling-free square root / division: a dependent chain 2.5x shorter), general.
+    // The first two hold for a zero gradient only: under weight decay (g' = wd * p) every step takes the general one.
+    const int s_grad = t - t0 - 1;                 // the step that takes the gradient
+    int s = old - t0;
+    if (!WD && s < s_grad) {
+        if (__builtin_amdgcn_ballot_w64(!lane_at_rest(pp, mm, vv, a.nss_bound[s], a)) == 0) {
+            for (; s < s_grad; ++s) {
+                mm = mm + a.one_minus_b1 * (0.0f - mm);
+                vv = vv * a.b2;
+            }
+        } else if (__builtin_amdgcn_ballot_w64(!lane_ordinary(mm, vv, a)) == 0) {
+            for (; s < s_grad; ++s) {
+                AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+                if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+                    adam_one_ordinary<true>(pp, mm, vv, one);
+                else
+                    adam_one_ordinary<false>(pp, mm, vv, one);
+            }
+        }
+    }
+    if (i < n) {
+        for (; s < t - t0; ++s) {   // step t0 + s + 1: what is left of the zero-gradient steps, then the gradient step
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            const float gs = (s == s_grad) ? gg : 0.0f;
+            if (!WD && __builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+                adam_elem_unit_bc2(pp, grad_wd<WD>(gs, pp, wd), mm, vv, one);
+            else
+                adam_elem(pp, grad_wd<WD>(gs, pp, wd), mm, vv, one);
+        }
+        p[i] = pp;
+        m[i] = mm;
+        v[i] = vv;
+    }
+    // a row named only because the NEXT batch reads it has no gradient yet: nothing to clear
+    if (__builtin_amdgcn_ballot_w64(gg != 0.0f) != 0 && i < n) g[i] = 0.0f;
+}
+
+}  // namespace
+
+// SKR_COLD_STATS=1: a device census of how the cold passes sorted their blocks (read with skr_cold_pass_census)
+unsigned long long* skr::cold_stats_buffer() {
+    static unsigned long long* buf = [] {
+        unsigned long long* p = nullptr;
+        const char* e = getenv("SKR_COLD_STATS");
+        if (e && atoi(e) == 1 && hipMalloc(&p, 4 * sizeof(unsigned long long)) == hipSuccess) {
+            (void)hipMemset(p, 0, 4 * sizeof(unsigned long long));
+            return p;
+        }
+        return static_cast<unsigned long long*>(nullptr);
+    }();
+    return buf;
+}
+
+extern "C" {
+
+// The three launches behind the nine public functions.  who: the called function's name, for its error messages;
+// tf: tf.train.AdamOptimizer's scalars; wd: the weight decay of the *_wd functions (NULL otherwise; never with tf).
+static int adam_step_impl(const char* who, float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1,
+                          float beta2, float eps, int64_t step_t, int zero_grad, uint8_t* d_touch, bool tf, const float* wd,
+                          void* stream) {
+    SKR_REQUIRE(d_p && d_g && d_m && d_v, "%s: NULL argument", who);
+    SKR_REQUIRE(n >= 0 && step_t >= 1, "%s: n must be >= 0 and step_t >= 1", who);
+    SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_g) | reinterpret_cast<uintptr_t>(d_m) |
+                  reinterpret_cast<uintptr_t>(d_v)) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+    if (n == 0) return SKR_OK;
+    AdamArgs a;
+    adam_shared_fields(a, beta1, beta2, eps);
+    adam_scalars(lr, beta1, beta2, step_t, &a.neg_step_size, &a.bc2_sqrt, tf);
+    // Launch shape measured on MI355X (tools/tune_adam.sh, profiles/r01_adam_tuning.txt): 2 workgroups
+    // per CU, 4 float4 per lane in flight, non-temporal accesses.  SKR_ADAM_CFG="<blocks_per_cu>,
+    // <unroll>,<nt>" overrides it for tuning runs (not for the weight-decay launch).
+    static int cfg_bpc = 2, cfg_unroll = 4, cfg_nt = 1;
+    static bool cfg_read = false;
+    if (!cfg_read) {
+        cfg_read = true;
+        if (const char* e = getenv("SKR_ADAM_CFG")) sscanf(e, "%d,%d,%d", &cfg_bpc, &cfg_unroll, &cfg_nt);
+    }
+    int64_t blocks = ((n >> 2) + 255) / 256;
+    if (blocks > 256 * (wd ? 2 : cfg_bpc)) blocks = 256 * (wd ? 2 : cfg_bpc);
+    if (blocks < 1) blocks = 1;
+    const dim3 grid(static_cast<unsigned>(blocks)), blk(256);
+    hipStream_t st = skr::as_stream(stream);
+#define SKR_ADAM_LAUNCH(T, U_, N_, W_)                                                                                   \
+    hipLaunchKernelGGL((adam_kernel<T, U_, N_, W_>), grid, blk, 0, st, d_p, d_g, d_m, d_v, n, a, wd ? *wd : 0.0f, zero_grad, \
+                       d_touch)
+#define SKR_ADAM_PICK(T)                                                        \
+    if (cfg_nt) {                                                               \
+        if (cfg_unroll == 4) SKR_ADAM_LAUNCH(T, 4, true, false);                \
+        else if (cfg_unroll == 2) SKR_ADAM_LAUNCH(T, 2, true, false);           \
+        else SKR_ADAM_LAUNCH(T, 1, true, false);                                \
+    } else {                                                                    \
+        if (cfg_unroll == 4) SKR_ADAM_LAUNCH(T, 4, false, false);               \
+        else if (cfg_unroll == 2) SKR_ADAM_LAUNCH(T, 2, false, false);          \
+        else SKR_ADAM_LAUNCH(T, 1, false, false);                               \
+    }
+    if (wd) { SKR_ADAM_LAUNCH(true, 4, true, true); } else if (d_touch) { SKR_ADAM_PICK(true) } else { SKR_ADAM_PICK(false) }
+#undef SKR_ADAM_PICK
+#undef SKR_ADAM_LAUNCH
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+int skr_adam_block_mark(const int32_t* d_ids, int64_t n_ids, int64_t offset_floats, int stride_floats, int32_t* d_tag,
+                        int32_t tag_value, int32_t* d_claim, int64_t step_t0, void* stream) {
+    SKR_REQUIRE(d_ids && d_tag, "skr_adam_block_mark: NULL argument");
+    SKR_REQUIRE(n_ids >= 0 && offset_floats >= 0 && stride_floats >= 1, "skr_adam_block_mark: bad shape");
+    SKR_REQUIRE(step_t0 >= 0 && step_t0 < INT32_MAX - AB_KMAX, "skr_adam_block_mark: step_t0 out of range");
+    if (n_ids == 0) return SKR_OK;
+    hipLaunchKernelGGL(adam_mark_kernel, dim3(static_cast<unsigned>((n_ids + 255) / 256)), dim3(256), 0, skr::as_stream(stream),
+                       d_ids, n_ids, offset_floats, stride_floats, d_tag, tag_value, d_claim, static_cast<int32_t>(step_t0));
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+
+int skr_cold_pass_census(uint64_t* h_counts3, int reset) {
+    SKR_REQUIRE(h_counts3, "skr_cold_pass_census: NULL argument");
+    unsigned long long* buf = cold_stats_buffer();
+    h_counts3[0] = h_counts3[1] = h_counts3[2] = 0;
+    if (!buf) return SKR_OK;
+    unsigned long long h[4];
+    SKR_HIP(hipDeviceSynchronize());
+    SKR_HIP(hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) SKR_HIP(hipMemset(buf, 0, sizeof(h)));
+    for (int i = 0; i < 3; ++i) h_counts3[i] = h[i];
+    return SKR_OK;
+}
+
+
+static int adam_block_cold_impl(const char* who, float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                                float eps, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, bool tf, const float* wd,
+                                void* stream) {
+    SKR_REQUIRE(d_p && d_m && d_v && d_tag, "%s: NULL argument", who);
+    SKR_REQUIRE(n >= 0 && step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "%s: need 1 <= k <= %d", who, AB_KMAX);
+    SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_m) | reinterpret_cast<uintptr_t>(d_v)) & 15) == 0,
+                "%s: buffers must be 16-byte aligned", who);
+    if (n == 0) return SKR_OK;
+    AdamBlockArgs a{};
+    adam_shared_fields(a, beta1, beta2, eps);
+    a.k = k;
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, k, tf);
+    hipStream_t st = skr::as_stream(stream);
+    if (wd) {
+        // every update moves every element, so there is no row at rest to find: the float4 kernel, and the pass is ALU-bound
+        // (k dependent updates per element): fill the CUs
+        int64_t blocks = ((n >> 2) + 255) / 256;
+        if (blocks > 256 * 8) blocks = 256 * 8;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL((adam_cold_kernel<2, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v, n, a,
+                           *wd, d_tag, hot_value);
+        SKR_LAUNCH_CHECK();
+        return SKR_OK;
+    }
+    static const int bpc = [] { const char* e = getenv("SKR_COLD_BPC"); const int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 8 ? 8 : v); }();   // workgroups per CU.  The pass runs beside the k-step block's small launches: round 2 settled on 4 (960 timed steps: 24.9 / 31.3 / 30.3 / 28.1 M interactions/s at 2 / 3 / 4 / 8); round 3: 5, together with the step kernel's issue priority (see bpr_fused_step_kernel)
+    // SKR_COLD_REST=0 keeps every cold block on the full update (the float4 kernel): the A/B switch of tools/microbench.py
+    static const bool rest = [] { const char* e = getenv("SKR_COLD_REST"); return !(e && atoi(e) == 0); }();
+    // A pass over a WHOLE block of the default length (32 steps and more) of the BPR tables takes six workgroups per CU
+    // (SKR_COLD_BPC_FULL; 0: SKR_COLD_BPC for every pass): in the steady state of an epoch the pass and the step stream are
+    // balanced (0.53 ms against 32 x 15 us + the write-back), and the sixth workgroup takes 0.04 ms off the pass for 0.4 us per
+    // step launch -- an epoch 0.997 -> 0.956 s on the same box (tools/r3_bpc_full.sh).  Shorter blocks (the 20-step slice of
+    // the bench line, an epoch's ragged last block) leave the step stream less work to hide the pass behind and keep five: with
+    // six for every pass the short slice scatters (34.5-39.5 M interactions/s against 39.4-41.0).  GRU4RecPlus's pass (TF
+    // arithmetic) keeps SKR_COLD_BPC: its step is a chain of eight small launches that was measured with five.
+    static const int bpc_full = [] { const char* e = getenv("SKR_COLD_BPC_FULL"); const int v = e ? atoi(e) : 6; return v < 1 ? 0 : (v > 8 ? 8 : v); }();
+    const int bpc_k = (bpc_full && k >= 32 && !tf) ? bpc_full : bpc;
+    adam_block_thresholds(a, lr, beta1, beta2, eps, k);
+    a.stats = cold_stats_buffer();
+    if (rest) {
+        int64_t blocks = ((n >> 6) + 4 * 4 - 1) / (4 * 4);
+        if (blocks > 256 * bpc_k) blocks = 256 * bpc_k;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(adam_cold_rows_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v, n, a,
+                           d_tag, hot_value);
+    } else {
+        int64_t blocks = ((n >> 2) + 255) / 256;
+        if (blocks > 256 * bpc) blocks = 256 * bpc;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL((adam_cold_kernel<2, false>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v, n, a,
+                           0.0f, d_tag, hot_value);
+    }
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+static int adam_block_hot_impl(const char* who, float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1,
+                               float beta2, float eps, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids,
+                               int64_t offset_floats, int stride_floats, int32_t* d_claim, bool tf, const float* wd, void* stream) {
+    SKR_REQUIRE(d_p && d_g && d_m && d_v && d_ids && d_claim, "%s: NULL argument", who);
+    SKR_REQUIRE(n >= 0 && step_t0 >= 0 && step_t > step_t0 && step_t - step_t0 <= AB_KMAX && step_t < INT32_MAX,
+                "%s: need step_t0 < step_t <= step_t0 + %d", who, AB_KMAX);
+    SKR_REQUIRE(n_ids >= 0 && offset_floats >= 0 && stride_floats >= 1, "%s: bad shape", who);
+    if (n_ids == 0) return SKR_OK;
+    AdamBlockArgs a{};
+    adam_shared_fields(a, beta1, beta2, eps);
+    a.k = static_cast<int>(step_t - step_t0);
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, a.k, tf);
+    if (!wd) adam_block_thresholds(a, lr, beta1, beta2, eps, a.k);   // for the zero-gradient steps a block may be behind
+#define SKR_HOT_LAUNCH(W_)                                                                                                         \
+    hipLaunchKernelGGL(adam_hot_kernel<W_>, dim3(static_cast<unsigned>((n_ids + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_p, \
+                       d_g, d_m, d_v, n, a, wd ? *wd : 0.0f, static_cast<int32_t>(step_t0), static_cast<int32_t>(step_t), d_ids, \
+                       n_ids, offset_floats, stride_floats, d_claim)
+    if (wd) SKR_HOT_LAUNCH(true); else SKR_HOT_LAUNCH(false);
+#undef SKR_HOT_LAUNCH
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+int skr_adam_step(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                  float eps, int64_t step_t, int zero_grad, uint8_t* d_touch, void* stream) {
+    return adam_step_impl("skr_adam_step", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t, zero_grad, d_touch, false, nullptr,
+                          stream);
+}
+int skr_adam_step_tf(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                     float eps, int64_t step_t, int zero_grad, uint8_t* d_touch, void* stream) {
+    return adam_step_impl("skr_adam_step_tf", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t, zero_grad, d_touch, true, nullptr,
+                          stream);
+}
+int skr_adam_step_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t step_t, int zero_grad, uint8_t* d_touch, void* stream) {
+    return adam_step_impl("skr_adam_step_wd", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t, zero_grad, d_touch, false,
+                          &weight_decay, stream);
+}
+
+int skr_adam_block_cold(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {
+    return adam_block_cold_impl("skr_adam_block_cold", d_p, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, k, d_tag, hot_value, false,
+                                nullptr, stream);
+}
+int skr_adam_block_cold_tf(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {
+    return adam_block_cold_impl("skr_adam_block_cold_tf", d_p, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, k, d_tag, hot_value, true,
+                                nullptr, stream);
+}
+int skr_adam_block_cold_wd(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {
+    return adam_block_cold_impl("skr_adam_block_cold_wd", d_p, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, k, d_tag, hot_value, false,
+                                &weight_decay, stream);
+}
+
+int skr_adam_block_hot(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                       float eps, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids, int64_t offset_floats,
+                       int stride_floats, int32_t* d_claim, void* stream) {
+    return adam_block_hot_impl("skr_adam_block_hot", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, step_t, d_ids, n_ids,
+                               offset_floats, stride_floats, d_claim, false, nullptr, stream);
+}
+int skr_adam_block_hot_tf(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                          float eps, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids, int64_t offset_floats,
+                          int stride_floats, int32_t* d_claim, void* stream) {
+    return adam_block_hot_impl("skr_adam_block_hot_tf", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, step_t, d_ids, n_ids,
+                               offset_floats, stride_floats, d_claim, true, nullptr, stream);
+}
+int skr_adam_block_hot_wd(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids,
+                          int64_t offset_floats, int stride_floats, int32_t* d_claim, void* stream) {
+    return adam_block_hot_impl("skr_adam_block_hot_wd", d_p, d_g, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, step_t, d_ids, n_ids,
+                               offset_floats, stride_floats, d_claim, false, &weight_decay, stream);
+}
+
+int skr_selftest_cold_math(uint64_t n_pairs, uint64_t* h_mismatches, void* stream) {
+    SKR_REQUIRE(h_mismatches, "skr_selftest_cold_math: NULL argument");
+    unsigned long long* d_bad = nullptr;
+    SKR_HIP(hipMalloc(&d_bad, 4 * sizeof(unsigned long long)));
+    SKR_HIP(hipMemsetAsync(d_bad, 0, 4 * sizeof(unsigned long long), skr::as_stream(stream)));
+    // square root: every float in [2^-96, largest finite]
+    hipLaunchKernelGGL(selftest_cold_math_kernel, dim3(256 * 8), dim3(256), 0, skr::as_stream(stream), 0x0f800000u, 0x7f7fffffu,
+                       n_pairs, d_bad);
+    SKR_LAUNCH_CHECK();
+    unsigned long long h[4] = {0, 0, 0, 0};
+    SKR_HIP(hipMemcpyAsync(h, d_bad, sizeof(h), hipMemcpyDeviceToHost, skr::as_stream(stream)));
+    SKR_HIP(hipStreamSynchronize(skr::as_stream(stream)));
+    (void)hipFree(d_bad);
+    h_mismatches[0] = h[0];
+    h_mismatches[1] = h[1];
+    h_mismatches[2] = h[2];
+    h_mismatches[3] = h[3];
+    return SKR_OK;
+}
+
+}  // extern "C"

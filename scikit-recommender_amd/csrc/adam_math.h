@@ -1,0 +1,213 @@
+// adam_math.h -- the Adam arithmetic shared by the optimiser (adam.hip) and the fused BPR step (bpr_fused.hip): the
+// per-element update, its exact cheaper evaluations for zero-gradient updates, and the per-step scalars on the host.
+#pragma once
+#include "skr_common.h"
+
+#include <cmath>
+
+namespace skr {
+
+// per-step scalars of torch.optim.Adam's single-tensor path (adam_scalars)
+struct AdamArgs {
+    float one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps;
+};
+
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamArgs& a) {
+    m = m + a.one_minus_b1 * (g - m);           // exp_avg.lerp_(grad, 1-beta1)
+    v = v * a.b2 + (a.one_minus_b2 * g) * g;    // mul_(beta2).addcmul_(grad, grad, value=1-beta2)
+    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+    p = p + (a.neg_step_size * m) / denom;      // addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+// the same update when sqrt(1 - beta2^t) is exactly 1.0f (beta2 = 0.999: from step ~16 600 on): x / 1.0f == x, so the
+// correctly rounded division by the bias correction (a dozen instructions) is left out -- results are identical
+__device__ __forceinline__ void adam_elem_unit_bc2(float& p, float g, float& m, float& v, const AdamArgs& a) {
+    m = m + a.one_minus_b1 * (g - m);
+    v = v * a.b2 + (a.one_minus_b2 * g) * g;
+    const float denom = sqrtf(v) + a.eps;
+    p = p + (a.neg_step_size * m) / denom;
+}
+
+// the scalars of a block of k <= AB_KMAX consecutive steps (adam.hip K2b, bpr_fused.hip K2c)
+constexpr int AB_KMAX = 64;
+struct AdamBlockArgs {
+    float one_minus_b1, b2, one_minus_b2, eps;
+    float neg_step_size[AB_KMAX], bc2_sqrt[AB_KMAX];
+    float nss_bound[AB_KMAX];   // max |neg_step_size[s']| over s' >= s: the bound the at-rest test of a run starting at s needs
+                                // (torch's -lr / bc1 only shrinks with the step: then this IS |neg_step_size[s]|; TF's
+                                //  -lr * sqrt(bc2) / bc1 falls, then rises again towards lr)
+    int k;
+    // thresholds of the "parameter at rest" test of adam_cold_rows_kernel (0 switches the test off)
+    float rest_eps;   // 2^-28 * eps
+    float rest_b2k;   // a lower bound of beta2^k
+    // ranges of the "ordinary magnitudes" test (fast_mlo = +inf switches it off)
+    float fast_vlo, fast_mlo, fast_mhi;
+    unsigned long long* stats;   // optional census (SKR_COLD_STATS=1): cold blocks at rest / ordinary / general
+};
+
+// Square root and division for ORDINARY MAGNITUDES, bit-identical to sqrtf(x) and n / d as compiled under
+// -fhip-fp32-correctly-rounded-divide-sqrt but cheaper:
+//   div_ordinary   the compiler's own expansion (v_rcp_f32, one Newton step, two quotient corrections, final fma)
+//                  minus v_div_scale_f32 and v_div_fixup_f32, which are the identity (VCC = 0) / a pass-through when
+//                  d is normal with |d| < 2^126, |n| >= 2^-103 and -125 <= exponent(n) - exponent(d) < 96
+//                  (CDNA3/4 ISA, V_DIV_SCALE_F32 / V_DIV_FIXUP_F32): same instructions on the same values;
+//   sqrt_ordinary  v_rsq_f32 and one fused correction s + (x - s*s) * r/2 instead of v_sqrt_f32 and two residual tests:
+//                  a different route to the correctly rounded root, so it is PROVEN BY ENUMERATION -- the self-test runs
+//                  it against sqrtf on every float of [2^-96, FLT_MAX] (the range it is used on is [2^-90, 2^20]).
+// skr_selftest_cold_math does that enumeration and tries the division on 2^32 hashed operand pairs of its range; as
+// a control it also counts how often the raw v_sqrt_f32 differs from sqrtf (it must: that is why a correction exists).
+__device__ __forceinline__ float sqrt_ordinary(float x) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    const float s = x * r, h = 0.5f * r;
+    return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);
+}
+
+__device__ __forceinline__ float div_ordinary(float n, float d) {
+    float r = __builtin_amdgcn_rcpf(d);
+    const float e = __builtin_fmaf(-d, r, 1.0f);
+    r = __builtin_fmaf(e, r, r);
+    float q = n * r;
+    float t = __builtin_fmaf(-d, q, n);
+    q = __builtin_fmaf(t, r, q);
+    t = __builtin_fmaf(-d, q, n);
+    return __builtin_fmaf(t, r, q);
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// one zero-gradient update of two rows of ordinary magnitudes (v > 0, so v*b2 + (c2*0)*0 == v*b2)
+template <bool UNIT_BC2>
+__device__ __forceinline__ void adam_pair_ordinary(f32x2& p, f32x2& m, f32x2& v, const AdamArgs& a) {
+    m = m + a.one_minus_b1 * (0.0f - m);
+    v = v * a.b2;
+    f32x2 sq;
+    sq.x = sqrt_ordinary(v.x);
+    sq.y = sqrt_ordinary(v.y);
+    if (!UNIT_BC2) {
+        sq.x = div_ordinary(sq.x, a.bc2_sqrt);
+        sq.y = div_ordinary(sq.y, a.bc2_sqrt);
+    }
+    const f32x2 d = sq + a.eps, n = a.neg_step_size * m;
+    f32x2 q;
+    q.x = div_ordinary(n.x, d.x);
+    q.y = div_ordinary(n.y, d.y);
+    p = p + q;
+}
+
+template <bool UNIT_BC2>
+__device__ __forceinline__ void adam_one_ordinary(float& p, float& m, float& v, const AdamArgs& a) {
+    m = m + a.one_minus_b1 * (0.0f - m);
+    v = v * a.b2;
+    float sq = sqrt_ordinary(v);
+    if (!UNIT_BC2) sq = div_ordinary(sq, a.bc2_sqrt);
+    p = p + div_ordinary(a.neg_step_size * m, sq + a.eps);
+}
+
+// the two per-lane tests of the cold pass (and of the hot step's catch-up): see adam_cold_rows_kernel (adam.hip).  nss0 = the largest
+// |neg_step_size| among the zero-gradient updates in question (AdamBlockArgs::nss_bound of the first of them)
+__device__ __forceinline__ bool lane_at_rest(float pp, float mm, float vv, float nss0, const AdamBlockArgs& a) {
+    const float ap = fabsf(pp), n0 = nss0 * fabsf(mm);
+    const float r = ap * 0x1p-29f;
+    const float bound = (r * r) * (vv * a.rest_b2k);
+    const bool small = n0 < ap * a.rest_eps || (n0 * n0 < bound && bound >= 0x1p-120f);
+    return __float_as_uint(vv) <= 0x7f800000u && ap >= 0x1p-60f && small;
+}
+
+__device__ __forceinline__ bool lane_ordinary(float mm, float vv, const AdamBlockArgs& a) {
+    const float am = fabsf(mm);
+    return vv >= a.fast_vlo && vv <= 0x1p20f && am >= a.fast_mlo && am <= a.fast_mhi;
+}
+
+// A run of zero-gradient updates of one row of ordinary magnitudes, indices [s, s_to).  The quotient of update s depends on
+// m_s and v_s only -- not on p -- so the square-root / division chains of consecutive updates are independent of each other:
+// four of them are laid side by side (one wavefront alone on its SIMD otherwise waits out the latency of every one of the
+// ~25 dependent instructions of a chain: ~200 cycles per update instead of ~70), and p takes the quotients in order -- the
+// same operations on the same values as update after update.
+template <bool UNIT_BC2>
+__device__ __forceinline__ void ordinary_run(float& p, float& m, float& v, const AdamBlockArgs& a, int& s, int s_to) {
+    for (; s + 4 <= s_to; s += 4) {
+        float ms[4], vs[4], q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            m = m + a.one_minus_b1 * (0.0f - m);
+            v = v * a.b2;
+            ms[u] = m;
+            vs[u] = v;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float sq = sqrt_ordinary(vs[u]);
+            if (!UNIT_BC2) sq = div_ordinary(sq, a.bc2_sqrt[s + u]);
+            q[u] = div_ordinary(a.neg_step_size[s + u] * ms[u], sq + a.eps);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p = p + q[u];
+    }
+    for (; s < s_to; ++s) {
+        AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+        adam_one_ordinary<UNIT_BC2>(p, m, v, one);
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------
+// SKR_COLD_STATS=1: the device census of how the cold passes sorted their blocks, or NULL (defined in adam.hip)
+__attribute__((visibility("hidden"))) unsigned long long* cold_stats_buffer();
+
+// the fields every step of a run shares (A: AdamArgs or AdamBlockArgs)
+template <class A>
+static inline void adam_shared_fields(A& a, float beta1, float beta2, float eps) {
+    a.one_minus_b1 = static_cast<float>(1.0 - static_cast<double>(beta1));
+    a.b2 = beta2;
+    a.one_minus_b2 = static_cast<float>(1.0 - static_cast<double>(beta2));
+    a.eps = eps;
+}
+
+static inline void adam_scalars(float lr, float beta1, float beta2, int64_t step_t, float* neg_step_size, float* bc2_sqrt, bool tf = false) {
+    // torch/optim/adam.py _single_tensor_adam: python-double scalars, cast to fp32 at the tensor ops
+    const double b1 = static_cast<double>(beta1), b2 = static_cast<double>(beta2);
+    const double bc1 = 1.0 - std::pow(b1, static_cast<double>(step_t));
+    const double bc2 = 1.0 - std::pow(b2, static_cast<double>(step_t));
+    if (tf) {
+        // tf.train.AdamOptimizer (GRU4RecPlus.py:192): p -= lr_t * m / (sqrt(v) + eps), lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t):
+        // the second bias correction sits in the step size, the denominator has none
+        *neg_step_size = static_cast<float>(-(static_cast<double>(lr) * std::sqrt(bc2) / bc1));
+        *bc2_sqrt = 1.0f;
+        return;
+    }
+    *neg_step_size = static_cast<float>(-(static_cast<double>(lr) / bc1));
+    *bc2_sqrt = static_cast<float>(std::sqrt(bc2));
+}
+
+// the k steps' scalars of a block that starts after step_t0, and the running maximum the at-rest tests use
+static inline void adam_block_scalars(AdamBlockArgs& a, float lr, float beta1, float beta2, int64_t step_t0, int k, bool tf) {
+    for (int s = 0; s < k; ++s) adam_scalars(lr, beta1, beta2, step_t0 + 1 + s, &a.neg_step_size[s], &a.bc2_sqrt[s], tf);
+    float mx = 0.0f;
+    for (int s = k - 1; s >= 0; --s) {
+        mx = std::fmax(mx, std::fabs(a.neg_step_size[s]));
+        a.nss_bound[s] = mx;
+    }
+}
+
+// thresholds of the at-rest / ordinary-magnitude tests for a run of up to k zero-gradient updates whose scalars sit in
+// a.neg_step_size[0 .. k-1] / a.bc2_sqrt[0 .. k-1] (|neg_step_size| falls, bc2_sqrt rises with the step)
+static inline void adam_block_thresholds(AdamBlockArgs& a, float lr, float beta1, float beta2, float eps, int k) {
+    const bool sane = beta1 > 0.0f && beta1 < 1.0f && beta2 > 0.0f && beta2 < 1.0f && lr > 0.0f && eps >= 0.0f &&
+                      std::isfinite(lr) && std::isfinite(eps);
+    a.rest_eps = sane ? eps * 0x1p-28f : 0.0f;
+    a.rest_b2k = sane ? static_cast<float>(std::pow(static_cast<double>(beta2), k) * (1.0 - 1e-4)) : 0.0f;
+    // ordinary magnitudes for all k updates (ranges of sqrt_ordinary / div_ordinary with room to spare): v in
+    // [2^-90, 2^20] throughout, |nss*m| in [2^-100, 2^40] throughout, eps <= 2^20, sqrt(1 - beta2^t) >= 2^-10
+    double nss_max = 0.0, nss_min = INFINITY;      // torch's scalars: the first and the last step's; TF's are not monotone
+    for (int s_ = 0; s_ < k; ++s_) {
+        nss_max = std::fmax(nss_max, std::fabs(static_cast<double>(a.neg_step_size[s_])));
+        nss_min = std::fmin(nss_min, std::fabs(static_cast<double>(a.neg_step_size[s_])));
+    }
+    const double m_lo = 0x1p-100 / (nss_min * std::pow(static_cast<double>(beta1), k) * 0.99), m_hi = 0x1p40 / nss_max;
+    const bool ord = sane && eps <= 0x1p20f && a.bc2_sqrt[0] >= 0x1p-10f && a.rest_b2k > 0.0f && m_lo < 1e30 && m_hi > 1e-30 &&
+                     std::isfinite(m_lo) && std::isfinite(m_hi);
+    a.fast_vlo = ord ? static_cast<float>(0x1p-90 / static_cast<double>(a.rest_b2k)) : 0.0f;
+    a.fast_mlo = ord ? static_cast<float>(m_lo) : INFINITY;
+    a.fast_mhi = ord ? static_cast<float>(std::fmin(m_hi, 1e38)) : 0.0f;
+}
+
+}  // namespace skr

@@ -156,7 +156,7 @@ class BPRMF(AbstractRecommender):
                     _hip.check(rc)
             self.step_losses = spread.sum(1)
             return
-        # Temporally blocked dense Adam (csrc/train.hip, K2b): the epoch's batches are known, so for every block of
+        # Temporally blocked dense Adam (csrc/adam.hip, K2b): the epoch's batches are known, so for every block of
         # `kblk` steps the rows no batch of the block touches get their kblk zero-gradient updates in one pass and
         # only the touched rows are stepped batch by batch -- the same updates in the same arithmetic, bit-identical
         # to the loop above, with 1/kblk of its optimiser traffic.
@@ -177,7 +177,7 @@ class BPRMF(AbstractRecommender):
             if n_full_blocks and not (self.fused_step and kblk * 5 * bsz <= (1 << 20)) else None
         first = 0
         if self.fused_step and n_full_blocks and kblk * 5 * bsz <= (1 << 20):      # slot numbers have 20 bits
-            # full blocks: ONE launch per step -- the hot rows' Adam is evaluated inside the BPR kernel (csrc/train.hip K2c)
+            # full blocks: ONE launch per step -- the hot rows' Adam is evaluated inside the BPR kernel (csrc/bpr_fused.hip K2c)
             from .fused import FusedBlocks
             if self._fused is None:
                 self._fused = FusedBlocks(opt, 0, nu, nu + ni, reg)

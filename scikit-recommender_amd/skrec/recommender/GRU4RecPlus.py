@@ -5,7 +5,7 @@ Karatzoglou).  Same constructor, config fields, session-parallel ``fit`` loop (:
 (:256-302) and ``predict`` (:309-324) as the reference; the graph itself (embedding lookup, GRUCell stack,
 logits against the batch's own next items plus ``n_sample`` popularity^alpha negatives, bpr_max / top1_max
 loss, l2 term, TF-style dense Adam) runs through ``skr_gru_cell_fwd/_bwd``, ``skr_session_loss``,
-``skr_session_out_grads``, ``skr_scatter_add_rows`` and ``skr_adam_step`` (csrc/gru.hip, train.hip).
+``skr_session_out_grads``, ``skr_scatter_add_rows`` and ``skr_adam_step`` (csrc/gru.hip, train.hip, adam.hip).
 
 What differs, and why:
 
@@ -131,7 +131,7 @@ class SessionGRU(object):
     def zero_states(self, b):
         return [torch.zeros((b, h), dtype=torch.float32, device=self.device) for h in self.hids]
 
-    # ---- the dense Adam blocked in time (csrc/train.hip K2b, TF arithmetic): the inputs and targets of the next k steps are
+    # ---- the dense Adam blocked in time (csrc/adam.hip K2b, TF arithmetic): the inputs and targets of the next k steps are
     # known (the session-parallel schedule is host logic on the data, the negatives' uniforms can be drawn ahead in the
     # reference's order), so the 64-float blocks of the flat buffer that none of the k steps names get their k
     # zero-gradient updates in ONE pass on a side stream and only the named rows -- at most b + (b + n_sample) item rows,

@@ -109,11 +109,11 @@ class SeqPairwiseRecommender(AbstractRecommender):
             pflat, pgrad, pm, pv = (t.data_ptr() for t in (opt.flat, opt.grad, opt.m, opt.v))
             n_par = opt.flat.numel()
             head = (pflat, pgrad, pm, pv, n_par, opt.lr, opt.betas[0], opt.betas[1], opt.eps)
-            dense, wd = (L.skr_adam_step_wd, (opt.weight_decay,)) if opt.weight_decay else (L.skr_adam_step, ())
+            dense = opt._entry("step")
             for k, (a, b) in enumerate(bounds):
                 rc = step(pcu + 4 * a, pcl + bl * a, pcp + bp * a, pcn + bn * a, b - a, ploss + 8 * S * k, st)
                 opt.t += 1
-                rc |= dense(*head, *wd, opt.t, 1, None, st)
+                rc |= dense(*head, opt.t, 1, None, st)
                 if rc:
                     _hip.check(rc)
             self.step_losses = spread.sum(1)

@@ -110,6 +110,16 @@ class DenseAdam(object):
         assert self.weight_decay >= 0.0 and not (self.weight_decay and self.tf_epsilon)
         self.t = 0
 
+    def _entry(self, kind):
+        """the library's entry point for ``kind`` -- "step" (one dense launch), "cold" or "hot" (the blocked form) -- in this
+        optimiser's arithmetic: plain, ``_tf`` or ``_wd``; the ``_wd`` functions' extra float (after eps) is already applied"""
+        from .. import _hip
+        name = {"step": "skr_adam_step", "cold": "skr_adam_block_cold", "hot": "skr_adam_block_hot"}[kind]
+        if not self.weight_decay:
+            return getattr(_hip.lib(), name + ("_tf" if self.tf_epsilon else ""))
+        fn, wd, at = getattr(_hip.lib(), name + "_wd"), self.weight_decay, 8 if kind == "cold" else 9
+        return lambda *a: fn(*a[:at], wd, *a[at:])
+
     # ---- temporally blocked stepping (bit-identical to step() after every batch) -----------------------------
     def begin_block(self, block_ids, k, per_step=None):
         """``block_ids``: int32 device tensor with the index (float offset / 64) of every 64-float block that any
@@ -140,13 +150,7 @@ class DenseAdam(object):
         self._ev_marked.record(cur)
         self._side.wait_event(self._ev_marked)
         self.launch_cold(self._blk_tag, self._blk_serial, int(k))
-        hot = L.skr_adam_block_hot_tf if self.tf_epsilon else L.skr_adam_block_hot
-        if self.weight_decay:
-            wd = self.weight_decay
-
-            def hot(pp, pg, pm, pv, n, lr, b1, b2, eps, *rest):
-                return L.skr_adam_block_hot_wd(pp, pg, pm, pv, n, lr, b1, b2, eps, wd, *rest)
-        self._hot = (hot, self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+        self._hot = (self._entry("hot"), self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                      self.flat.numel(), block_ids.data_ptr(), block_ids.numel(), self._blk_claim.data_ptr(), st,
                      self.t, int(k), None if per_step is None else int(per_step))
 
@@ -176,14 +180,9 @@ class DenseAdam(object):
         if timing is not None:
             e0, e1 = pool.pop() if pool is not None else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             e0.record(self._side)
-        L = _hip.lib()
-        head = (_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
-                self.eps)
-        tail = (self.t, int(k), _hip.ptr(tag), int(serial), self._side.cuda_stream)
-        if self.weight_decay:
-            _hip.check(L.skr_adam_block_cold_wd(*head, self.weight_decay, *tail))
-        else:
-            _hip.check((L.skr_adam_block_cold_tf if self.tf_epsilon else L.skr_adam_block_cold)(*head, *tail))
+        _hip.check(self._entry("cold")(_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
+                                       self.betas[0], self.betas[1], self.eps, self.t, int(k), _hip.ptr(tag), int(serial),
+                                       self._side.cuda_stream))
         if timing is not None:
             e1.record(self._side)
             timing.append((e0, e1, int(k)))
@@ -216,11 +215,6 @@ class DenseAdam(object):
     def step(self):
         from .. import _hip
         self.t += 1
-        L = _hip.lib()
-        head = (_hip.ptr(self.flat), _hip.ptr(self.grad), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
-                self.betas[0], self.betas[1], self.eps)
-        tail = (self.t, 1, _hip.ptr(self.touch), _hip.stream())
-        if self.weight_decay:
-            _hip.check(L.skr_adam_step_wd(*head, self.weight_decay, *tail))
-        else:
-            _hip.check((L.skr_adam_step_tf if self.tf_epsilon else L.skr_adam_step)(*head, *tail))
+        _hip.check(self._entry("step")(_hip.ptr(self.flat), _hip.ptr(self.grad), _hip.ptr(self.m), _hip.ptr(self.v),
+                                       self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t, 1,
+                                       _hip.ptr(self.touch), _hip.stream()))

@@ -1,4 +1,4 @@
-"""Host side of the one-launch BPRMF step (csrc/train.hip K2c: ``skr_bpr_fused_step`` / ``skr_bpr_fused_end``).
+"""Host side of the one-launch BPRMF step (csrc/bpr_fused.hip K2c: ``skr_bpr_fused_step`` / ``skr_bpr_fused_end``).
 
 The reference's step is ``loss.backward(); optimizer.step()`` with a DENSE Adam (BPRMF.py:108-127): every row moves at
 every step.  The blocked optimiser (base.DenseAdam.begin_block) already gives the rows no batch of a k-step block touches

@@ -1,4 +1,4 @@
-"""GPU suite of HGN (csrc/hgn.hip, the weight-decay Adam of csrc/train.hip, skrec/recommender/HGN.py): golden replay of
+"""GPU suite of HGN (csrc/hgn.hip, the weight-decay Adam of csrc/adam.hip, skrec/recommender/HGN.py): golden replay of
 the reference's fit(), the step kernel against float64 autograd of a plain-torch restatement, the ordered gate
 gradients, skr_adam_step_wd against torch and the blocked form against the dense one, the query rows against float64
 numpy, the evaluator's fused path against its generic one, the reference's KeyError, and the command line."""

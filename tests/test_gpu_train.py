@@ -609,6 +609,20 @@ def test_fused_step_with_rows_shared_inside_a_step(k, n_blocks):
     assert float(fb.work[:, 6 * fb.cap * 64:].abs().max()) == 0.0
 
 
+def _aged_rows(rng, rows, age=None):
+    """[rows, 64] parameters and Adam moments as `age[r]` steps without a gradient leave them: lively, of ordinary
+    magnitudes, at rest, down to denormal and zero.  age = None: random ages with a dense sweep across the regime boundaries"""
+    if age is None:
+        age = rng.integers(0, 3000, rows)
+        sweep = min(200, rows // 2)
+        age[:sweep] = np.arange(sweep) * 5
+    age = np.asarray(age)
+    m = (rng.standard_normal((rows, 64)) * 1e-3 * np.exp(np.log(0.9) * age)[:, None]).astype(np.float32)
+    v = (rng.random((rows, 64)) * 1e-6 * np.exp(np.log(0.999) * age)[:, None]).astype(np.float32)
+    p = (rng.standard_normal((rows, 64)) * 0.05).astype(np.float32)
+    return p, m, v, age
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,t0,eps,lr", [(8, 0, 1e-8, 1e-3), (16, 20000, 1e-8, 1e-3), (5, 16596, 1e-8, 5e-2), (8, 100, 0.0, 1e-3),
                                          (8, 3, 1e-3, 1e-3), (32, 0, 1e-8, 1e-3), (32, 16580, 1e-8, 1e-3), (32, 777, 1e-8, 1e-2),
@@ -623,11 +637,7 @@ def test_cold_pass_rest_regime_is_bit_identical(k, t0, eps, lr):
     L, st = _hip.lib(), _hip.stream
     rng = np.random.default_rng(7 * k + t0)
     rows = 6000
-    age = rng.integers(0, 3000, rows)
-    age[:200] = np.arange(200) * 5                                   # a dense sweep across the regime boundaries
-    m = (rng.standard_normal((rows, 64)) * 1e-3 * np.exp(np.log(0.9) * age)[:, None]).astype(np.float32)
-    v = (rng.random((rows, 64)) * 1e-6 * np.exp(np.log(0.999) * age)[:, None]).astype(np.float32)
-    p = (rng.standard_normal((rows, 64)) * 0.05).astype(np.float32)
+    p, m, v, age = _aged_rows(rng, rows)
     sp = rows - 400                                                   # special rows at the end
     m[sp:sp + 40] = 0.0
     v[sp:sp + 40] = 0.0                                               # never touched
@@ -783,3 +793,178 @@ def test_blocked_adam_lists_may_hold_empty_slots():
     assert L.skr_bpr_fused_end(_hip.ptr(p), _hip.ptr(m), _hip.ptr(v), n, _hip.ptr(w), 64, _hip.ptr(i32), _hip.ptr(i32), _hip.ptr(i32), 1e-3,
                                0.9, 0.999, 1e-8, 0, 4, None, 0, 1, st()) == -1          # which = 1 needs the next block's tags
     torch.cuda.synchronize()
+
+
+# ---- the weight-decay entry points against the plain ones and against each other, BIT FOR BIT (finite inputs, eps = 1e-8) ----
+def _bits(t):
+    import torch
+    return t.view(torch.int32)
+
+
+def _same_bits(a, b):
+    import torch
+    return all(torch.equal(_bits(x), _bits(y)) for x, y in zip(a, b))
+
+
+def _dense_run(n, wd, use_touch, seed, steps=5):
+    """`steps` dense launches from one seeded state; gradients live in ~60 % of the 64-float blocks, the touch bytes (if
+    any) are 1 exactly there.  wd = None: skr_adam_step.  -> final p, m, v, g and every step's touch bytes after the launch"""
+    import torch
+    from gpu_utils import to_dev
+    from skrec import _hip
+    L = _hip.lib()
+    rng = np.random.default_rng(seed)
+    nb = (n + 63) // 64
+    p, m = to_dev((rng.standard_normal(n) * 0.1).astype(np.float32)), to_dev((rng.standard_normal(n) * 1e-3).astype(np.float32))
+    v = to_dev((rng.random(n) * 1e-6).astype(np.float32))
+    touched = []
+    for t in range(1, steps + 1):
+        blocks = rng.random(nb) >= 0.4
+        g = to_dev(np.where(np.repeat(blocks, 64)[:n], rng.standard_normal(n) * 1e-2, 0.0).astype(np.float32))
+        touch = to_dev(blocks.astype(np.uint8)) if use_touch else None
+        head = (_hip.ptr(p), _hip.ptr(g), _hip.ptr(m), _hip.ptr(v), n, 1e-3, 0.9, 0.999, 1e-8)
+        tail = (t, 1, _hip.ptr(touch), _hip.stream())
+        _hip.check(L.skr_adam_step(*head, *tail) if wd is None else L.skr_adam_step_wd(*head, wd, *tail))
+        torch.cuda.synchronize()
+        assert float(g.abs().max()) == 0.0
+        if use_touch:
+            touched.append(touch)
+    return (p, m, v, g), touched
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_touch", [False, True])
+@pytest.mark.parametrize("n", [3, 64, 259, 4099])       # tail only, one full block, a partial last block, several workgroups
+def test_adam_wd_zero_equals_plain(n, use_touch):
+    """skr_adam_step_wd(weight_decay = 0) == skr_adam_step: fmaf(0, p, g) is g for finite p"""
+    a, ta = _dense_run(n, 0.0, use_touch, seed=n)
+    b, tb = _dense_run(n, None, use_touch, seed=n)
+    assert _same_bits(a, b)
+    assert len(ta) == len(tb) and all(bool((x == y).all()) for x, y in zip(ta, tb))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [3, 64, 259, 4099])
+def test_adam_wd_touch_bytes_change_nothing(n):
+    """under weight decay every element moves whether or not its block carries a gradient: the touch bytes only spare
+    the read of a zero gradient, and come back cleared"""
+    a, ta = _dense_run(n, 1e-2, True, seed=n)
+    b, _ = _dense_run(n, 1e-2, False, seed=n)
+    assert _same_bits(a, b)
+    assert len(ta) == 5 and all(int(x.max()) == 0 for x in ta)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,t0,tail_hot", [(1, 0, False), (3, 16597, True), (64, 40, False)])
+def test_cold_pass_wd_zero_equals_plain(k, t0, tail_hot):
+    """skr_adam_block_cold_wd(weight_decay = 0) == skr_adam_block_cold over rows of every age: the float4 kernel's full
+    update against the rows kernel's three exact evaluations (at rest, ordinary magnitudes, general)"""
+    import torch
+    from gpu_utils import to_dev
+    from skrec import _hip
+    L, st = _hip.lib(), _hip.stream
+    rng = np.random.default_rng(100 + k)
+    nb = 38
+    n = 64 * 37 + 5
+    p, m, v, _ = _aged_rows(rng, nb)
+    for x in (p, m, v):
+        x[[5, 20, 33]] = 0.0                                        # padding: p = m = v = +0
+    tag_h = (rng.random(nb) < 0.25).astype(np.int32)
+    tag_h[nb - 1] = 1 if tail_hot else 0
+    assert 0 < tag_h.sum() < nb // 2
+    tag = to_dev(tag_h)
+    start = [to_dev(x.reshape(-1)[:n].copy()) for x in (p, m, v)]
+    a, b = [x.clone() for x in start], [x.clone() for x in start]
+    _hip.check(L.skr_adam_block_cold_wd(*(_hip.ptr(x) for x in a), n, 1e-3, 0.9, 0.999, 1e-8, 0.0, t0, k, _hip.ptr(tag), 1, st()))
+    _hip.check(L.skr_adam_block_cold(*(_hip.ptr(x) for x in b), n, 1e-3, 0.9, 0.999, 1e-8, t0, k, _hip.ptr(tag), 1, st()))
+    torch.cuda.synchronize()
+    assert _same_bits(a, b)
+    hot = to_dev(np.repeat(tag_h == 1, 64)[:n])
+    assert all(torch.equal(_bits(x)[hot], _bits(x0)[hot]) for x, x0 in zip(a, start))      # hot blocks are left alone
+    assert not torch.equal(_bits(a[1])[~hot], _bits(start[1])[~hot])                      # and the cold ones moved
+
+
+def _blocked_hot_run(n, k, t0, named, state, grads, wd, cold):
+    """mark the blocks of named[-1] hot, the cold pass if asked for (skr_adam_block_cold_wd), then k hot launches (wd = None:
+    skr_adam_block_hot, else skr_adam_block_hot_wd); before launch s the gradient of step s is put into the blocks it
+    names.  -> p, m, v, g, claim, tag"""
+    import torch
+    from gpu_utils import to_dev
+    from skrec import _hip
+    L, st = _hip.lib(), _hip.stream
+    p, m, v = (x.clone() for x in state)
+    g = torch.zeros_like(p)
+    nb = (n + 63) // 64
+    tag = torch.zeros(nb, dtype=torch.int32, device="cuda")
+    claim = torch.zeros(nb, dtype=torch.int32, device="cuda")
+    ids = [to_dev(np.asarray(x, dtype=np.int32)) for x in named]
+    _hip.check(L.skr_adam_block_mark(_hip.ptr(ids[-1]), ids[-1].numel(), 0, 64, _hip.ptr(tag), 1, _hip.ptr(claim), t0, st()))
+    if cold:
+        _hip.check(L.skr_adam_block_cold_wd(_hip.ptr(p), _hip.ptr(m), _hip.ptr(v), n, 1e-3, 0.9, 0.999, 1e-8, wd, t0, k, _hip.ptr(tag), 1,
+                                            st()))
+    for s in range(k):
+        g += grads[s]
+        head = (_hip.ptr(p), _hip.ptr(g), _hip.ptr(m), _hip.ptr(v), n, 1e-3, 0.9, 0.999, 1e-8)
+        tail = (t0, t0 + s + 1, _hip.ptr(ids[s]), ids[s].numel(), 0, 64, _hip.ptr(claim), st())
+        _hip.check(L.skr_adam_block_hot(*head, *tail) if wd is None else L.skr_adam_block_hot_wd(*head, wd, *tail))
+    torch.cuda.synchronize()
+    return p, m, v, g, claim, tag
+
+
+def _hot_case(n, named, age, seed):
+    """start state (block b aged age[b] steps) and, per step, a gradient in exactly the blocks the step names"""
+    from gpu_utils import to_dev
+    rng = np.random.default_rng(seed)
+    nb = (n + 63) // 64
+    state = [to_dev(x.reshape(-1)[:n].copy()) for x in _aged_rows(rng, nb, age)[:3]]
+    grads = []
+    for ids in named:
+        mask = np.repeat(np.isin(np.arange(nb), [i for i in ids if i >= 0]), 64)[:n]
+        grads.append(to_dev(np.where(mask, rng.standard_normal(n) * 1e-2, 0.0).astype(np.float32)))
+    return state, grads
+
+
+@pytest.mark.gpu
+def test_blocked_adam_wd_equals_dense_launches():
+    """one skr_adam_block_cold_wd + k skr_adam_block_hot_wd == k skr_adam_step_wd: ten blocks, the last one partial; blocks
+    1, 4 and 9 hot, block 4 named at steps 2 and 5 only (it catches up one, then two steps with g' = wd * p); a duplicate
+    and an empty slot in every list"""
+    import torch
+    from skrec import _hip
+    n, k, t0, wd = 64 * 9 + 5, 5, 7, 1e-2
+    named = [[1, 9, 1, -1], [4, 1, 9, 4, -1], [1, 9, 1, -1], [1, 9, 1, -1], [4, 1, 9, 4, -1]]
+    state, grads = _hot_case(n, named, [0] * 10, seed=41)
+    p, m, v, g, claim, tag = _blocked_hot_run(n, k, t0, named, state, grads, wd, cold=True)
+    assert tag.tolist() == [0, 1, 0, 0, 1, 0, 0, 0, 0, 1]
+    assert claim.tolist() == [0, t0 + k, 0, 0, t0 + k, 0, 0, 0, 0, t0 + k]
+    assert float(g.abs().max()) == 0.0                              # the gradients were consumed
+    dp, dm, dv = (x.clone() for x in state)
+    for s in range(k):
+        dg = grads[s].clone()
+        _hip.check(_hip.lib().skr_adam_step_wd(_hip.ptr(dp), _hip.ptr(dg), _hip.ptr(dm), _hip.ptr(dv), n, 1e-3, 0.9, 0.999, 1e-8, wd,
+                                               t0 + s + 1, 1, None, _hip.stream()))
+    torch.cuda.synchronize()
+    assert _same_bits((p, m, v), (dp, dm, dv))
+    assert not torch.equal(_bits(p), _bits(state[0]))
+
+
+@pytest.mark.gpu
+def test_hot_step_wd_zero_equals_plain():
+    """skr_adam_block_hot_wd(weight_decay = 0) == skr_adam_block_hot, catch-up included: block 4 (named at steps 2 and 6) is
+    at rest when it catches up one step and of ordinary magnitudes -- its moments fresh from step 2's gradient -- when it
+    catches up three; block 9, the partial one, is of ordinary magnitudes two steps behind; block 6 mixes lanes with zero
+    moments and lively ones (neither shortcut applies).  The plain kernel's exact shortcuts against the full update"""
+    n, k, t0 = 64 * 9 + 5, 6, 200
+    named = [[1, 1, -1], [4, 1, 4, -1], [9, 1, 1, -1], [6, 1, -1, 6], [1, 1, -1], [4, 1, 9, 6, 4, -1]]
+    age = [0, 0, 0, 0, 1000, 0, 0, 0, 0, 0]
+    state, grads = _hot_case(n, named, age, seed=43)
+    state[1][6 * 64:6 * 64 + 64:3] = 0.0
+    state[2][6 * 64:6 * 64 + 64:3] = 0.0
+    assert float(state[1][4 * 64:5 * 64].abs().max()) < 1e-40       # block 4 starts at rest
+    a = _blocked_hot_run(n, k, t0, named, state, grads, 0.0, cold=False)
+    b = _blocked_hot_run(n, k, t0, named, state, grads, None, cold=False)
+    assert _same_bits(a, b)                                         # p, m, v, g, claim, tag
+    assert float(a[3].abs().max()) == 0.0
+    assert a[4].tolist() == [0, t0 + k, 0, 0, t0 + k, 0, t0 + k, 0, 0, t0 + k]
+    assert all(not bool((_bits(x)[64 * c:64 * c + 5] == _bits(x0)[64 * c:64 * c + 5]).all()) for c in (1, 4, 6, 9)
+               for x, x0 in zip(a[:2], state[:2]))                  # every hot block moved
