@@ -403,3 +403,30 @@ def test_fused_default_arithmetic_on_random_cases():
     n_rows, n_id_rows, worst, n_rej = mod.run(30, seed=7, verbose=False)
     assert n_id_rows > 0.6 * n_rows and worst < 1e-6
     assert 0 < n_rej < n_rows          # both the guarded kernel and its fall-back were exercised
+
+
+def _fused_bits():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_fused_bits", os.path.join(REPO, "tests", "golden", "make_golden_fused_bits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_fused_topk_bits_equal_the_recorded_ones(fused_mode):
+    """the evaluator's output BITS in each arithmetic, on the smallest shapes that reach each path of the sweep (listed in
+    tests/golden/make_golden_fused_bits.py, which recorded tests/golden/fused_topk_bits.json): ids, score bit patterns and the
+    guard's count.  A refactor must hold them; the float64 tests above would pass a reordering of the piece products."""
+    import json
+    G = _fused_bits()
+    with open(os.path.join(REPO, "tests", "golden", "fused_topk_bits.json")) as f:
+        rec = json.load(f)
+    assert [tuple(c["case"]) for c in rec["cases"]] == G.CASES
+    for c in rec["cases"]:
+        case = tuple(c["case"])
+        inp = G.make_inputs(case)
+        assert G.inputs_digest(inp) == c["inputs_sha256"], \
+            f"{case}: the generated INPUTS differ from the recorded ones (numpy {np.__version__} vs {rec['numpy']}), not the kernel"
+        got = G.run_case(inp, case[2], fused_mode)
+        print(case, fused_mode, got)
+        assert got == c["modes"][fused_mode], (case, fused_mode)
