@@ -753,6 +753,55 @@ int skr_hgn_queries(const float* d_U, const float* d_E, const float* d_gates, co
                     const int32_t* d_windows, int n_users, int n_rows, int pad_idx, int dim, int seq_L, float* d_Q,
                     void* stream);
 
+/* ============================================================================================
+ * S -- MultVAE, variational autoencoder with a multinomial likelihood (csrc/multvae.hip)
+ * replaces: _MultVAE.q_graph / forward and MultVAE.fit's step (recommender/MultVAE.py:99-136,179-201) for p_dims = [d],
+ * q_dims = None, d <= 64.
+ * Tables: d_WqT [n_items, 128], the encoder weight transposed: an item's row is 64 mu columns then 64 logvar columns,
+ * each half zero beyond dim; d_bq [128] likewise; d_Wp [n_items, 64] (16-byte aligned) and d_bp [n_items], the decoder.
+ * A user's input is its row of the train CSR (d_rowptr int64 [n_users + 1], d_items int32, ASCENDING inside a row).
+ * Per user u of the batch (n users, n <= SKR_MULTVAE_MAX_BATCH; a user outside [0, n_users) counts as an empty row):
+ *   h = x_u / ||x_u|| * keep / keep_prob,  e = h Wq^T + bq,  mu = e[:dim], logvar = e[64:64 + dim],
+ *   z = mu + eps * exp(logvar / 2),  logits = z Wp^T + bp,
+ *   neg_ll = -mean_u sum_{i in x_u} log_softmax(logits)_ui,  kl = mean_u sum 0.5 (-logvar + exp(logvar) + mu^2 - 1).
+ * ========================================================================================== */
+#define SKR_MULTVAE_MAX_BATCH 1024
+#define SKR_MULTVAE_MAX_WG 512
+/* bytes of d_work for a batch of n users: grows with n * 64 * min(ceil(n_items / 64), SKR_MULTVAE_MAX_WG), never with
+ * n * n_items; 0 for arguments out of range */
+size_t skr_multvae_workspace(int n, int n_items);
+/* One training batch, forward and backward of neg_ll + anneal * kl (the l2 term is the optimiser's weight decay).
+ * d_loss[0] = neg_ll, d_loss[1] = kl are WRITTEN.  The four gradients are ADDED to d_gWqT, d_gbq, d_gWp, d_gbp (layouts
+ * of the tables; the caller's optimiser zeroes them).  Draws: d_keep (one byte per non-zero of the batch's rows, user
+ * after user in batch order, items ascending) and d_eps (float [n, 64]) together, or both NULL: then the step draws on
+ * the device, keyed by (seed, step, user, item) and (seed, step, user, column) -- a user's draws do not depend on the
+ * rest of the batch; equal to the reference's torch draws in law only.  Nothing on the decoder side is a float atomic:
+ * d_gWp, d_gbp, d_loss of two calls on the same inputs are bit-equal; d_gWqT rows are atomic scatter-adds.
+ * d_work: skr_multvae_workspace(n, n_items) bytes, 16-byte aligned, no initial contents, not to be shared by calls that
+ * may run at the same time. */
+int skr_multvae_step(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp, const int64_t* d_rowptr,
+                     const int32_t* d_items, const int32_t* d_users, int n, int n_users, int n_items, int dim, float keep_prob,
+                     float anneal, const uint8_t* d_keep, const float* d_eps, uint64_t seed, uint64_t step, float* d_gWqT,
+                     float* d_gbq, float* d_gWp, float* d_gbp, void* d_work, size_t work_bytes, float* d_loss, void* stream);
+/* The same step with an event after each of its SKR_MULTVAE_LAUNCHES launches (prep, encode, pass 1, merge, pass 2,
+ * reduce, encoder backward, dbq): h_ms[k] (host) = milliseconds of launch k; synchronises the stream (timing tools). */
+#define SKR_MULTVAE_LAUNCHES 8
+int skr_multvae_step_timed(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp,
+                           const int64_t* d_rowptr, const int32_t* d_items, const int32_t* d_users, int n, int n_users,
+                           int n_items, int dim, float keep_prob, float anneal, const uint8_t* d_keep, const float* d_eps,
+                           uint64_t seed, uint64_t step, float* d_gWqT, float* d_gbq, float* d_gWp, float* d_gbp, void* d_work,
+                           size_t work_bytes, float* d_loss, void* stream, float* h_ms);
+/* Query rows: d_Q[u][0..63] = mu of user u = d_users[i] (d_users NULL: u = i) from its whole train row, no dropout, so
+ * that the model's score of item t is <d_Q[u], Wp[t]> + bp[t] (skr_eval_fused_topk, skr_score_matrix).  An empty row
+ * gives bq[0..63] (MultVAE.py:216-220 ranks such a user like any other).  Users out of range are skipped. */
+int skr_multvae_queries(const float* d_WqT, const float* d_bq, const int64_t* d_rowptr, const int32_t* d_items,
+                        const int32_t* d_users, int n, int n_users, int n_items, float* d_Q, void* stream);
+/* The draws skr_multvae_step makes for (seed, step) when it is handed none, in the explicit form: d_off int32 [n + 1]
+ * (offsets of the batch's rows in d_keep), d_keep one byte per non-zero, d_eps float [n, 64] (zero beyond dim). */
+int skr_multvae_draws(const int64_t* d_rowptr, const int32_t* d_items, const int32_t* d_users, int n, int n_users, int dim,
+                      float keep_prob, uint64_t seed, uint64_t step, int32_t* d_off, uint8_t* d_keep, float* d_eps,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,734 @@
+// multvae.hip -- MultVAE (Variational Autoencoders for Collaborative Filtering): one fused training step and the
+// per-user query rows.
+//
+// Replaces the stock torch ops the reference issues per step on a dense [B, I] input (no native code there):
+//   recommender/MultVAE.py:99-114    q_graph: F.normalize, dropout, Linear(I, 2d), split, std, KL
+//   recommender/MultVAE.py:126-136   forward: z = mu + eps * std, logits = Linear(d, I)
+//   recommender/MultVAE.py:187-200   log_softmax over the catalogue, multinomial log-likelihood, backward
+//
+// Layout: the encoder weight transposed, WqT [I, 128] (an item's row: 64 mu columns, 64 logvar columns, each half
+// zero-padded beyond d), the decoder weight Wp [I, 64] as the evaluator ranks it, bq [128], bp [I].  A user's input is
+// its ascending train row of the CSR: the encoder is a gather of 512-byte rows, and no [B, I] array exists anywhere.
+//
+// Launches of a step:
+//   prep      offsets of the batch's rows in the keep flags (one scan)
+//   encode    one wavefront per user: e = scale * sum of the kept WqT rows + bq, the latent (std, z, KL sum), and
+//             sum_{i in x_u} logit_ui as <z_u, sum Wp[i]> + sum bp[i]
+//   pass 1    persistent workgroups over tiles of 64 items: logits tile = z Wp[tile]^T on v_mfma_f32_16x16x4_f32 (exact
+//             fp32 operands), + bp, online (max, sum exp) per user; one partial per workgroup and user
+//   merge     the partials in workgroup order -> lse_u, neg_ll, kl
+//   pass 2    the tile again, G = (n_u exp(logit - lse_u) - x_ui) / B in LDS; three more MFMA products from it:
+//             dz += G Wp[tile] (per workgroup partial), dWp[tile] += G^T z, and the column sums dbp[tile]
+//   reduce    dz partials in workgroup order, then the latent's backward: de [B, 128]
+//   enc bwd   dWqT[i] += h_ui de_u by 512-byte row atomics; dbq by an ordered column sum
+//
+// A wavefront owns 16 users (the 16 rows of the MFMA's A operand, held in registers for all tiles of a user chunk); a
+// workgroup of four owns a chunk of 64 users and walks its tiles for one chunk after the other.  Wp's tile is staged
+// in LDS once per tile and chunk and is the B operand of the logits (read by rows) and of dz (read by columns).
+//
+// Determinism: nothing on the decoder side is a float atomic.  A tile belongs to one workgroup, which adds its chunks'
+// dWp / dbp to the gradient in chunk order; dz, the softmax partials, neg_ll and kl are summed in fixed orders.
+#include "skr_common.h"
+#include "fast_rng.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int D = 64;          // latent columns (narrower models zero-padded)
+constexpr int E2 = 2 * D;      // an encoder row: mu | logvar
+constexpr int TI = 64;         // items of a tile
+constexpr int UC = 64;         // users of a chunk: 16 per wavefront
+constexpr int HW = 4;          // wavefronts per workgroup
+constexpr int LDP = 68;        // LDS row stride: 16-byte rows, and row r, k-group g of an operand read fall on bank 4 r + g
+constexpr int R_WAVES = 16;
+constexpr int MAX_WG = SKR_MULTVAE_MAX_WG;
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+__host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
+
+struct Layout {                // float offsets into the workspace
+    int64_t e, eps, z, de, scale, klu, possum, lse, part, dzpart, off, total;
+};
+
+inline int n_workgroups(int n_items) {
+    const int tiles = (n_items + TI - 1) / TI;
+    return tiles < MAX_WG ? tiles : MAX_WG;
+}
+
+inline Layout layout(int n, int n_wg) {
+    Layout L;
+    const int64_t n4 = round4(n);
+    int64_t o = 0;
+    L.e = o; o += n4 * E2;
+    L.eps = o; o += n4 * D;
+    L.z = o; o += n4 * D;
+    L.de = o; o += n4 * E2;
+    L.scale = o; o += n4;
+    L.klu = o; o += n4;
+    L.possum = o; o += n4;
+    L.lse = o; o += n4;
+    L.part = o; o += static_cast<int64_t>(n_wg) * n4 * 2;
+    L.dzpart = o; o += static_cast<int64_t>(n_wg) * n4 * D;
+    L.off = o; o += round4(n + 1);
+    L.total = o;
+    return L;
+}
+
+// ---- device draws: keyed by (seed, step, user, item) and (seed, step, user, column) -----------------------------
+__device__ __forceinline__ bool keep_draw(uint64_t seed, uint64_t step, int user, int item, float keep_prob) {
+    Xoshiro128pp g;
+    g.seed(seed, step, (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(item));
+    return static_cast<float>(g.next() >> 8) * 0x1p-24f < keep_prob;
+}
+
+__device__ __forceinline__ float normal_draw(uint64_t seed, uint64_t step, int user, int col) {
+    Xoshiro128pp g;
+    g.seed(seed, step, (1ull << 63) | (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(col));
+    const float u1 = static_cast<float>((g.next() >> 8) + 1u) * 0x1p-24f;      // (0, 1]
+    const float u2 = static_cast<float>(g.next() >> 8) * 0x1p-24f;             // [0, 1)
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);            // Box-Muller
+}
+
+// a0 (a1) += the rows of T that `sel(position in the row, item)` picks from the CSR row [beg, end), in ascending
+// order; rows of LD floats, lane j owns column j (WIDE: and 64 + j).  Four rows are requested before the first is added.
+template <int LD, bool WIDE, typename Sel>
+__device__ __forceinline__ void gather_rows(const float* __restrict__ T, const int32_t* __restrict__ items, int64_t beg,
+                                            int64_t end, int n_items, int lane, Sel sel, float& a0, float& a1) {
+    for (int64_t j0 = beg; j0 < end; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const int it = j < end ? items[j] : -1;
+        const bool kp = it >= 0 && it < n_items && sel(static_cast<int>(j - beg), it);
+        uint64_t mask = __builtin_amdgcn_ballot_w64(kp);
+        while (mask != 0) {
+            float r0[4], r1[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                r0[q] = r1[q] = 0.0f;
+                if (mask != 0) {
+                    const int l = __builtin_ctzll(mask);
+                    mask &= mask - 1;
+                    const int64_t i = __shfl(it, l, 64);
+                    r0[q] = T[i * LD + lane];
+                    if (WIDE) r1[q] = T[i * LD + D + lane];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a0 += r0[q];
+                a1 += r1[q];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// prep: off[b] = non-zeros of the batch's rows before user b (the keep flags' order)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void mv_prep_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ users,
+                                                       int n, int n_users, int32_t* __restrict__ off) {
+    __shared__ int s[1024];
+    const int t = threadIdx.x;
+    int len = 0;
+    if (t < n) {
+        const int u = users[t];
+        if (u >= 0 && u < n_users) len = static_cast<int>(rowptr[u + 1] - rowptr[u]);
+    }
+    s[t] = len;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = t >= o ? s[t - o] : 0;
+        __syncthreads();
+        s[t] += v;
+        __syncthreads();
+    }
+    if (t < n) off[t] = s[t] - len;
+    if (t == n - 1) off[n] = s[t];
+}
+
+// ------------------------------------------------------------------------------------------------
+// encode + latent (MultVAE.py:99-114,128-131), and the positives' logit sum
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HW * 64) void mv_encode_kernel(
+    const float* __restrict__ WqT, const float* __restrict__ bq, const float* __restrict__ Wp, const float* __restrict__ bp,
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ items, const int32_t* __restrict__ users, int n,
+    int n_users, int n_items, int d, float keep_prob, const uint8_t* __restrict__ keep, const float* __restrict__ eps_in,
+    uint64_t seed, uint64_t step, const int32_t* __restrict__ off, float* __restrict__ e_out, float* __restrict__ eps_out,
+    float* __restrict__ z_out, float* __restrict__ scale_out, float* __restrict__ klu, float* __restrict__ possum) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x * HW + wv;
+    if (b >= n) return;
+    const int u = users[b];
+    const bool valid = u >= 0 && u < n_users;          // a user out of range counts as an empty row
+    const int64_t beg = valid ? rowptr[u] : 0, end = valid ? rowptr[u + 1] : 0;
+    const int len = static_cast<int>(end - beg);
+    float a0 = 0.0f, a1 = 0.0f;
+    if (keep != nullptr) {
+        const uint8_t* kb = keep + off[b];
+        gather_rows<E2, true>(WqT, items, beg, end, n_items, lane, [&](int p, int) { return kb[p] != 0; }, a0, a1);
+    } else {
+        gather_rows<E2, true>(WqT, items, beg, end, n_items, lane,
+                          [&](int, int it) { return keep_draw(seed, step, u, it, keep_prob); }, a0, a1);
+    }
+    // h = x / ||x|| * keep / keep_prob: one scale for every kept item of the row
+    const float scale = len > 0 ? (1.0f / sqrtf(static_cast<float>(len))) * (1.0f / keep_prob) : 0.0f;
+    const float mu = a0 * scale + bq[lane], lv = a1 * scale + bq[D + lane];
+    const bool live = lane < d;
+    float eps = 0.0f;
+    if (live) eps = eps_in != nullptr ? eps_in[static_cast<int64_t>(b) * D + lane] : normal_draw(seed, step, u, lane);
+    const float sd = expf(0.5f * lv);
+    const float z = live ? mu + eps * sd : 0.0f;
+    const float klt = live ? 0.5f * (((-lv + expf(lv)) + mu * mu) - 1.0f) : 0.0f;
+    const float kls = skr::wave_sum(klt);
+    e_out[static_cast<int64_t>(b) * E2 + lane] = mu;
+    e_out[static_cast<int64_t>(b) * E2 + D + lane] = lv;
+    eps_out[static_cast<int64_t>(b) * D + lane] = eps;
+    z_out[static_cast<int64_t>(b) * D + lane] = z;
+    // sum over the row's items (kept or not) of <z, Wp[i]> + bp[i]
+    float w0 = 0.0f, w1 = 0.0f, bs = 0.0f;
+    gather_rows<D, false>(Wp, items, beg, end, n_items, lane, [&](int, int) { return true; }, w0, w1);
+    for (int64_t j = beg + lane; j < end; j += 64) {
+        const int it = items[j];
+        if (it >= 0 && it < n_items) bs += bp[it];
+    }
+    const float ps = skr::wave_sum(z * w0) + skr::wave_sum(bs);
+    if (lane == 0) {
+        scale_out[b] = scale;
+        klu[b] = kls;
+        possum[b] = ps;
+    }
+}
+
+// query rows: Q[u] = mu of the whole row, no dropout (MultVAE.py:131 with training = 0)
+__global__ __launch_bounds__(HW * 64) void mv_queries_kernel(const float* __restrict__ WqT, const float* __restrict__ bq,
+                                                             const int64_t* __restrict__ rowptr,
+                                                             const int32_t* __restrict__ items,
+                                                             const int32_t* __restrict__ users, int n, int n_users,
+                                                             int n_items, float* __restrict__ Q) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int b = blockIdx.x * HW + wv; b < n; b += gridDim.x * HW) {
+        const int64_t u = users ? users[b] : b;
+        if (u < 0 || u >= n_users) continue;
+        const int64_t beg = rowptr[u], end = rowptr[u + 1];
+        float a0 = 0.0f, a1 = 0.0f;
+        gather_rows<E2, false>(WqT, items, beg, end, n_items, lane, [&](int, int) { return true; }, a0, a1);
+        const float scale = end > beg ? 1.0f / sqrtf(static_cast<float>(end - beg)) : 0.0f;
+        Q[u * D + lane] = a0 * scale + bq[lane];           // an empty row: bq
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// decoder tiles
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void tile_range(int tiles, int& t0, int& t1) {
+    t0 = static_cast<int>(static_cast<int64_t>(blockIdx.x) * tiles / gridDim.x);
+    t1 = static_cast<int>(static_cast<int64_t>(blockIdx.x + 1) * tiles / gridDim.x);
+}
+
+// Wp[item0 .. item0 + 64) into LDS, rows beyond the catalogue as zeros
+__device__ __forceinline__ void load_tile(float* __restrict__ sW, const float* __restrict__ Wp, int item0, int n_items) {
+    const float4* W4 = reinterpret_cast<const float4*>(Wp);
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
+        const int item = item0 + row;
+        v[i] = item < n_items ? W4[static_cast<int64_t>(item) * 16 + c4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
+        *reinterpret_cast<float4*>(sW + row * LDP + c4 * 4) = v[i];
+    }
+}
+
+// the wavefront's z rows as the A operand of 16 k-steps: lane (r, g) holds z[user r][4 kk + g]
+__device__ __forceinline__ void load_a(float a[16], const float* __restrict__ z, int ub, int n, int r, int g) {
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) a[kk] = ub + r < n ? z[static_cast<int64_t>(ub + r) * D + 4 * kk + g] : 0.0f;
+}
+
+// acc[nb][rr] = <z[user 4 g + rr], Wp[item 16 nb + r]>
+__device__ __forceinline__ void logits_tile(f32x4 acc[4], const float a[16], const float* __restrict__ sW, int r, int g) {
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], sW[(nb * 16 + r) * LDP + 4 * kk + g], acc[nb], 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ float max16(float v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float sum16(float v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// pass 1: part[wg][user] = (max, sum exp(logit - max)) over the workgroup's tiles
+__global__ __launch_bounds__(HW * 64) void mv_pass1_kernel(const float* __restrict__ Wp, const float* __restrict__ bp,
+                                                           const float* __restrict__ z, int n, int n4, int n_items,
+                                                           int tiles, float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float sW[TI * LDP];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    int t0, t1;
+    tile_range(tiles, t0, t1);
+    for (int u0 = 0; u0 < n; u0 += UC) {
+        const int ub = u0 + wv * 16;
+        float a[16];
+        load_a(a, z, ub, n, r, g);
+        float m[4], s[4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) { m[rr] = -INFINITY; s[rr] = 0.0f; }
+        for (int t = t0; t < t1; ++t) {
+            __syncthreads();
+            load_tile(sW, Wp, t * TI, n_items);
+            __syncthreads();
+            float bpv[4];
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) {
+                const int item = t * TI + nb * 16 + r;
+                bpv[nb] = item < n_items ? bp[item] : -INFINITY;      // items beyond the catalogue: exp(-inf) = 0
+            }
+            f32x4 acc[4];
+            logits_tile(acc, a, sW, r, g);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                float v[4];
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb) v[nb] = acc[nb][rr] + bpv[nb];
+                const float tm = max16(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));    // finite: a tile has an item
+                const float mn = fmaxf(m[rr], tm);
+                const float ts = sum16((expf(v[0] - mn) + expf(v[1] - mn)) + (expf(v[2] - mn) + expf(v[3] - mn)));
+                s[rr] = s[rr] * expf(m[rr] - mn) + ts;
+                m[rr] = mn;
+            }
+        }
+        if (r == 0) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int user = ub + 4 * g + rr;
+                if (user < n) {
+                    float* p = part + (static_cast<int64_t>(blockIdx.x) * n4 + user) * 2;
+                    p[0] = m[rr];
+                    p[1] = s[rr];
+                }
+            }
+        }
+    }
+}
+
+// merge: lse_u from the partials in workgroup order; neg_ll and kl by a fixed tree over the users
+__global__ __launch_bounds__(1024) void mv_merge_kernel(const float* __restrict__ part, int n_wg, int n, int n4,
+                                                        const int64_t* __restrict__ rowptr, const int32_t* __restrict__ users,
+                                                        int n_users, const float* __restrict__ possum,
+                                                        const float* __restrict__ klu, float* __restrict__ lse,
+                                                        float* __restrict__ loss) {
+    __shared__ float s_nll[1024], s_kl[1024];
+    const int b = threadIdx.x;
+    float nll = 0.0f, kl = 0.0f;
+    if (b < n) {
+        float M = -INFINITY;
+        for (int w = 0; w < n_wg; ++w) M = fmaxf(M, part[(static_cast<int64_t>(w) * n4 + b) * 2]);
+        float S = 0.0f;
+        for (int w = 0; w < n_wg; ++w) {
+            const float* p = part + (static_cast<int64_t>(w) * n4 + b) * 2;
+            S += p[1] * expf(p[0] - M);
+        }
+        const float l = M + logf(S);
+        lse[b] = l;
+        const int u = users[b];
+        const float len = (u >= 0 && u < n_users) ? static_cast<float>(rowptr[u + 1] - rowptr[u]) : 0.0f;
+        nll = len * l - possum[b];
+        kl = klu[b];
+    }
+    s_nll[b] = nll;
+    s_kl[b] = kl;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (b < o) {
+            s_nll[b] += s_nll[b + o];
+            s_kl[b] += s_kl[b + o];
+        }
+        __syncthreads();
+    }
+    if (b == 0) {
+        loss[0] = s_nll[0] / static_cast<float>(n);
+        loss[1] = s_kl[0] / static_cast<float>(n);
+    }
+}
+
+__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int v) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// pass 2: G in LDS, then dz partial, dWp[tile], dbp[tile]
+__global__ __launch_bounds__(HW * 64) void mv_pass2_kernel(
+    const float* __restrict__ Wp, const float* __restrict__ bp, const float* __restrict__ z, const float* __restrict__ lse,
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ items, const int32_t* __restrict__ users, int n, int n4,
+    int n_users, int n_items, int tiles, float* __restrict__ gWp, float* __restrict__ gbp, float* __restrict__ dzpart) {
+    __shared__ __attribute__((aligned(16))) float sW[TI * LDP];
+    __shared__ float sG[UC * LDP];
+    __shared__ float sZ[UC * LDP];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const float invB = 1.0f / static_cast<float>(n);
+    int t0, t1;
+    tile_range(tiles, t0, t1);
+    for (int u0 = 0; u0 < n; u0 += UC) {
+        const int ub = u0 + wv * 16;
+        __syncthreads();                                   // the previous chunk's last tile still reads sZ
+        for (int idx = threadIdx.x; idx < UC * D; idx += HW * 64) {
+            const int row = idx >> 6, c = idx & 63;
+            sZ[row * LDP + c] = u0 + row < n ? z[static_cast<int64_t>(u0 + row) * D + c] : 0.0f;
+        }
+        float a[16];
+        load_a(a, z, ub, n, r, g);
+        // lanes 0..15: the CSR cursor of user ub + lane, at the first item of the workgroup's first tile
+        int64_t cur = 0, rend = 0;
+        float nsc[4], lsev[4];
+        {
+            const int user = ub + r;
+            if (user < n) {
+                const int u = users[user];
+                if (u >= 0 && u < n_users) {
+                    rend = rowptr[u + 1];
+                    cur = lower_bound(items, rowptr[u], rend, t0 * TI);
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int us = ub + 4 * g + rr;
+                nsc[rr] = 0.0f;
+                lsev[rr] = INFINITY;                      // rows beyond the batch: exp(-inf) = 0
+                if (us < n) {
+                    const int u = users[us];
+                    const float len = (u >= 0 && u < n_users) ? static_cast<float>(rowptr[u + 1] - rowptr[u]) : 0.0f;
+                    nsc[rr] = len * invB;
+                    lsev[rr] = lse[us];
+                }
+            }
+        }
+        f32x4 dz[4];
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) dz[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = t0; t < t1; ++t) {
+            const int item0 = t * TI;
+            __syncthreads();                               // the previous tile's products still read sW and sG
+            load_tile(sW, Wp, item0, n_items);
+            // this tile's entries of the 16 rows: requested before the products, used after them
+            int its[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int64_t cq = __shfl(cur, q, 64), eq = __shfl(rend, q, 64);
+                const int64_t j = cq + lane;
+                its[q] = j < eq ? items[j] : 0x7fffffff;
+            }
+            __syncthreads();
+            float bpv[4];
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) {
+                const int item = item0 + nb * 16 + r;
+                bpv[nb] = item < n_items ? bp[item] : 0.0f;
+            }
+            f32x4 acc[4];
+            logits_tile(acc, a, sW, r, g);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) {
+                const bool in = item0 + nb * 16 + r < n_items;
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const float p = in ? nsc[rr] * expf((acc[nb][rr] + bpv[nb]) - lsev[rr]) : 0.0f;
+                    sG[(wv * 16 + 4 * g + rr) * LDP + nb * 16 + r] = p;
+                }
+            }
+            __syncthreads();
+            // - x_ui / B at the row's items of this tile (ascending and distinct: at most one per lane)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const bool hit = its[q] >= item0 && its[q] < item0 + TI && its[q] < n_items;
+                if (hit) sG[(wv * 16 + q) * LDP + (its[q] - item0)] -= invB;
+                const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(its[q] < item0 + TI));
+                if (lane == q) cur += cnt;
+            }
+            __syncthreads();
+            // dz[user][col] += sum_item G[user][item] Wp[item][col]: the wavefront's own 16 rows of G
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) {
+                const float ga = sG[(wv * 16 + r) * LDP + 4 * kk + g];
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb)
+                    dz[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga, sW[(4 * kk + g) * LDP + nb * 16 + r], dz[nb], 0, 0, 0);
+            }
+            // dWp[item][col] = sum_user G[user][item] z[user][col] over the chunk: the wavefront's 16 items
+            f32x4 dw[4];
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) dw[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) {
+                const float gt = sG[(4 * kk + g) * LDP + wv * 16 + r];
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb)
+                    dw[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(gt, sZ[(4 * kk + g) * LDP + nb * 16 + r], dw[nb], 0, 0, 0);
+            }
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int item = item0 + wv * 16 + 4 * g + rr;
+                if (item < n_items) {
+#pragma unroll
+                    for (int nb = 0; nb < 4; ++nb) gWp[static_cast<int64_t>(item) * D + nb * 16 + r] += dw[nb][rr];
+                }
+            }
+            // dbp[item] = sum_user G[user][item]: lane (r, g) the users 16 g .. 16 g + 15, then the four g in order
+            float cs = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) cs += sG[(16 * g + k) * LDP + wv * 16 + r];
+            cs += __shfl_xor(cs, 16, 64);
+            cs += __shfl_xor(cs, 32, 64);
+            if (g == 0 && item0 + wv * 16 + r < n_items) gbp[item0 + wv * 16 + r] += cs;
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int user = ub + 4 * g + rr;
+            if (user < n) {
+                float* p = dzpart + (static_cast<int64_t>(blockIdx.x) * n4 + user) * D;
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb) p[nb * 16 + r] = dz[nb][rr];
+            }
+        }
+    }
+}
+
+// dz = the workgroups' partials in a fixed order (as hgn_reduce_kernel), then the latent's backward:
+//   z = mu + eps exp(logvar / 2), loss = neg_ll + anneal kl  ->  de = (dmu | dlogvar), zero beyond d
+__global__ __launch_bounds__(R_WAVES * 64) void mv_reduce_kernel(const float* __restrict__ dzpart, int n_wg, int n4, int d,
+                                                                 float anneal, float invB, const float* __restrict__ e,
+                                                                 const float* __restrict__ eps, float* __restrict__ de) {
+    __shared__ float s_part[R_WAVES][D];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x;
+    float s = 0.0f;
+    int w = wv;
+    for (; w + 3 * R_WAVES < n_wg; w += 4 * R_WAVES) {
+        const float a0 = dzpart[(static_cast<int64_t>(w) * n4 + b) * D + lane];
+        const float a1 = dzpart[(static_cast<int64_t>(w + R_WAVES) * n4 + b) * D + lane];
+        const float a2 = dzpart[(static_cast<int64_t>(w + 2 * R_WAVES) * n4 + b) * D + lane];
+        const float a3 = dzpart[(static_cast<int64_t>(w + 3 * R_WAVES) * n4 + b) * D + lane];
+        s += a0; s += a1; s += a2; s += a3;
+    }
+    for (; w < n_wg; w += R_WAVES) s += dzpart[(static_cast<int64_t>(w) * n4 + b) * D + lane];
+    s_part[wv][lane] = s;
+    __syncthreads();
+    if (wv != 0) return;
+    float dzv = 0.0f;
+    for (int k = 0; k < R_WAVES; ++k) dzv += s_part[k][lane];
+    const float mu = e[b * E2 + lane], lv = e[b * E2 + D + lane], ep = eps[b * D + lane];
+    const bool live = lane < d;
+    const float dmu = dzv + (anneal * invB) * mu;
+    const float dlv = (dzv * ep) * (0.5f * expf(0.5f * lv)) + (anneal * invB) * (0.5f * (expf(lv) - 1.0f));
+    de[b * E2 + lane] = live ? dmu : 0.0f;
+    de[b * E2 + D + lane] = live ? dlv : 0.0f;
+}
+
+// encoder backward: dWqT[i] += h_ui de_u for the kept non-zeros (row atomics); one wavefront per user
+__global__ __launch_bounds__(HW * 64) void mv_encbwd_kernel(const float* __restrict__ de, const float* __restrict__ scale,
+                                                            const int64_t* __restrict__ rowptr,
+                                                            const int32_t* __restrict__ items,
+                                                            const int32_t* __restrict__ users, int n, int n_users,
+                                                            int n_items, float keep_prob, const uint8_t* __restrict__ keep,
+                                                            uint64_t seed, uint64_t step, const int32_t* __restrict__ off,
+                                                            float* __restrict__ gWqT) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x * HW + wv;
+    if (b >= n) return;
+    const int u = users[b];
+    if (u < 0 || u >= n_users) return;
+    const int64_t beg = rowptr[u], end = rowptr[u + 1];
+    const float sc = scale[b];
+    const float g0 = sc * de[static_cast<int64_t>(b) * E2 + lane], g1 = sc * de[static_cast<int64_t>(b) * E2 + D + lane];
+    const uint8_t* kb = keep != nullptr ? keep + off[b] : nullptr;
+    for (int64_t j0 = beg; j0 < end; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const int it = j < end ? items[j] : -1;
+        bool kp = it >= 0 && it < n_items;
+        if (kp) kp = kb != nullptr ? kb[j - beg] != 0 : keep_draw(seed, step, u, it, keep_prob);
+        uint64_t mask = __builtin_amdgcn_ballot_w64(kp);
+        while (mask != 0) {
+            const int l = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int64_t i = __shfl(it, l, 64);
+            atomicAdd(&gWqT[i * E2 + lane], g0);
+            atomicAdd(&gWqT[i * E2 + D + lane], g1);
+        }
+    }
+}
+
+// dbq += the column sums of de, in a fixed order: eight strided parts, then the parts in order
+__global__ __launch_bounds__(1024) void mv_dbq_kernel(const float* __restrict__ de, int n, float* __restrict__ gbq) {
+    __shared__ float s[8][E2];
+    const int c = threadIdx.x & (E2 - 1), p = threadIdx.x >> 7;
+    float a = 0.0f;
+    for (int b = p; b < n; b += 8) a += de[static_cast<int64_t>(b) * E2 + c];
+    s[p][c] = a;
+    __syncthreads();
+    if (p != 0) return;
+    float t = 0.0f;
+    for (int k = 0; k < 8; ++k) t += s[k][c];
+    gbq[c] += t;
+}
+
+// the draws of a step in the explicit form: keep[off[b] + p] for the p-th non-zero of user b's row, eps [n, 64]
+__global__ __launch_bounds__(HW * 64) void mv_draws_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ items,
+                                                           const int32_t* __restrict__ users, int n, int n_users, int d,
+                                                           float keep_prob, uint64_t seed, uint64_t step,
+                                                           const int32_t* __restrict__ off, uint8_t* __restrict__ keep,
+                                                           float* __restrict__ eps) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x * HW + wv;
+    if (b >= n) return;
+    const int u = users[b];
+    eps[static_cast<int64_t>(b) * D + lane] = lane < d ? normal_draw(seed, step, u, lane) : 0.0f;
+    if (u < 0 || u >= n_users) return;
+    const int64_t beg = rowptr[u], end = rowptr[u + 1];
+    for (int64_t j = beg + lane; j < end; j += 64) keep[off[b] + (j - beg)] = keep_draw(seed, step, u, items[j], keep_prob) ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t skr_multvae_workspace(int n, int n_items) {
+    if (n <= 0 || n > SKR_MULTVAE_MAX_BATCH || n_items <= 0) return 0;
+    return static_cast<size_t>(layout(n, n_workgroups(n_items)).total) * sizeof(float);
+}
+
+static int run_step(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp, const int64_t* d_rowptr,
+                     const int32_t* d_items, const int32_t* d_users, int n, int n_users, int n_items, int dim, float keep_prob,
+                     float anneal, const uint8_t* d_keep, const float* d_eps, uint64_t seed, uint64_t step, float* d_gWqT,
+                     float* d_gbq, float* d_gWp, float* d_gbp, void* d_work, size_t work_bytes, float* d_loss, void* stream,
+                    float* h_ms) {
+    SKR_REQUIRE(d_WqT && d_bq && d_Wp && d_bp && d_rowptr && d_items && d_users && d_gWqT && d_gbq && d_gWp && d_gbp && d_work &&
+                    d_loss,
+                "skr_multvae_step: NULL argument");
+    SKR_REQUIRE(n >= 0 && n <= SKR_MULTVAE_MAX_BATCH && n_users > 0 && n_items > 0,
+                "skr_multvae_step: n = %d (at most %d), n_users = %d, n_items = %d", n, SKR_MULTVAE_MAX_BATCH, n_users, n_items);
+    SKR_REQUIRE(dim >= 1 && dim <= D, "skr_multvae_step: 1 <= dim <= 64 (got %d); rows are 64 floats, zero-padded", dim);
+    SKR_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "skr_multvae_step: keep_prob = %g is not in (0, 1]", keep_prob);
+    SKR_REQUIRE((d_keep == nullptr) == (d_eps == nullptr), "skr_multvae_step: d_keep and d_eps come together or not at all");
+    if (n == 0) return SKR_OK;
+    const int n_wg = n_workgroups(n_items), tiles = (n_items + TI - 1) / TI, n4 = round4(n);
+    const Layout L = layout(n, n_wg);
+    SKR_REQUIRE(work_bytes >= static_cast<size_t>(L.total) * sizeof(float),
+                "skr_multvae_step: d_work holds %zu bytes, skr_multvae_workspace(%d, %d) asks for %zu", work_bytes, n, n_items,
+                static_cast<size_t>(L.total) * sizeof(float));
+    SKR_REQUIRE((reinterpret_cast<uintptr_t>(d_Wp) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0,
+                "skr_multvae_step: d_Wp and d_work must be 16-byte aligned");
+    float* w = static_cast<float*>(d_work);
+    int32_t* off = reinterpret_cast<int32_t*>(w + L.off);
+    hipStream_t st = skr::as_stream(stream);
+    const float invB = 1.0f / static_cast<float>(n);
+    const int ub = (n + HW - 1) / HW;
+    // h_ms: an event after every launch (the profiling entry); otherwise nothing but the eight launches
+    hipEvent_t ev[SKR_MULTVAE_LAUNCHES + 1] = {};
+    int n_ev = 0;
+    auto mark = [&]() -> hipError_t {
+        if (h_ms == nullptr) return hipSuccess;
+        hipError_t e = hipEventCreate(&ev[n_ev]);
+        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
+        return e;
+    };
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_prep_kernel, dim3(1), dim3(1024), 0, st, d_rowptr, d_users, n, n_users, off);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_encode_kernel, dim3(ub), dim3(HW * 64), 0, st, d_WqT, d_bq, d_Wp, d_bp, d_rowptr, d_items, d_users, n,
+                       n_users, n_items, dim, keep_prob, d_keep, d_eps, seed, step, off, w + L.e, w + L.eps, w + L.z,
+                       w + L.scale, w + L.klu, w + L.possum);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_pass1_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_Wp, d_bp, w + L.z, n, n4, n_items, tiles,
+                       w + L.part);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_merge_kernel, dim3(1), dim3(1024), 0, st, w + L.part, n_wg, n, n4, d_rowptr, d_users, n_users,
+                       w + L.possum, w + L.klu, w + L.lse, d_loss);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_pass2_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_Wp, d_bp, w + L.z, w + L.lse, d_rowptr, d_items,
+                       d_users, n, n4, n_users, n_items, tiles, d_gWp, d_gbp, w + L.dzpart);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_reduce_kernel, dim3(n), dim3(R_WAVES * 64), 0, st, w + L.dzpart, n_wg, n4, dim, anneal, invB, w + L.e,
+                       w + L.eps, w + L.de);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_encbwd_kernel, dim3(ub), dim3(HW * 64), 0, st, w + L.de, w + L.scale, d_rowptr, d_items, d_users, n,
+                       n_users, n_items, keep_prob, d_keep, seed, step, off, d_gWqT);
+    SKR_HIP(mark());
+    hipLaunchKernelGGL(mv_dbq_kernel, dim3(1), dim3(1024), 0, st, w + L.de, n, d_gbq);
+    SKR_HIP(mark());
+    SKR_LAUNCH_CHECK();
+    if (h_ms != nullptr) {
+        SKR_HIP(hipEventSynchronize(ev[n_ev - 1]));
+        for (int k = 0; k + 1 < n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], ev[k], ev[k + 1]));
+        for (int k = 0; k < n_ev; ++k) SKR_HIP(hipEventDestroy(ev[k]));
+    }
+    return SKR_OK;
+}
+
+int skr_multvae_step(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp, const int64_t* d_rowptr,
+                     const int32_t* d_items, const int32_t* d_users, int n, int n_users, int n_items, int dim, float keep_prob,
+                     float anneal, const uint8_t* d_keep, const float* d_eps, uint64_t seed, uint64_t step, float* d_gWqT,
+                     float* d_gbq, float* d_gWp, float* d_gbp, void* d_work, size_t work_bytes, float* d_loss, void* stream) {
+    return run_step(d_WqT, d_bq, d_Wp, d_bp, d_rowptr, d_items, d_users, n, n_users, n_items, dim, keep_prob, anneal, d_keep,
+                    d_eps, seed, step, d_gWqT, d_gbq, d_gWp, d_gbp, d_work, work_bytes, d_loss, stream, nullptr);
+}
+
+int skr_multvae_step_timed(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp,
+                           const int64_t* d_rowptr, const int32_t* d_items, const int32_t* d_users, int n, int n_users,
+                           int n_items, int dim, float keep_prob, float anneal, const uint8_t* d_keep, const float* d_eps,
+                           uint64_t seed, uint64_t step, float* d_gWqT, float* d_gbq, float* d_gWp, float* d_gbp, void* d_work,
+                           size_t work_bytes, float* d_loss, void* stream, float* h_ms) {
+    SKR_REQUIRE(h_ms != nullptr, "skr_multvae_step_timed: NULL argument");
+    return run_step(d_WqT, d_bq, d_Wp, d_bp, d_rowptr, d_items, d_users, n, n_users, n_items, dim, keep_prob, anneal, d_keep,
+                    d_eps, seed, step, d_gWqT, d_gbq, d_gWp, d_gbp, d_work, work_bytes, d_loss, stream, h_ms);
+}
+
+int skr_multvae_queries(const float* d_WqT, const float* d_bq, const int64_t* d_rowptr, const int32_t* d_items,
+                        const int32_t* d_users, int n, int n_users, int n_items, float* d_Q, void* stream) {
+    SKR_REQUIRE(d_WqT && d_bq && d_rowptr && d_items && d_Q, "skr_multvae_queries: NULL argument");
+    SKR_REQUIRE(n >= 0 && n_users > 0 && n_items > 0, "skr_multvae_queries: n = %d, n_users = %d, n_items = %d", n, n_users,
+                n_items);
+    SKR_REQUIRE(d_users || n <= n_users, "skr_multvae_queries: without a user list n = %d must not exceed n_users = %d", n,
+                n_users);
+    if (n == 0) return SKR_OK;
+    int blocks = (n + HW - 1) / HW;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(mv_queries_kernel, dim3(blocks), dim3(HW * 64), 0, skr::as_stream(stream), d_WqT, d_bq, d_rowptr, d_items,
+                       d_users, n, n_users, n_items, d_Q);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+int skr_multvae_draws(const int64_t* d_rowptr, const int32_t* d_items, const int32_t* d_users, int n, int n_users, int dim,
+                      float keep_prob, uint64_t seed, uint64_t step, int32_t* d_off, uint8_t* d_keep, float* d_eps,
+                      void* stream) {
+    SKR_REQUIRE(d_rowptr && d_items && d_users && d_off && d_keep && d_eps, "skr_multvae_draws: NULL argument");
+    SKR_REQUIRE(n >= 0 && n <= SKR_MULTVAE_MAX_BATCH && n_users > 0, "skr_multvae_draws: n = %d (at most %d), n_users = %d", n,
+                SKR_MULTVAE_MAX_BATCH, n_users);
+    SKR_REQUIRE(dim >= 1 && dim <= D, "skr_multvae_draws: 1 <= dim <= 64 (got %d)", dim);
+    SKR_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "skr_multvae_draws: keep_prob = %g is not in (0, 1]", keep_prob);
+    if (n == 0) return SKR_OK;
+    hipStream_t st = skr::as_stream(stream);
+    hipLaunchKernelGGL(mv_prep_kernel, dim3(1), dim3(1024), 0, st, d_rowptr, d_users, n, n_users, d_off);
+    hipLaunchKernelGGL(mv_draws_kernel, dim3((n + HW - 1) / HW), dim3(HW * 64), 0, st, d_rowptr, d_items, d_users, n, n_users,
+                       dim, keep_prob, seed, step, d_off, d_keep, d_eps);
+    SKR_LAUNCH_CHECK();
+    return SKR_OK;
+}
+
+}  // extern "C"

@@ -17,6 +17,8 @@
 #include "skr_common.h"
 #include "mt_jump.h"
 
+#include "fast_rng.h"
+
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -1048,36 +1050,7 @@ constexpr int FS_SLOTS = FS_T * FS_PER;  // slots per workgroup
 constexpr int FS_POS_CAP = 6144;         // positives staged in LDS (24 KB)
 constexpr int FS_ROW_CAP = 2048;         // row offsets staged in LDS (8 KB)
 
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t& x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
-
-struct Xoshiro128pp {
-    uint32_t s0, s1, s2, s3;
-    __host__ __device__ void seed(uint64_t seed, uint64_t epoch, uint64_t slot) {
-        uint64_t x = seed;
-        uint64_t k = splitmix64(x) ^ (epoch * 0xD1B54A32D192ED03ull);
-        x = k;
-        k = splitmix64(x) ^ slot;
-        x = k;
-        const uint64_t a = splitmix64(x), b = splitmix64(x);
-        s0 = static_cast<uint32_t>(a); s1 = static_cast<uint32_t>(a >> 32);
-        s2 = static_cast<uint32_t>(b); s3 = static_cast<uint32_t>(b >> 32);
-        if ((s0 | s1 | s2 | s3) == 0) s0 = 1;
-    }
-    __host__ __device__ uint32_t next() {
-        const uint32_t r = rotl32(s0 + s3, 7) + s0;
-        const uint32_t t = s1 << 9;
-        s2 ^= s0; s3 ^= s1; s1 ^= s2; s0 ^= s3; s2 ^= t;
-        s3 = rotl32(s3, 11);
-        return r;
-    }
-};
+// splitmix64 and Xoshiro128pp: fast_rng.h (shared with multvae.hip)
 
 __global__ __launch_bounds__(FS_T) void sample_fast_kernel(uint64_t seed, uint64_t epoch, int64_t slot_offset,
                                                            uint32_t high, int n_users,

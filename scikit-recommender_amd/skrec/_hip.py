@@ -116,6 +116,13 @@ SIGNATURES = {
     "skr_hgn_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32,
                            vp]),
     "skr_hgn_queries": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "skr_multvae_workspace": (sz, [i32, i32]),
+    "skr_multvae_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, u64, u64, vp, vp, vp, vp, vp, sz,
+                               vp, vp]),
+    "skr_multvae_step_timed": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, u64, u64, vp, vp, vp, vp, vp,
+                                     sz, vp, vp, vp]),
+    "skr_multvae_queries": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "skr_multvae_draws": (i32, [vp, vp, vp, i32, i32, i32, f32, u64, u64, vp, vp, vp, vp]),
 }
 
 class SpmmEpilogue(C.Structure):
@@ -132,6 +139,7 @@ SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
 SKR_TRANSREC_MAX_BLOCKS = 1024   # skr_transrec_step: d_work holds this many rows of dim floats
 SKR_SEQ_FPMC, SKR_SEQ_TRANSREC = 0, 1     # skr_seq_scores modes
 SKR_HGN_MAX_L, SKR_HGN_MAX_T, SKR_HGN_MAX_BLOCKS = 32, 16, 256   # skr_hgn_step limits; d_work holds MAX_BLOCKS partials
+SKR_MULTVAE_MAX_BATCH = 1024   # skr_multvae_step: users of a batch
 
 
 def hgn_gate_floats(L):
