@@ -802,6 +802,59 @@ int skr_multvae_draws(const int64_t* d_rowptr, const int32_t* d_items, const int
                       float keep_prob, uint64_t seed, uint64_t step, int32_t* d_off, uint8_t* d_keep, float* d_eps,
                       void* stream);
 
+/* ============================================================================================
+ * S -- CDAE, collaborative denoising autoencoder (csrc/cdae.hip)
+ * replaces: _CDAE.forward / _encoding / predict and CDAE.fit's step (recommender/CDAE.py:95-130,168-206) for
+ * hidden_dim <= 64 and the sigmoid cross entropy loss.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned: d_E_en, d_E_de [n_items, 64], d_offset [64], d_U [n_users, 64];
+ * d_bias [n_items].
+ * A batch of n DISTINCT users (n <= SKR_CDAE_MAX_BATCH) is a pair list: user b = d_users[b] owns the pairs
+ * [d_uptr[b], d_uptr[b + 1]) of d_pitem / d_plabel / d_pkeep -- its positives (label 1) and its de-duplicated negatives
+ * (label 0), items ASCENDING, d_pkeep the dropout keep flag of the encoder input.  d_uptr[0] is the batch's first pair:
+ * the three pair arrays and d_puser may belong to a longer list (a block of batches prepared at once) and are indexed by
+ * the values of d_uptr as they are; n_pairs = d_uptr[n] - d_uptr[0].  d_puser[p] is the batch position of pair p.
+ * The item-major view: distinct item d_ditems[j] (j < n_distinct) owns d_ipair[d_iptr[j] .. d_iptr[j + 1]), pair numbers
+ * RELATIVE to d_uptr[0]; every pair is listed once.  Entries out of range are skipped, never followed.
+ *   h_u = act(sum_{kept i} E_en[i] / keep_prob + U[u] + offset),   r = <h_u, E_de[i]> + bias[i] for every pair,
+ *   loss = sum_pairs bce_with_logits(r, label) + reg * l2,
+ *   l2 = 0.5 (|E_en[J]|^2 + |offset|^2 + |U[users]|^2 + |E_de[J]|^2 + |bias[J]|^2), J the distinct items.
+ * ========================================================================================== */
+#define SKR_CDAE_MAX_BATCH 1024
+#define SKR_CDAE_IDENTITY 0
+#define SKR_CDAE_SIGMOID 1
+/* bytes of d_work for n users and n_pairs pairs; 0 for arguments out of range */
+size_t skr_cdae_workspace(int n, int64_t n_pairs);
+/* One training batch, forward and backward.  d_loss[0] = the BCE sum, d_loss[1] = l2 (without reg) are WRITTEN.  The
+ * gradient of the whole loss is WRITTEN into the rows the batch names -- d_gU[users], d_gE_en[J], d_gE_de[J], d_gbias[J]
+ * and d_goffset [64] (layouts of the tables) -- and nothing else is touched: the caller's optimiser leaves the other
+ * rows at zero.  No floating-point atomic: two calls on the same inputs give bit-equal results.
+ * d_work: skr_cdae_workspace(n, n_pairs) bytes, 16-byte aligned, no initial contents. */
+int skr_cdae_step(const float* d_E_en, const float* d_E_de, const float* d_bias, const float* d_offset, const float* d_U,
+                  const int32_t* d_users, const int32_t* d_uptr, const int32_t* d_pitem, const uint8_t* d_plabel,
+                  const uint8_t* d_pkeep, const int32_t* d_puser, const int32_t* d_ditems, const int32_t* d_iptr,
+                  const int32_t* d_ipair, int n, int64_t n_pairs, int n_distinct, int n_users, int n_items, int dim, int act,
+                  float keep_prob, float reg, float* d_gE_en, float* d_gE_de, float* d_gbias, float* d_goffset, float* d_gU,
+                  void* d_work, size_t work_bytes, float* d_loss, void* stream);
+/* The same step with an event after each of its SKR_CDAE_LAUNCHES launches (user side, item side, finish): h_ms[k]
+ * (host) = milliseconds of launch k; synchronises the stream (timing tools). */
+#define SKR_CDAE_LAUNCHES 3
+int skr_cdae_step_timed(const float* d_E_en, const float* d_E_de, const float* d_bias, const float* d_offset, const float* d_U,
+                        const int32_t* d_users, const int32_t* d_uptr, const int32_t* d_pitem, const uint8_t* d_plabel,
+                        const uint8_t* d_pkeep, const int32_t* d_puser, const int32_t* d_ditems, const int32_t* d_iptr,
+                        const int32_t* d_ipair, int n, int64_t n_pairs, int n_distinct, int n_users, int n_items, int dim, int act,
+                        float keep_prob, float reg, float* d_gE_en, float* d_gE_de, float* d_gbias, float* d_goffset, float* d_gU,
+                        void* d_work, size_t work_bytes, float* d_loss, void* stream, float* h_ms);
+/* Query rows: d_Q[u][0..63] = act(sum E_en[train(u)] + U[u] + offset) of user u = d_users[i] (d_users NULL: u = i) from
+ * its train row (d_rowptr int64 [n_users + 1], d_items int32), no negatives, no dropout, zero beyond dim: the model's
+ * score of item t is <d_Q[u], E_de[t]> + bias[t].  An empty row gives act(U[u] + offset).  Users out of range are skipped. */
+int skr_cdae_queries(const float* d_E_en, const float* d_offset, const float* d_U, const int64_t* d_rowptr, const int32_t* d_items,
+                     const int32_t* d_users, int n, int n_users, int n_items, int dim, int act, float* d_Q, void* stream);
+/* Keep flags drawn on the device: d_pkeep[p] for pair p of batch position d_puser[p] is keyed by (seed, step + d_pstep[p],
+ * user, item) (d_pstep NULL: step) -- a user's flags do not depend on the rest of the batch; equal to the reference's
+ * torch draws in law only. */
+int skr_cdae_draws(const int32_t* d_users, const int32_t* d_puser, const int32_t* d_pitem, const int32_t* d_pstep, int64_t n_pairs,
+                   int n, float keep_prob, uint64_t seed, uint64_t step, uint8_t* d_pkeep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

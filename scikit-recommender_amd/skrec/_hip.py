@@ -123,6 +123,11 @@ SIGNATURES = {
                                      sz, vp, vp, vp]),
     "skr_multvae_queries": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "skr_multvae_draws": (i32, [vp, vp, vp, i32, i32, i32, f32, u64, u64, vp, vp, vp, vp]),
+    "skr_cdae_workspace": (sz, [i32, i64]),
+    "skr_cdae_step": (i32, [vp] * 14 + [i32, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "skr_cdae_step_timed": (i32, [vp] * 14 + [i32, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+    "skr_cdae_queries": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "skr_cdae_draws": (i32, [vp, vp, vp, vp, i64, i32, f32, u64, u64, vp, vp]),
 }
 
 class SpmmEpilogue(C.Structure):
@@ -140,6 +145,8 @@ SKR_TRANSREC_MAX_BLOCKS = 1024   # skr_transrec_step: d_work holds this many row
 SKR_SEQ_FPMC, SKR_SEQ_TRANSREC = 0, 1     # skr_seq_scores modes
 SKR_HGN_MAX_L, SKR_HGN_MAX_T, SKR_HGN_MAX_BLOCKS = 32, 16, 256   # skr_hgn_step limits; d_work holds MAX_BLOCKS partials
 SKR_MULTVAE_MAX_BATCH = 1024   # skr_multvae_step: users of a batch
+SKR_CDAE_MAX_BATCH = 1024      # skr_cdae_step: users of a batch
+SKR_CDAE_IDENTITY, SKR_CDAE_SIGMOID, SKR_CDAE_LAUNCHES = 0, 1, 3
 
 
 def hgn_gate_floats(L):
