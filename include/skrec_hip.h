@@ -855,6 +855,70 @@ int skr_cdae_queries(const float* d_E_en, const float* d_offset, const float* d_
 int skr_cdae_draws(const int32_t* d_users, const int32_t* d_puser, const int32_t* d_pitem, const int32_t* d_pstep, int64_t n_pairs,
                    int n, float keep_prob, uint64_t seed, uint64_t step, uint8_t* d_pkeep, void* stream);
 
+/* ============================================================================================
+ * G -- LightGCL, graph contrastive learning with an SVD view (csrc/lightgcl.hip)
+ * replaces: _LightGCL.forward and LightGCL.fit's step (recommender/LightGCL.py:117-169,222-232) at dropout = 0, d <= 64,
+ * svd_q <= 16.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  The SVD factors (LightGCL.py:202-204) are row-major [N, 16], zero beyond q.
+ * ========================================================================================== */
+#define SKR_LIGHTGCL_MAX_QUERIES 4096
+#define SKR_LIGHTGCL_MAX_Q 16
+#define SKR_LIGHTGCL_MAX_WG 512
+/* The InfoNCE term of one side (LightGCL.py:146-147), forward and backward, with no [n, n_rows] array:
+ *   s_bk = <d_Q[b], d_E[k]> * inv_temp,   lse_b = log(sum_k exp(s_bk) + 1e-8)   (evaluated without overflow for any s),
+ *   d_loss[0] = weight * sum_b lse_b                                               WRITTEN
+ *   d_dQ[b]   = weight * inv_temp * sum_k exp(s_bk - lse_b) d_E[k]                 WRITTEN, [n, 64]
+ *   d_dE[k]   = weight * inv_temp * sum_b exp(s_bk - lse_b) d_Q[b]                 WRITTEN, [n_rows, 64]
+ * d_Q [n, 64] (rows may repeat), n <= SKR_LIGHTGCL_MAX_QUERIES; d_E [n_rows, 64], any n_rows.  Products on the fp32 matrix
+ * pipe with exact fp32 operands; no floating-point atomic: two calls on the same inputs give the same bits.
+ * d_work: skr_lightgcl_cl_workspace(n, n_rows) bytes (0 for arguments out of range; grows with n * 64 * min(ceil(n_rows / 64),
+ * SKR_LIGHTGCL_MAX_WG)), 16-byte aligned, no initial contents, not to be shared by calls that may run at the same time. */
+size_t skr_lightgcl_cl_workspace(int n, int n_rows);
+int skr_lightgcl_cl(const float* d_Q, int n, const float* d_E, int n_rows, float inv_temp, float weight, float* d_dQ, float* d_dE,
+                    float* d_loss, void* d_work, size_t work_bytes, void* stream);
+/* One training step, forward and backward, issued on `stream`: 2 n_layers plan runs forward, the low-rank view
+ * G = E_0 + factor (factor^T S) at the batch's rows, the two InfoNCE terms, the clamped positive scores, the BPR term, and
+ * 2 n_layers plan runs backward.  Every pointer is a device pointer except the plans.
+ *   loss[0] = mean -logsigmoid(<E_u[u], E_i[p]> - <E_u[u], E_i[n]>), loss[1] = lambda1 (neg_score - pos_score),
+ *   loss[2] = lambda2 |E0|^2, loss[3] = their sum (LightGCL.py:168)                 WRITTEN
+ *   grad = the gradient of loss[0] + loss[1] with respect to E0                      WRITTEN, every row (the l2 term is the
+ *          optimiser's weight decay 2 lambda2)
+ *   sum  = E_u | E_i, the sums over the layers the reference keeps for evaluate()    WRITTEN
+ * lambda1 == 0 skips the contrastive and low-rank work (factor tables, q and addend are then not used).  Ids out of range
+ * are skipped.  n <= SKR_LIGHTGCL_MAX_QUERIES / 2 pairs.  No floating-point atomic: the step is bit-reproducible. */
+typedef struct skr_lightgcl_step_args {
+    const skr_spmm_plan* plan_a;       /* A [n_users, n_items], values 1 / sqrt(rowdeg coldeg) (LightGCL.py:185-196) */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    int32_t n_users, n_items, dim, n_layers, q, n;
+    const float* E0;                   /* [n_users + n_items, 64] the parameters */
+    const float* fac_us;               /* u_mul_s [n_users, 16] */
+    const float* fac_vs;               /* v_mul_s [n_items, 16] */
+    const float* fac_ut;               /* ut^T    [n_users, 16] */
+    const float* fac_vt;               /* vt^T    [n_items, 16] */
+    const int32_t* uids;               /* [n] */
+    const int32_t* pos;                /* [n] */
+    const int32_t* neg;                /* [n] */
+    float inv_temp, lambda1, lambda2;
+    float* sum;                        /* [n_users + n_items, 64] */
+    float* below;                      /* [n_users + n_items, 64] scratch: the sum of the layers below the last; NULL if n_layers == 1 */
+    float* ping[2];                    /* [n_users + n_items, 64] scratch each; NULL if n_layers == 1 */
+    float* gsum;                       /* [n_users + n_items, 64] scratch: dL / d sum */
+    float* addend;                     /* [n_users + n_items, 64] scratch; NULL if lambda1 == 0 */
+    float* grad;                       /* [n_users + n_items, 64] */
+    float* loss;                       /* [4] */
+    void* work;                        /* skr_lightgcl_workspace(n, n_users, n_items) bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_lightgcl_step_args;
+size_t skr_lightgcl_workspace(int n, int n_users, int n_items);
+int skr_lightgcl_step(const skr_lightgcl_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_LIGHTGCL_GROUPS launch groups (forward plan runs; sumsq, prep, low-rank
+ * reductions, gather; user side pass 1 + merge; user side pass 2 + reduce; item side pass 1 + merge; item side pass 2 +
+ * reduce; finish, seg_add, loss, dT, expansion; backward plan runs + seg_add): h_ms[k] (host) = milliseconds of group k;
+ * synchronises the stream (timing tools). */
+#define SKR_LIGHTGCL_GROUPS 8
+int skr_lightgcl_step_timed(const skr_lightgcl_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

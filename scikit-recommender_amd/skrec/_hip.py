@@ -128,7 +128,13 @@ SIGNATURES = {
     "skr_cdae_step_timed": (i32, [vp] * 14 + [i32, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
     "skr_cdae_queries": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "skr_cdae_draws": (i32, [vp, vp, vp, vp, i64, i32, f32, u64, u64, vp, vp]),
+    "skr_lightgcl_cl_workspace": (sz, [i32, i32]),
+    "skr_lightgcl_cl": (i32, [vp, i32, vp, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
+    "skr_lightgcl_workspace": (sz, [i32, i32, i32]),
+    "skr_lightgcl_step": (i32, [vp, vp]),
+    "skr_lightgcl_step_timed": (i32, [vp, vp, vp]),
 }
+
 
 class SpmmEpilogue(C.Structure):
     """skr_spmm_epilogue (include/skrec_hip.h): what happens to a finished row of a propagation"""
@@ -137,6 +143,16 @@ class SpmmEpilogue(C.Structure):
 
 
 EPI_PLAIN, EPI_REFINE_FWD, EPI_REFINE_BWD = 0, 1, 2
+
+
+class LightGCLStepArgs(C.Structure):
+    """skr_lightgcl_step_args (include/skrec_hip.h): the tables, the batch and the scratch of one LightGCL step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32),
+                ("n_layers", C.c_int32), ("q", C.c_int32), ("n", C.c_int32), ("E0", vp), ("fac_us", vp), ("fac_vs", vp),
+                ("fac_ut", vp), ("fac_vt", vp), ("uids", vp), ("pos", vp), ("neg", vp), ("inv_temp", C.c_float),
+                ("lambda1", C.c_float), ("lambda2", C.c_float), ("sum", vp), ("below", vp), ("ping", vp * 2), ("gsum", vp),
+                ("addend", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
+
 
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
@@ -147,6 +163,7 @@ SKR_HGN_MAX_L, SKR_HGN_MAX_T, SKR_HGN_MAX_BLOCKS = 32, 16, 256   # skr_hgn_step 
 SKR_MULTVAE_MAX_BATCH = 1024   # skr_multvae_step: users of a batch
 SKR_CDAE_MAX_BATCH = 1024      # skr_cdae_step: users of a batch
 SKR_CDAE_IDENTITY, SKR_CDAE_SIGMOID, SKR_CDAE_LAUNCHES = 0, 1, 3
+SKR_LIGHTGCL_MAX_QUERIES, SKR_LIGHTGCL_MAX_Q, SKR_LIGHTGCL_GROUPS = 4096, 16, 8   # skr_lightgcl_cl / _step limits
 
 
 def hgn_gate_floats(L):
