@@ -575,6 +575,27 @@ int skr_selftest_cold_math(uint64_t n_pairs, uint64_t* h_mismatches, void* strea
  * device.  (Measurement hook: tools/e2e_scale.py prints the shares of a real epoch.) */
 int skr_cold_pass_census(uint64_t* h_counts3, int reset);
 
+/* The lazily advanced rows of skr_bpr_fused_step / _pre / _end take a gradient update on the scaling-free
+ * square root and divisions when, AFTER the moment update, every lane of the wavefront holds moments of ordinary magnitudes;
+ * the zero-gradient run behind it then needs no test of its own.  With SKR_FUSED_STATS=1 in the environment the launches
+ * count their evaluations: h_counts[8 * kernel + 4 * kind + class], kernel = {0 step launch: user / item rows, 1 step launch:
+ * bias blocks, 2 end launch, 3 pre launch}, kind = {0 gradient update, 1 run of zero-gradient updates},
+ * class = {0 at rest, 1 ordinary, 3 general}; then [32] / [33] slots the end launch advanced two to a wavefront / one by one
+ * (a paired slot counts one gradient update and, where its partner was named later, one run up to that step under kernel 2;
+ * the run the two rows make together is counted in [32] only).
+ * n_counts <= 34 counters are copied (all zero when the census is off).  The
+ * variable is read at the first launch and again at every call of this function.  Synchronises the device.
+ * (Measurement hook.) */
+#define SKR_FUSED_CENSUS_COUNTERS 34
+int skr_fused_census(uint64_t* h_counts, int n_counts, int reset);
+/* skr_selftest_grad_math: that gradient update against the dense kernel's arithmetic, bits of p, m and v, on n_tuples
+ * hashed (p, g, m, v) tuples of the ordinary ranges in wavefronts of 64 at a hashed step of the block (step_t0, k; tf: TF's
+ * scalars), followed by run_len - 1 zero-gradient updates (as far as the block goes) in the same call.  Of every 16 wavefronts two are CONTROLS with lanes outside the ordinary ranges.  h_counts5 (host): [0] tuples
+ * tested, [1] mismatches (must be 0), [2] non-control wavefronts that took the scaling-free form (must be all of them),
+ * [3] / [4] controls that took the general / the scaling-free form ([4] must be 0).  (Test hook; synchronises the stream.) */
+int skr_selftest_grad_math(uint64_t n_tuples, float lr, float beta1, float beta2, float eps, int64_t step_t0, int k, int tf,
+                           int run_len, uint64_t* h_counts5, void* stream);
+
 /* Sparse exchange of a replicated table's gradient between ranks (no reference counterpart -- the
  * reference is single-process).  A BPR step touches at most 2*batch item rows, so instead of all-reducing the
  * dense [I, 65] block each rank packs its touched rows, the ranks all-gather the packs, and every rank adds

@@ -228,6 +228,80 @@ __global__ __launch_bounds__(256) void selftest_cold_math_kernel(uint32_t lo, ui
     if (b2) atomicAdd(&bad[3], b2);
 }
 
+// skr_selftest_grad_math: the gradient update of the lazy rows (adam_grad_run) against adam_elem / adam_elem_unit_bc2, bits of
+// p, m and v.  One wavefront per group of 64 hashed tuples of the ordinary ranges, all at the same step of the block.  Of
+// every 16 groups, groups 3 and 7 are CONTROLS with lanes outside the ordinary ranges (3: untouched moments m = v = +0 and
+// lanes at rest with |m| = 2^-95; 7: one lane with m = -0, a NaN p, v = +inf or a stalled denormal m), so the wavefront must
+// take the general form -- and must still give the same bits.
+__global__ __launch_bounds__(256) void selftest_grad_math_kernel(uint64_t n_groups, AdamBlockArgs a, int run_len,
+                                                                 unsigned long long* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_waves = static_cast<uint64_t>(gridDim.x) * 4;
+    unsigned long long bad = 0, fast = 0, ctl_general = 0, ctl_fast = 0, tested = 0;
+    for (uint64_t gi = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); gi < n_groups; gi += n_waves) {
+        auto mix = [](uint64_t h) {      // splitmix64
+            h *= 0x9E3779B97F4A7C15ull;
+            h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+            return h ^ (h >> 31);
+        };
+        const uint64_t h1 = mix(2 * (gi * 64 + lane) + 1), h2 = mix(2 * (gi * 64 + lane) + 2);
+        const int s = static_cast<int>(mix(~gi) % static_cast<uint64_t>(a.k));
+        auto make = [](uint32_t h, int e_lo, int e_n) {      // random sign and mantissa, exponent in [e_lo, e_lo + e_n)
+            return __uint_as_float((h & 0x807fffffu) | ((127 + e_lo + (h >> 23 & 0xff) % e_n) << 23));
+        };
+        float p = make(static_cast<uint32_t>(h1), -20, 30), m = make(static_cast<uint32_t>(h1 >> 32), -40, 50);
+        float v = fabsf(make(static_cast<uint32_t>(h2), -60, 70)), g = make(static_cast<uint32_t>(h2 >> 32), -30, 36);
+        {   // no cancellation in m + c1 * (g - m) down to the bottom of the ordinary range: opposite signs only where |g| is far from 9 |m|
+            const int de = static_cast<int>(__float_as_uint(g) >> 23 & 0xff) - static_cast<int>(__float_as_uint(m) >> 23 & 0xff);
+            if (de >= 1 && de <= 5) g = copysignf(g, m);
+        }
+        const int kind = static_cast<int>(gi & 15);
+        const bool control = kind == 7 || kind == 3;
+        if (kind == 3) {
+            if ((lane & 7) == 1) {           // null: untouched moments, g = +-0, any p without NaN (+-0 among them)
+                m = 0.0f, v = 0.0f, g = (lane & 8) ? -0.0f : 0.0f;
+                if (lane & 16) p = (lane & 32) ? -0.0f : 0.0f;
+            } else if ((lane & 7) == 2) {    // at rest and below the ordinary range
+                m = copysignf(0x1p-95f, m), g = (lane & 8) ? -0.0f : 0.0f;
+                v = 0x1p-20f * (1.0f + 0x1p-3f * (lane >> 3));
+                p = copysignf(fmaxf(fabsf(p), 0x1p-10f), p);
+            }
+        } else if (kind == 7 && lane == 5) {
+            switch (static_cast<int>(gi >> 4 & 3)) {
+                case 0: m = -0.0f, v = 0.0f, g = 0.0f, p = 0.0f; break;      // (beside an ordinary p, m = -0 is at rest)
+                case 1: m = 0.0f, v = 0.0f, g = 0.0f, p = __uint_as_float(0x7fc00001u); break;
+                case 2: v = __uint_as_float(0x7f800000u); break;
+                default: m = __uint_as_float(0x00000123u), g = 0.0f, p = 0x1p-70f; break;
+            }
+        }
+        // the gradient update and run_len - 1 zero-gradient updates behind it (as far as the block goes): the reference update
+        // by update, the lazy rows' form in one call (the gradient's quotient is then the first of the side-by-side chains)
+        const int s_to = s + run_len < a.k ? s + run_len : a.k;
+        float wp = p, wm = m, wv = v;
+        for (int q = s; q < s_to; ++q) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[q], a.bc2_sqrt[q], a.eps};
+            if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+                adam_elem_unit_bc2(wp, q == s ? g : 0.0f, wm, wv, one);
+            else
+                adam_elem(wp, q == s ? g : 0.0f, wm, wv, one);
+        }
+        const bool took_fast = adam_grad_run(p, g, m, v, a, s, s_to, FC_END);
+        bad += (__float_as_uint(p) != __float_as_uint(wp)) || (__float_as_uint(m) != __float_as_uint(wm)) ||
+               (__float_as_uint(v) != __float_as_uint(wv));
+        tested += 1;
+        if (lane == 0) {
+            if (control) (took_fast ? ctl_fast : ctl_general) += 1;
+            else fast += took_fast;
+        }
+    }
+    if (tested) atomicAdd(&out[0], tested);
+    if (bad) atomicAdd(&out[1], bad);
+    if (fast) atomicAdd(&out[2], fast);
+    if (ctl_general) atomicAdd(&out[3], ctl_general);
+    if (ctl_fast) atomicAdd(&out[4], ctl_fast);
+}
+
 // cold pass, one wavefront per 64-float block (= one embedding row), with a cheap exact path for rows AT REST.
 //
 // A zero-gradient update is p += (nss*m') / (sqrt(v')/bc2 + eps) with m' = m + c1*(0 - m), v' = v*b2.  A row that
@@ -457,6 +531,28 @@ unsigned long long* skr::cold_stats_buffer() {
     return buf;
 }
 
+// SKR_FUSED_STATS=1: a device census of how the fused BPR step's lazily advanced rows were evaluated.  The
+// environment is read at the first launch and again whenever skr_fused_census is called (reread), so a process can
+// switch the census on and off between launches.
+// (Like cold_stats_buffer, plain function-static state: the census is a single-threaded measurement hook, and a process
+// that launches from several host threads must switch it on before they start.)
+unsigned long long* skr::fused_stats_buffer(bool reread) {
+    static unsigned long long* buf = nullptr;
+    static bool on = false, read = false;
+    if (!read || reread) {
+        read = true;
+        const char* e = getenv("SKR_FUSED_STATS");
+        on = e && atoi(e) == 1;
+        if (on && !buf) {
+            if (hipMalloc(&buf, FC_COUNTERS * sizeof(unsigned long long)) == hipSuccess)
+                (void)hipMemset(buf, 0, FC_COUNTERS * sizeof(unsigned long long));
+            else
+                buf = nullptr;
+        }
+    }
+    return on ? buf : nullptr;
+}
+
 extern "C" {
 
 // The three launches behind the nine public functions.  who: the called function's name, for its error messages;
@@ -532,6 +628,19 @@ int skr_cold_pass_census(uint64_t* h_counts3, int reset) {
     return SKR_OK;
 }
 
+
+int skr_fused_census(uint64_t* h_counts, int n_counts, int reset) {
+    SKR_REQUIRE(h_counts && n_counts >= 0, "skr_fused_census: bad argument");
+    for (int i = 0; i < n_counts; ++i) h_counts[i] = 0;
+    unsigned long long* buf = fused_stats_buffer(true);
+    if (!buf) return SKR_OK;
+    unsigned long long h[FC_COUNTERS];
+    SKR_HIP(hipDeviceSynchronize());
+    SKR_HIP(hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) SKR_HIP(hipMemset(buf, 0, sizeof(h)));
+    for (int i = 0; i < n_counts && i < FC_COUNTERS; ++i) h_counts[i] = h[i];
+    return SKR_OK;
+}
 
 static int adam_block_cold_impl(const char* who, float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                                 float eps, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, bool tf, const float* wd,
@@ -679,6 +788,28 @@ int skr_selftest_cold_math(uint64_t n_pairs, uint64_t* h_mismatches, void* strea
     h_mismatches[1] = h[1];
     h_mismatches[2] = h[2];
     h_mismatches[3] = h[3];
+    return SKR_OK;
+}
+
+int skr_selftest_grad_math(uint64_t n_tuples, float lr, float beta1, float beta2, float eps, int64_t step_t0, int k, int tf,
+                           int run_len, uint64_t* h_counts5, void* stream) {
+    SKR_REQUIRE(h_counts5, "skr_selftest_grad_math: NULL argument");
+    SKR_REQUIRE(step_t0 >= 0 && k >= 1 && k <= AB_KMAX && run_len >= 1, "skr_selftest_grad_math: need 1 <= k <= %d, run_len >= 1", AB_KMAX);
+    AdamBlockArgs a{};
+    adam_shared_fields(a, beta1, beta2, eps);
+    a.k = k;
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, k, tf != 0);
+    adam_block_thresholds(a, lr, beta1, beta2, eps, k);
+    unsigned long long* d_out = nullptr;
+    SKR_HIP(hipMalloc(&d_out, 5 * sizeof(unsigned long long)));
+    SKR_HIP(hipMemsetAsync(d_out, 0, 5 * sizeof(unsigned long long), skr::as_stream(stream)));
+    hipLaunchKernelGGL(selftest_grad_math_kernel, dim3(256 * 4), dim3(256), 0, skr::as_stream(stream), n_tuples / 64, a, run_len, d_out);
+    SKR_LAUNCH_CHECK();
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    SKR_HIP(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, skr::as_stream(stream)));
+    SKR_HIP(hipStreamSynchronize(skr::as_stream(stream)));
+    (void)hipFree(d_out);
+    for (int q = 0; q < 5; ++q) h_counts5[q] = h[q];
     return SKR_OK;
 }
 

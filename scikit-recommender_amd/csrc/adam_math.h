@@ -1,5 +1,7 @@
 // adam_math.h -- the Adam arithmetic shared by the optimiser (adam.hip) and the fused BPR step (bpr_fused.hip): the
-// per-element update, its exact cheaper evaluations for zero-gradient updates, and the per-step scalars on the host.
+// per-element update (moment update + step quotient), its exact cheaper evaluations -- for zero-gradient updates in the cold
+// pass, for gradient updates and zero-gradient runs of the lazily advanced rows (adam_grad_run / adam_zero_run) -- their
+// census, and the per-step scalars on the host.
 #pragma once
 #include "skr_common.h"
 
@@ -12,20 +14,30 @@ struct AdamArgs {
     float one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps;
 };
 
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamArgs& a) {
+// the moment update every evaluation shares (AdamArgs or AdamBlockArgs): m' and v' are the same bits on every path
+template <class A>
+__device__ __forceinline__ void adam_moments(float g, float& m, float& v, const A& a) {
     m = m + a.one_minus_b1 * (g - m);           // exp_avg.lerp_(grad, 1-beta1)
     v = v * a.b2 + (a.one_minus_b2 * g) * g;    // mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p = p + (a.neg_step_size * m) / denom;      // addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-// the same update when sqrt(1 - beta2^t) is exactly 1.0f (beta2 = 0.999: from step ~16 600 on): x / 1.0f == x, so the
-// correctly rounded division by the bias correction (a dozen instructions) is left out -- results are identical
+// the step's quotient from the updated moments, general form.  UNIT_BC2: sqrt(1 - beta2^t) is exactly 1.0f (beta2 = 0.999:
+// from step ~16 600 on): x / 1.0f == x, so the correctly rounded division by the bias correction (a dozen instructions) is
+// left out -- results are identical
+template <bool UNIT_BC2>
+__device__ __forceinline__ float adam_quot(float m, float v, float neg_step_size, float bc2_sqrt, float eps) {
+    const float denom = UNIT_BC2 ? sqrtf(v) + eps : sqrtf(v) / bc2_sqrt + eps;
+    return (neg_step_size * m) / denom;         // addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamArgs& a) {
+    adam_moments(g, m, v, a);
+    p = p + adam_quot<false>(m, v, a.neg_step_size, a.bc2_sqrt, a.eps);
+}
+
 __device__ __forceinline__ void adam_elem_unit_bc2(float& p, float g, float& m, float& v, const AdamArgs& a) {
-    m = m + a.one_minus_b1 * (g - m);
-    v = v * a.b2 + (a.one_minus_b2 * g) * g;
-    const float denom = sqrtf(v) + a.eps;
-    p = p + (a.neg_step_size * m) / denom;
+    adam_moments(g, m, v, a);
+    p = p + adam_quot<true>(m, v, a.neg_step_size, a.bc2_sqrt, a.eps);
 }
 
 // the scalars of a block of k <= AB_KMAX consecutive steps (adam.hip K2b, bpr_fused.hip K2c)
@@ -42,7 +54,8 @@ struct AdamBlockArgs {
     float rest_b2k;   // a lower bound of beta2^k
     // ranges of the "ordinary magnitudes" test (fast_mlo = +inf switches it off)
     float fast_vlo, fast_mlo, fast_mhi;
-    unsigned long long* stats;   // optional census (SKR_COLD_STATS=1): cold blocks at rest / ordinary / general
+    unsigned long long* stats;   // optional census: the cold pass's (SKR_COLD_STATS=1: blocks at rest / ordinary / general) or,
+                                 // in the fused step's launches, theirs (SKR_FUSED_STATS=1: FC_* below)
 };
 
 // Square root and division for ORDINARY MAGNITUDES, bit-identical to sqrtf(x) and n / d as compiled under
@@ -118,40 +131,150 @@ __device__ __forceinline__ bool lane_ordinary(float mm, float vv, const AdamBloc
     return vv >= a.fast_vlo && vv <= 0x1p20f && am >= a.fast_mlo && am <= a.fast_mhi;
 }
 
-// A run of zero-gradient updates of one row of ordinary magnitudes, indices [s, s_to).  The quotient of update s depends on
-// m_s and v_s only -- not on p -- so the square-root / division chains of consecutive updates are independent of each other:
-// four of them are laid side by side (one wavefront alone on its SIMD otherwise waits out the latency of every one of the
-// ~25 dependent instructions of a chain: ~200 cycles per update instead of ~70), and p takes the quotients in order -- the
-// same operations on the same values as update after update.
+// ---- the lazy rows' updates (fused_advance of bpr_fused.hip) -----------------------------------------------------------------
+// The scaling-free quotient of one update from the UPDATED moments: the same operations as adam_one_ordinary
 template <bool UNIT_BC2>
-__device__ __forceinline__ void ordinary_run(float& p, float& m, float& v, const AdamBlockArgs& a, int& s, int s_to) {
+__device__ __forceinline__ float adam_quot_ordinary(float m, float v, float neg_step_size, float bc2_sqrt, float eps) {
+    float sq = sqrt_ordinary(v);
+    if (!UNIT_BC2) sq = div_ordinary(sq, bc2_sqrt);
+    return div_ordinary(neg_step_size * m, sq + eps);
+}
+
+// census of the lazy rows' evaluations (SKR_FUSED_STATS=1, skr_fused_census): counter = 8 * kernel + 4 * kind + class
+enum { FC_STEP_ROW = 0, FC_STEP_BIAS = 1, FC_END = 2, FC_PRE = 3, FC_KERNELS = 4 };   // kernel
+enum { FC_GRAD = 0, FC_RUN = 1 };                                                               // kind: gradient update / zero-gradient run
+enum { FC_REST = 0, FC_ORD = 1, FC_GENERAL = 3 };                                               // class (2: not used)
+constexpr int FC_END_PAIRED = 8 * FC_KERNELS;       // end launch: slots advanced two to a wavefront / alone
+constexpr int FC_END_SINGLE = FC_END_PAIRED + 1;
+constexpr int FC_COUNTERS = FC_END_PAIRED + 2;
+
+__device__ __forceinline__ void fused_count(const AdamBlockArgs& a, int ck, int kind, int cls) {
+    if (a.stats && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[8 * ck + 4 * kind + cls], 1ull);
+}
+
+// Updates [s, s_to) of a row of ordinary magnitudes.  `updated`: the moments already hold update s (the gradient update's,
+// which then is the first chain here); every other update is a zero-gradient one.  The quotient of an update depends on
+// that update's m and v only -- not on p -- so the square-root / division chains of consecutive updates are independent of
+// each other: four of them are laid side by side (one wavefront alone on its SIMD otherwise waits out the latency of every
+// one of the ~25 dependent instructions of a chain: ~200 cycles per update instead of ~70), and p takes the quotients in
+// order -- the same operations on the same values as update after update.
+template <bool UNIT_BC2>
+__device__ __forceinline__ void ordinary_run(float& p, float& m, float& v, const AdamBlockArgs& a, int& s, int s_to, bool& updated) {
     for (; s + 4 <= s_to; s += 4) {
         float ms[4], vs[4], q[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            m = m + a.one_minus_b1 * (0.0f - m);
-            v = v * a.b2;
+            if (u > 0 || !updated) {
+                m = m + a.one_minus_b1 * (0.0f - m);
+                v = v * a.b2;
+            }
             ms[u] = m;
             vs[u] = v;
         }
+        updated = false;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float sq = sqrt_ordinary(vs[u]);
-            if (!UNIT_BC2) sq = div_ordinary(sq, a.bc2_sqrt[s + u]);
-            q[u] = div_ordinary(a.neg_step_size[s + u] * ms[u], sq + a.eps);
-        }
+        for (int u = 0; u < 4; ++u) q[u] = adam_quot_ordinary<UNIT_BC2>(ms[u], vs[u], a.neg_step_size[s + u], a.bc2_sqrt[s + u], a.eps);
 #pragma unroll
         for (int u = 0; u < 4; ++u) p = p + q[u];
     }
     for (; s < s_to; ++s) {
+        if (!updated) {
+            m = m + a.one_minus_b1 * (0.0f - m);
+            v = v * a.b2;
+        }
+        updated = false;
+        p = p + adam_quot_ordinary<UNIT_BC2>(m, v, a.neg_step_size[s], a.bc2_sqrt[s], a.eps);
+    }
+}
+
+// the same, choosing the form: sqrt(1 - beta2^t) rises with t and stays at 1.0f once it gets there, so a run is all-unit,
+// all-non-unit, or (around step 16 600, once) mixed -- then update by update
+__device__ __forceinline__ void fast_run(float& p, float& m, float& v, const AdamBlockArgs& a, int s, int s_to, bool updated) {
+    if (s >= s_to) return;
+    if (__builtin_amdgcn_readfirstlane(__float_as_int(a.bc2_sqrt[s])) == 0x3f800000) {
+        ordinary_run<true>(p, m, v, a, s, s_to, updated);
+    } else if (__builtin_amdgcn_readfirstlane(__float_as_int(a.bc2_sqrt[s_to - 1])) != 0x3f800000) {
+        ordinary_run<false>(p, m, v, a, s, s_to, updated);
+    } else {
+        for (; s < s_to; ++s) {
+            int s1 = s;
+            if (__builtin_amdgcn_readfirstlane(__float_as_int(a.bc2_sqrt[s])) == 0x3f800000)
+                ordinary_run<true>(p, m, v, a, s1, s + 1, updated);
+            else
+                ordinary_run<false>(p, m, v, a, s1, s + 1, updated);
+        }
+    }
+}
+
+// zero-gradient updates [s, s_to) of one row, on the cold pass's three evaluations (all 64 lanes at rest: the moments decay;
+// all of ordinary magnitudes: scaling-free; general otherwise).  ck: the census's kernel index
+__device__ __forceinline__ void adam_zero_run(float& p, float& m, float& v, const AdamBlockArgs& a, int s, int s_to, int ck) {
+    if (s >= s_to) return;
+    if (__builtin_amdgcn_ballot_w64(!lane_at_rest(p, m, v, a.nss_bound[s], a)) == 0) {
+        fused_count(a, ck, FC_RUN, FC_REST);
+        for (; s < s_to; ++s) {
+            m = m + a.one_minus_b1 * (0.0f - m);
+            v = v * a.b2;
+        }
+    } else if (__builtin_amdgcn_ballot_w64(!lane_ordinary(m, v, a)) == 0) {
+        fused_count(a, ck, FC_RUN, FC_ORD);
+        fast_run(p, m, v, a, s, s_to, false);
+    } else {
+        fused_count(a, ck, FC_RUN, FC_GENERAL);
+        for (; s < s_to; ++s) {
+            AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
+            if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+                adam_elem_unit_bc2(p, 0.0f, m, v, one);
+            else
+                adam_elem(p, 0.0f, m, v, one);
+        }
+    }
+}
+
+// update s with gradient g, then the zero-gradient updates [s + 1, s_to).  The lanes are tested ONCE, after the moment
+// update, on (m', v'): the ranges of sqrt_ordinary / div_ordinary then hold for the very operands of this update's quotient,
+// and the block's thresholds cover the decays of every later update of the block -- so the run behind the gradient update
+// needs no test of its own, and the gradient update's quotient is the first of ordinary_run's side-by-side chains.
+// Needs s < s_to <= a.k (update s is always made).  Returns whether the wavefront took the scaling-free evaluation.
+// adam_grad_finish is the part behind the moment update and the test (`ord`: every lane passed lane_ordinary on m', v').
+__device__ __forceinline__ bool adam_grad_finish(float& p, float& m, float& v, const AdamBlockArgs& a, int s, int s_to, int ck, bool ord) {
+    if (ord) {
+        fused_count(a, ck, FC_GRAD, FC_ORD);
+        if (s + 1 < s_to) fused_count(a, ck, FC_RUN, FC_ORD);
+        fast_run(p, m, v, a, s, s_to, true);
+        return true;
+    }
+    fused_count(a, ck, FC_GRAD, FC_GENERAL);
+    const float nss = a.neg_step_size[s], bc2 = a.bc2_sqrt[s];
+    if (__builtin_amdgcn_readfirstlane(__float_as_int(bc2)) == 0x3f800000)
+        p = p + adam_quot<true>(m, v, nss, bc2, a.eps);
+    else
+        p = p + adam_quot<false>(m, v, nss, bc2, a.eps);
+    adam_zero_run(p, m, v, a, s + 1, s_to, ck);
+    return false;
+}
+
+__device__ __forceinline__ bool adam_grad_run(float& p, float g, float& m, float& v, const AdamBlockArgs& a, int s, int s_to, int ck) {
+    adam_moments(g, m, v, a);
+    return adam_grad_finish(p, m, v, a, s, s_to, ck, __builtin_amdgcn_ballot_w64(!lane_ordinary(m, v, a)) == 0);
+}
+
+// zero-gradient updates [s, s_to) of TWO rows of ordinary magnitudes in one wavefront, on the cold pass's packed pair form
+__device__ __forceinline__ void adam_pair_run(f32x2& p, f32x2& m, f32x2& v, const AdamBlockArgs& a, int s, int s_to) {
+    for (; s < s_to; ++s) {
         AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
-        adam_one_ordinary<UNIT_BC2>(p, m, v, one);
+        if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
+            adam_pair_ordinary<true>(p, m, v, one);
+        else
+            adam_pair_ordinary<false>(p, m, v, one);
     }
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
 // SKR_COLD_STATS=1: the device census of how the cold passes sorted their blocks, or NULL (defined in adam.hip)
 __attribute__((visibility("hidden"))) unsigned long long* cold_stats_buffer();
+// SKR_FUSED_STATS=1: the census of the lazy rows' evaluations (FC_COUNTERS counters), or NULL (defined in adam.hip)
+__attribute__((visibility("hidden"))) unsigned long long* fused_stats_buffer(bool reread = false);
 
 // the fields every step of a run shares (A: AdamArgs or AdamBlockArgs)
 template <class A>

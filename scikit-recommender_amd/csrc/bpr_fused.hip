@@ -25,8 +25,9 @@ constexpr int BPR_WAVES = 4;      // wavefronts per workgroup, as bpr_step_kerne
 // The row's state before step s:  n0 == 0: the dense tables (no step of the block has touched it);  n0 > 0: workspace copy
 // n0 & 1, valid through optimiser index prev - 1, plus the gradient of step `prev` waiting in gradient buffer (n0 - 1) % 3.
 // Every wavefront that reads the row applies, in registers, index `prev` with that gradient and the zero-gradient indices
-// prev + 1 .. s - 1 -- the updates the dense optimiser makes, in its arithmetic (adam_elem and the at-rest / ordinary
-// evaluations of the cold pass, which give the same bits) -- and uses the result for its scores.  The pair's OWNER also
+// prev + 1 .. s - 1 -- the updates the dense optimiser makes, in its arithmetic (adam_math.h: the shared moment update, then
+// the scaling-free quotient when every lane is of ordinary magnitudes -- tested on the updated moments, once for the gradient
+// update and the run behind it -- the general form otherwise: the same bits) -- and uses the result for its scores.  The pair's OWNER also
 // writes it to copy (n0 + 1) & 1 and clears gradient buffer (n0 + 1) % 3; all of them add this step's gradient into buffer
 // n0 % 3.  Within one launch nobody writes what another wavefront reads: two state copies and three gradient buffers keep
 // readers, the writer and the accumulators apart, so no wavefront waits for another and no hand-off crosses the L2s.
@@ -41,46 +42,14 @@ struct FusedRow {
     float p, m, v, g;
 };
 
-// zero-gradient indices [s_from, s_to) and, before them, index g_idx with gradient r.g (g_idx < 0: none)
-__device__ __forceinline__ void fused_advance(FusedRow& r, int g_idx, int s_from, int s_to, const AdamBlockArgs& a) {
-    if (g_idx >= 0) {
-        AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[g_idx], a.bc2_sqrt[g_idx], a.eps};
-        if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
-            adam_elem_unit_bc2(r.p, r.g, r.m, r.v, one);
-        else
-            adam_elem(r.p, r.g, r.m, r.v, one);
-    }
-    int s = s_from;
-    if (s < s_to) {
-        if (__builtin_amdgcn_ballot_w64(!lane_at_rest(r.p, r.m, r.v, a.nss_bound[s], a)) == 0) {
-            for (; s < s_to; ++s) {
-                r.m = r.m + a.one_minus_b1 * (0.0f - r.m);
-                r.v = r.v * a.b2;
-            }
-        } else if (__builtin_amdgcn_ballot_w64(!lane_ordinary(r.m, r.v, a)) == 0) {
-            // sqrt(1 - beta2^t) rises with t and stays at 1.0f once it gets there: the run is all-unit, all-non-unit, or
-            // (around step 16 600, once) mixed -- then update by update
-            if (__builtin_amdgcn_readfirstlane(__float_as_int(a.bc2_sqrt[s])) == 0x3f800000)
-                ordinary_run<true>(r.p, r.m, r.v, a, s, s_to);
-            else if (__builtin_amdgcn_readfirstlane(__float_as_int(a.bc2_sqrt[s_to - 1])) != 0x3f800000)
-                ordinary_run<false>(r.p, r.m, r.v, a, s, s_to);
-            else
-                for (; s < s_to; ++s) {
-                    AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
-                    if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
-                        adam_one_ordinary<true>(r.p, r.m, r.v, one);
-                    else
-                        adam_one_ordinary<false>(r.p, r.m, r.v, one);
-                }
-        }
-    }
-    for (; s < s_to; ++s) {
-        AdamArgs one{a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size[s], a.bc2_sqrt[s], a.eps};
-        if (__builtin_amdgcn_readfirstlane(__float_as_int(one.bc2_sqrt)) == 0x3f800000)
-            adam_elem_unit_bc2(r.p, 0.0f, r.m, r.v, one);
-        else
-            adam_elem(r.p, 0.0f, r.m, r.v, one);
-    }
+// prev1 > 0: index prev1 - 1 with gradient r.g, then the zero-gradient indices [prev1, s_to) (the plan has prev1 <= s_to: the
+// previous naming lies before this step);  prev1 == 0: the zero-gradient indices [s_from, s_to) only.  ck: the census's kernel
+// index (adam_math.h)
+__device__ __forceinline__ void fused_advance(FusedRow& r, int prev1, int s_from, int s_to, const AdamBlockArgs& a, int ck) {
+    if (prev1 > 0)
+        adam_grad_run(r.p, r.g, r.m, r.v, a, prev1 - 1, s_to, ck);
+    else
+        adam_zero_run(r.p, r.m, r.v, a, s_from, s_to, ck);
 }
 
 struct FusedWork {
@@ -150,7 +119,7 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 const int prev1 = (mt[r] >> 24) & 0x7f;
-                fused_advance(row[r], prev1 - 1, from[r], s_now, a);
+                fused_advance(row[r], prev1, from[r], s_now, a, r < 3 ? FC_STEP_ROW : FC_STEP_BIAS);
             }
         }
         if (!(dbg & 4)) {
@@ -237,7 +206,7 @@ __global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const float* __restr
     const int64_t e = blk * 64 + lane;
     FusedRow r{1.0f, 0.0f, 0.0f, 0.0f};
     if (e < n_par) { r.p = P[e]; r.m = M[e]; r.v = V[e]; }
-    fused_advance(r, -1, 0, first, a);
+    fused_advance(r, 0, 0, first, a, FC_PRE);
     const int64_t o = slot * 64 + lane;
     pre[o] = r.p;
     pre[cap * 64 + o] = r.m;
@@ -245,38 +214,89 @@ __global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const float* __restr
 }
 
 // end of a k-step block: every slot is brought to the block's last index and written back; its gradient buffers are
-// left zero for the next block.  fin = (number of namings mod 6) | (step of the last naming << 8) | (step of the first << 16)
+// left zero for the next block.  fin = (number of namings mod 6) | (step of the last naming << 8) | (step of the first << 16).
+// A wavefront takes two neighbouring slots.  Each row makes its own gradient update (index `last`) and its zero-gradient
+// updates up to the later of the two rows' last namings; from there to the block's end two rows that both passed the
+// ordinary test advance together on the packed pair form (adam_pair_ordinary: the cold pass's, the same operations per
+// component).  A pair with a row that failed the test or that the `which` filter drops, and a lone last slot, run one by one.
 __global__ __launch_bounds__(256) void bpr_fused_end_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
                                                             int64_t n_par, FusedWork w, const int32_t* __restrict__ slot_blk,
                                                             const int32_t* __restrict__ slot_fin,
                                                             const int32_t* __restrict__ n_slots, AdamBlockArgs a,
                                                             const int32_t* __restrict__ tag_next, int32_t tag_next_value, int which) {
     const int lane = threadIdx.x & 63;
-    const int64_t slot = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (slot >= *n_slots) return;
-    const int64_t blk = slot_blk[slot];
-    // which = 1: only the rows the NEXT block touches too (it must find them in the dense tables); 2: only the others (they
-    // can be written back beside the next block's steps); 0: all
-    if (which != 0 && ((tag_next[blk] == tag_next_value) != (which == 1))) return;
-    const int fin = slot_fin[slot], nn = fin & 7, last = (fin >> 8) & 0xff;
-    FusedRow r;
-    {
-        const int64_t e = ((nn & 1) * w.cap + slot) * 64 + lane;
-        r.p = w.wp[e];
-        r.m = w.wm[e];
-        r.v = w.wv[e];
-        r.g = w.g[(((nn + 2) % 3) * w.cap + slot) * 64 + lane];
+    const int64_t slot0 = 2 * (static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    const int64_t n = *n_slots;
+    if (slot0 >= n) return;
+    FusedRow r[2];
+    int64_t e[2];
+    int last[2];
+    bool live[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int64_t slot = slot0 + h;
+        live[h] = slot < n;
+        e[h] = 0, last[h] = 0;
+        r[h] = FusedRow{1.0f, 0.0f, 0.0f, 0.0f};
+        if (!live[h]) continue;
+        const int64_t blk = slot_blk[slot];
+        // which = 1: only the rows the NEXT block touches too (it must find them in the dense tables); 2: only the others (they
+        // can be written back beside the next block's steps); 0: all
+        if (which != 0 && ((tag_next[blk] == tag_next_value) != (which == 1))) {
+            live[h] = false;
+            continue;
+        }
+        const int fin = slot_fin[slot], nn = fin & 7;
+        last[h] = (fin >> 8) & 0xff;
+        e[h] = blk * 64 + lane;
+        if (e[h] < n_par) {
+            const int64_t o = ((nn & 1) * w.cap + slot) * 64 + lane;
+            r[h].p = w.wp[o];
+            r[h].m = w.wm[o];
+            r[h].v = w.wv[o];
+            r[h].g = w.g[(((nn + 2) % 3) * w.cap + slot) * 64 + lane];
+        }
     }
-    const int64_t e = blk * 64 + lane;
-    if (e >= n_par) r = FusedRow{1.0f, 0.0f, 0.0f, 0.0f};
-    fused_advance(r, last, last + 1, a.k, a);
-    if (e < n_par) {
-        P[e] = r.p;
-        M[e] = r.m;
-        V[e] = r.v;
+    if (live[0] && live[1]) {
+        bool ord[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            adam_moments(r[h].g, r[h].m, r[h].v, a);
+            ord[h] = __builtin_amdgcn_ballot_w64(!lane_ordinary(r[h].m, r[h].v, a)) == 0;
+        }
+        if (ord[0] && ord[1]) {
+            const int hi = last[0] > last[1] ? last[0] : last[1];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) adam_grad_finish(r[h].p, r[h].m, r[h].v, a, last[h], hi + 1, FC_END, true);
+            f32x2 p2{r[0].p, r[1].p}, m2{r[0].m, r[1].m}, v2{r[0].v, r[1].v};
+            adam_pair_run(p2, m2, v2, a, hi + 1, a.k);
+            r[0].p = p2.x, r[0].m = m2.x, r[0].v = v2.x;
+            r[1].p = p2.y, r[1].m = m2.y, r[1].v = v2.y;
+            if (a.stats && lane == 0) atomicAdd(&a.stats[FC_END_PAIRED], 2ull);
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) adam_grad_finish(r[h].p, r[h].m, r[h].v, a, last[h], a.k, FC_END, ord[h]);
+            if (a.stats && lane == 0) atomicAdd(&a.stats[FC_END_SINGLE], 2ull);
+        }
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (!live[h]) continue;
+            adam_grad_run(r[h].p, r[h].g, r[h].m, r[h].v, a, last[h], a.k, FC_END);
+            if (a.stats && lane == 0) atomicAdd(&a.stats[FC_END_SINGLE], 1ull);
+        }
     }
 #pragma unroll
-    for (int q = 0; q < 3; ++q) w.g[(q * w.cap + slot) * 64 + lane] = 0.0f;
+    for (int h = 0; h < 2; ++h) {
+        if (!live[h]) continue;
+        if (e[h] < n_par) {
+            P[e[h]] = r[h].p;
+            M[e[h]] = r[h].m;
+            V[e[h]] = r[h].v;
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) w.g[(q * w.cap + slot0 + h) * 64 + lane] = 0.0f;
+    }
 }
 
 // ---- the references' words of a k-step block (skr_bpr_fused_plan): four small launches, no sort -------------------------
@@ -377,6 +397,7 @@ static const AdamBlockArgs& fused_block_args(float lr, float beta1, float beta2,
         adam_block_thresholds(a, lr, beta1, beta2, eps, k);
         key = Key{lr, beta1, beta2, eps, step_t0, k};
     }
+    a.stats = fused_stats_buffer();
     return a;
 }
 
@@ -463,6 +484,7 @@ int skr_bpr_fused_pre(const float* d_p, const float* d_m, const float* d_v, int6
     a.k = k;
     adam_block_scalars(a, lr, beta1, beta2, step_t0, k, false);
     adam_block_thresholds(a, lr, beta1, beta2, eps, k);
+    a.stats = fused_stats_buffer();
     hipLaunchKernelGGL(bpr_fused_pre_kernel, dim3(static_cast<unsigned>((cap + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_p, d_m,
                        d_v, n, d_pre, cap, d_slot_block, d_slot_fin, d_n_slots, a, d_tag_prev, tag_prev_value);
     SKR_LAUNCH_CHECK();
@@ -477,7 +499,7 @@ int skr_bpr_fused_end(float* d_p, float* d_m, float* d_v, int64_t n, float* d_wo
     SKR_REQUIRE(step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "skr_bpr_fused_end: need 1 <= k <= %d", AB_KMAX);
     SKR_REQUIRE(which >= 0 && which <= 2 && (which == 0 || d_tag_next), "skr_bpr_fused_end: which must be 0, or 1 / 2 with the next block's tags");
     const AdamBlockArgs& a = fused_block_args(lr, beta1, beta2, eps, step_t0, k);
-    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>((cap + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_p,
+    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>((cap + 7) / 8)), dim3(256), 0, skr::as_stream(stream), d_p,
                        d_m, d_v, n, fused_work(d_work, cap), d_slot_block, d_slot_fin, d_n_slots, a, d_tag_next, tag_next_value, which);
     SKR_LAUNCH_CHECK();
     return SKR_OK;

@@ -1,6 +1,7 @@
 """Where the time of skr_bpr_fused_step goes: k launches of a block timed with HIP events, nothing beside them.
 SKR_FUSED_DBG (one-wavefront kernel only; results are then wrong, timing only): 1 no catch-up arithmetic, 2 no gradient
-atomics, 4 no owner stores, 8 no loss atomics. 
+atomics, 4 no owner stores, 8 no loss atomics.  SKR_FUSED_STATS=1: prints the census of the evaluations (skr_fused_census;
+its counters slow the launches -- not for timing).
 usage: python tools/fused_lab.py [k] [blocks]"""
 import os
 import sys
@@ -60,3 +61,13 @@ h = n_blocks // 2
 print(f"k={k} dbg={os.environ.get('SKR_FUSED_DBG', '0')}: "
       f"plan {np.mean(t_plan[h:]) * 1e3:.1f} us/block, steps {np.mean(t_steps[h:]) * 1e3 / k:.2f} us/step, end {np.mean(t_end[h:]) * 1e3:.1f} us/block"
       f"  (slots {int(ns)})")
+if os.environ.get("SKR_FUSED_STATS") == "1":
+    import ctypes
+    cen = (ctypes.c_uint64 * 34)()
+    _hip.check(L.skr_fused_census(cen, 34, 0))
+    for kn, name in enumerate(("step: rows", "step: bias blocks", "end", "pre")):
+        for kd, kind in enumerate(("gradient updates", "zero-gradient runs")):
+            c = [int(x) for x in cen[8 * kn + 4 * kd:8 * kn + 4 * kd + 4]]
+            if sum(c):
+                print(f"census {name:18s} {kind:18s}: at rest {c[0]}, ordinary {c[1]}, general {c[3]}")
+    print(f"census end launch: slots paired {int(cen[32])}, one by one {int(cen[33])}")
