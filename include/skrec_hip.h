@@ -940,6 +940,61 @@ int skr_lightgcl_step(const skr_lightgcl_step_args* args, void* stream);
 #define SKR_LIGHTGCL_GROUPS 8
 int skr_lightgcl_step_timed(const skr_lightgcl_step_args* args, void* stream, float* h_ms);
 
+/* ============================================================================================
+ * H -- DENS, disentangled negative sampling on a propagated embedding (csrc/dens.hip)
+ * replaces: _DENS.forward, dise_negative_sampling, create_bpr_loss and DENS.fit's step (recommender/DENS.py:115-136,
+ * 196-257, 318-374, 449-453) at ns = "dens", pool = "mean", K = 1, no message or edge dropout, dim <= 64.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  The parameters are ONE flat buffer: the [n_users + n_items, 64] rows, then the four gate blocks
+ * user_gate, item_gate, pos_gate, neg_gate of SKR_DENS_GATE_FLOATS each: W row-major [64 out][64 in], then b [64], zero
+ * beyond dim.  The gradient has the same layout.
+ * ========================================================================================== */
+#define SKR_DENS_MAX_BATCH 2048
+#define SKR_DENS_MAX_NEGS 16
+#define SKR_DENS_MAX_HOPS 3
+#define SKR_DENS_MAX_WG 128
+#define SKR_DENS_GATE_FLOATS (64 * 64 + 64)
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   X_0 = the parameter rows, X_h = A-hat X_(h-1): 2 n_hops plan runs; per batch row b and hop h, with s = X_h[u],
+ *   p = X_h[pos], c_k = X_h[cand_k]:  gp = sigmoid(item_gate(p) + user_gate(s)), gn_k = sigmoid(neg_gate(c_k) + pos_gate(p gp)),
+ *   k*(b, h) = argmax_k <s, w c_k - c_k gn_k> (the first of equal scores); the loss of DENS.py:318-374 on the hop means with the
+ *   gate values of the selection; its backward, the hop-h gradient rows added per distinct node in a fixed order, then
+ *   acc = G_H, acc = A-hat acc + G_h for h = n_hops-1 .. 0: 2 n_hops plan runs.
+ *   loss[0] = mf, loss[1] = emb, loss[2] = mf + emb                                   WRITTEN
+ *   grad = the gradient of loss[2] with respect to the flat parameter buffer          WRITTEN, every element
+ *   sel_out[b, h] = k*(b, h)                                                           WRITTEN when not NULL
+ *   sel_in[b, h] >= 0 forces k*(b, h) to that candidate (values beyond n_negs - 1 are clamped); -1: the kernel chooses
+ * The gamma terms apply when gamma > 0.  Rows whose user or positive item is out of range contribute nothing; a candidate
+ * out of range counts as a zero row.  Every product of the selection is fp32 (v_mfma_f32_16x16x4_f32 and fp32 VALU).
+ * No floating-point atomic: the step is bit-reproducible. */
+typedef struct skr_dens_step_args {
+    const skr_spmm_plan* plan_a;       /* A [n_users, n_items], values 1 / sqrt(rowdeg coldeg); may be NULL if n_hops == 0 */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    int32_t n_users, n_items, dim, n_hops, n_negs, n;
+    const float* params;               /* the flat parameter buffer */
+    const int32_t* uids;               /* [n] */
+    const int32_t* pos;                /* [n] */
+    const int32_t* cand;               /* [n, n_negs] */
+    const int32_t* sel_in;             /* [n, n_hops + 1] or NULL */
+    int32_t* sel_out;                  /* [n, n_hops + 1] or NULL */
+    float w;                           /* 1 - min(1, epoch / warmup) */
+    float gamma, l2;
+    float* hop[SKR_DENS_MAX_HOPS];     /* X_1 .. X_(n_hops), [n_users + n_items, 64] each              WRITTEN */
+    float* G[SKR_DENS_MAX_HOPS + 1];   /* scratch, [n_users + n_items, 64] each: G_0 .. G_(n_hops); not used if n_hops == 0 */
+    float* ping;                       /* scratch, [n_users + n_items, 64]; NULL if n_hops < 2 */
+    float* grad;                       /* the flat gradient buffer */
+    float* loss;                       /* [3] */
+    void* work;                        /* skr_dens_workspace(n, n_hops) bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_dens_step_args;
+size_t skr_dens_workspace(int n, int n_hops);
+int skr_dens_step(const skr_dens_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_DENS_GROUPS launch groups (forward plan runs; select; pool and loss;
+ * back and gate_reduce; clears, rank and seg_add; backward plan runs): h_ms[k] (host) = milliseconds of group k;
+ * synchronises the stream (timing tools). */
+#define SKR_DENS_GROUPS 6
+int skr_dens_step_timed(const skr_dens_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

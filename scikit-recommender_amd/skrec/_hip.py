@@ -135,6 +135,9 @@ SIGNATURES = {
     "skr_lightgcl_workspace": (sz, [i32, i32, i32]),
     "skr_lightgcl_step": (i32, [vp, vp]),
     "skr_lightgcl_step_timed": (i32, [vp, vp, vp]),
+    "skr_dens_workspace": (sz, [i32, i32]),
+    "skr_dens_step": (i32, [vp, vp]),
+    "skr_dens_step_timed": (i32, [vp, vp, vp]),
 }
 
 
@@ -156,6 +159,14 @@ class LightGCLStepArgs(C.Structure):
                 ("addend", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
 
 
+class DensStepArgs(C.Structure):
+    """skr_dens_step_args (include/skrec_hip.h): the parameters, the batch, the hop tables and the scratch of one DENS step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32),
+                ("n_hops", C.c_int32), ("n_negs", C.c_int32), ("n", C.c_int32), ("params", vp), ("uids", vp), ("pos", vp),
+                ("cand", vp), ("sel_in", vp), ("sel_out", vp), ("w", C.c_float), ("gamma", C.c_float), ("l2", C.c_float),
+                ("hop", vp * 3), ("G", vp * 4), ("ping", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -166,6 +177,8 @@ SKR_MULTVAE_MAX_BATCH = 1024   # skr_multvae_step: users of a batch
 SKR_CDAE_MAX_BATCH = 1024      # skr_cdae_step: users of a batch
 SKR_CDAE_IDENTITY, SKR_CDAE_SIGMOID, SKR_CDAE_LAUNCHES = 0, 1, 3
 SKR_LIGHTGCL_MAX_QUERIES, SKR_LIGHTGCL_MAX_Q, SKR_LIGHTGCL_GROUPS = 4096, 16, 8   # skr_lightgcl_cl / _step limits
+SKR_DENS_MAX_BATCH, SKR_DENS_MAX_NEGS, SKR_DENS_MAX_HOPS, SKR_DENS_GROUPS = 2048, 16, 3, 6   # skr_dens_step limits
+SKR_DENS_GATE_FLOATS = 64 * 64 + 64      # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 
 def hgn_gate_floats(L):
