@@ -376,6 +376,15 @@ typedef struct skr_spmm_epilogue {
 } skr_spmm_epilogue;
 int skr_spmm_plan_run_ex(const skr_spmm_plan* plan, const float* d_X, int dim, const skr_spmm_epilogue* epi,
                          const uint8_t* d_row_mask, const uint8_t* d_col_mask, void* stream);
+/* The product with per-ENTRY dropout (edge dropout drawn anew for every step, no new plan):
+ *   A'[e] = d_keep[e] ? val[e] * scale : 0     (one fp32 multiply; the reference's v[mask] * (1. / (1 - rate)),
+ *                                                recommender/SelfCF.py:133-144, with scale = float32(1 / (1 - rate)))
+ * d_keep: uint8 [nnz] in the plan's CSR entry order.  A dropped entry is SKIPPED: its row of X is not gathered.  Same row /
+ * task / reduce structure and the same fixed order of additions as skr_spmm_plan_run_ex; the plan's densest rows go through
+ * the task path (their block-major copies hold no flags).  No float atomic: repeated runs are bit-identical.  SKR_EPI_PLAIN
+ * only (any other mode: SKR_EINVAL); a row whose entries are all dropped still gets its epilogue (y = addend_r or 0). */
+int skr_spmm_plan_run_dropped(const skr_spmm_plan* plan, const float* d_X, int dim, const skr_spmm_epilogue* epi,
+                              const uint8_t* d_keep, float scale, void* stream);
 int skr_spmm_plan_info(const skr_spmm_plan* plan, int64_t* h_info4);
 int skr_spmm_plan_destroy(skr_spmm_plan* plan);
 
@@ -994,6 +1003,77 @@ int skr_dens_step(const skr_dens_step_args* args, void* stream);
  * synchronises the stream (timing tools). */
 #define SKR_DENS_GROUPS 6
 int skr_dens_step_timed(const skr_dens_step_args* args, void* stream, float* h_ms);
+
+/* ============================================================================================
+ * I -- SelfCF, self-supervised collaborative filtering with edge dropout (csrc/selfcf.hip)
+ * replaces: LightGCN_Encoder.sparse_dropout / forward, SELFCFED_LGN.forward / calculate_loss / full_sort_predict and
+ * SelfCF.fit's step (recommender/SelfCF.py:133-168, 205-241, 267-274) at embed_dim <= 64.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  The parameters are ONE flat buffer: the [n_users + n_items, 64] rows, then the predictor's W row-major
+ * [64 out][64 in] and b [64] (SKR_SELFCF_PRED_FLOATS), zero beyond dim.  The gradient has the same layout.
+ * R is the binary train matrix in CSR, A the plan of its normalisation (SelfCF.py:118-123), At the plan of the transpose;
+ * perm[e] is the position in At's entry order of entry e of A's.
+ * ========================================================================================== */
+#define SKR_SELFCF_MAX_BATCH 2048
+#define SKR_SELFCF_MAX_LAYERS 4
+#define SKR_SELFCF_PRED_FLOATS (64 * 64 + 64)
+/* The four keep arrays of one step's plan runs, nnz bytes each.  The reference masks the 2 nnz entries of the square
+ * matrix independently (SelfCF.py:147-149): k1 [nnz] covers the user rows (A's order), k2 [nnz] the item rows (At's order),
+ * and the masked matrix [[0, R1], [R2^T, 0]] is not symmetric.
+ *   d_fu = k1 (forward, user rows: runs of A)        d_fi = k2 (forward, item rows: runs of At)
+ *   d_bu = k2 in A's order (backward, user rows)     d_bi = k1 in At's order (backward, item rows)
+ * d_k1 / d_k2 NULL: drawn on the device -- keep iff a 24-bit uniform keyed by (seed, step, half, entry) is >= rate (the
+ * reference's floor(1 - rate + rand), equal in law only). */
+int skr_selfcf_keeps(const int32_t* d_perm, int64_t nnz, const uint8_t* d_k1, const uint8_t* d_k2, float rate, uint64_t seed,
+                     uint64_t step, uint8_t* d_fu, uint8_t* d_fi, uint8_t* d_bu, uint8_t* d_bi, void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   X_0 = the parameter rows, X_k = A-hat' X_(k-1) through skr_spmm_plan_run_dropped (2 n_layers runs), M = mean_k X_k;
+ *   with u = M[users], i = M[n_users + items]:  p_u = W u + b, p_i = W i + b, t_u = u ku / (1 - dropout),
+ *   t_i = i ki / (1 - dropout), c(x, y) = <x, y> / (max(|x|, 1e-8) max(|y|, 1e-8)),
+ *   loss[0] = -mean c(p_u, t_i) / 2 - mean c(p_i, t_u) / 2, loss[1] = reg * 0.5 * (sum u^2 + sum i^2) over the batch rows
+ *   (duplicates counted), loss[2] = their sum (SelfCF.py:221-233)                      WRITTEN
+ *   grad = the gradient of loss[2] with respect to the flat parameter buffer            WRITTEN, every element
+ *   M                                                                                  WRITTEN
+ * The targets carry no gradient.  ku / ki NULL: drawn on the device, keyed by (seed, step, side, row, column), the user
+ * side first.  Rows whose user or item is out of range contribute nothing.  The predictor's products run as 16-row tiles on
+ * v_mfma_f32_16x16x4_f32 with fp32 operands.  No floating-point atomic: the step is bit-reproducible. */
+typedef struct skr_selfcf_step_args {
+    const skr_spmm_plan* plan_a;       /* A [n_users, n_items]; may be NULL if n_layers == 0 */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    int32_t n_users, n_items, dim, n_layers, n;
+    const float* params;               /* the flat parameter buffer */
+    const int32_t* users;              /* [n] */
+    const int32_t* items;              /* [n] */
+    const uint8_t* keep_fu;            /* skr_selfcf_keeps' four arrays; not used if n_layers == 0 */
+    const uint8_t* keep_fi;
+    const uint8_t* keep_bu;
+    const uint8_t* keep_bi;
+    float edge_scale;                  /* float32(1 / (1 - rate)) */
+    const uint8_t* ku;                 /* [n, 64] the user targets' keep flags, or NULL */
+    const uint8_t* ki;                 /* [n, 64] the item targets' keep flags, or NULL */
+    float dropout, reg;
+    uint64_t seed, step;               /* key of the device draws of ku / ki */
+    float* M;                          /* [n_users + n_items, 64] */
+    float* ping[2];                    /* scratch, [n_users + n_items, 64] each; NULL if n_layers < 2 */
+    float* G;                          /* scratch, [n_users + n_items, 64]; not used if n_layers == 0 */
+    float* grad;                       /* the flat gradient buffer */
+    float* loss;                       /* [3] */
+    void* work;                        /* skr_selfcf_workspace(n, n_layers) bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_selfcf_step_args;
+size_t skr_selfcf_workspace(int n, int n_layers);
+int skr_selfcf_step(const skr_selfcf_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_SELFCF_GROUPS launch groups (forward plan runs; batch kernel, predictor
+ * reduction and loss; clear, rank and seg_add; backward plan runs): h_ms[k] (host) = milliseconds of group k; synchronises
+ * the stream (timing tools). */
+#define SKR_SELFCF_GROUPS 4
+int skr_selfcf_step_timed(const skr_selfcf_step_args* args, void* stream, float* h_ms);
+/* Ranking (SelfCF.py:235-241): the score (W u + b).i + u.(W i + b) = u^T (W + W^T) i + <b, i> + <b, u>, so
+ *   d_Q[r] = (W + W^T) M_r for the n_users user rows, d_item_bias[t] = <b, M_(n_users + t)>, d_user_const[r] = <b, M_r>:
+ * skr_eval_fused_topk ranks <d_Q[u], M_i> + d_item_bias[i]; the per-user constant does not move a ranking.
+ * d_pred: the predictor's W and b (SKR_SELFCF_PRED_FLOATS floats). */
+int skr_selfcf_queries(const float* d_pred, const float* d_M, int n_users, int n_items, float* d_Q, float* d_item_bias,
+                       float* d_user_const, void* stream);
 
 #ifdef __cplusplus
 }

@@ -370,6 +370,78 @@ __global__ __launch_bounds__(256) void spmm_reduce_kernel(const int32_t* __restr
     }
 }
 
+// ---- dropped runs (skr_spmm_plan_run_dropped): per-ENTRY keep flags, drawn anew by the caller for every step ---------------
+// Siblings of spmm_rows_kernel / spmm_tasks_kernel, same row / task / reduce structure and the same order of additions: an
+// entry e counts as val[e] * scale when keep[e] != 0 and is SKIPPED otherwise -- its row of X is not gathered.  The kept
+// entries of a block of 64 move to the front in their order (as keep_marked does for marked columns), so a run whose flags
+// are all set adds the same terms in the same order as the plain run.
+__device__ __forceinline__ int compact_kept(bool keep, int lane, int& cl, float& vl) {
+    const unsigned long long b = __ballot(keep);
+    const int kept = __popcll(b);
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    const int dst = keep ? below : kept + (lane - below);
+    cl = __builtin_amdgcn_ds_permute(dst << 2, cl);
+    vl = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(keep ? vl : 0.0f)));
+    return kept;
+}
+
+__global__ __launch_bounds__(ROW_WAVES * 64) void spmm_rows_dropped_kernel(int n_rows, int long_thr, const int64_t* __restrict__ rowptr,
+                                                                           const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                                           const uint8_t* __restrict__ keep, float scale,
+                                                                           const float* __restrict__ X, const skr_spmm_epilogue ep) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int grp = lane >> 4, sub = lane & 15;
+    const float4* X4 = reinterpret_cast<const float4*>(X);
+    const int ld = ep.ld ? ep.ld : D, ld4 = ld >> 2;
+    for (int64_t r = blockIdx.x * ROW_WAVES + wv; r < n_rows; r += static_cast<int64_t>(gridDim.x) * ROW_WAVES) {
+        const int64_t rb = rowptr[r], re = rowptr[r + 1];
+        if (re - rb >= long_thr) continue;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int64_t e = rb; e < re; e += 64) {
+            int m = static_cast<int>(re - e < 64 ? re - e : 64);
+            int cl = col[rb];              // dropped and padding lanes: a valid column, value 0, behind the kept ones
+            float vl = 0.0f;
+            const bool k = lane < m && keep[e + lane] != 0;
+            if (k) { cl = col[e + lane]; vl = val[e + lane] * scale; }
+            m = compact_kept(k, lane, cl, vl);
+            gather_block(X4, cl, vl, m, grp, sub, acc, ld4);
+        }
+        sum_groups(acc);
+        float y[4] = {acc.x, acc.y, acc.z, acc.w};
+        epilogue<4>(ep, y, r, sub, grp == 0);      // a row with nothing kept: y = 0, then the addend
+    }
+}
+
+__global__ __launch_bounds__(ROW_WAVES * 64) void spmm_tasks_dropped_kernel(const int64_t* __restrict__ first_task, int n_long, int n_blocks, int group,
+                                                                            const Task* __restrict__ tasks, const int32_t* __restrict__ col,
+                                                                            const float* __restrict__ val, const uint8_t* __restrict__ keep,
+                                                                            float scale, const float* __restrict__ X, float* __restrict__ part,
+                                                                            int ld4) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int grp = lane >> 4, sub = lane & 15;
+    const float4* X4 = reinterpret_cast<const float4*>(X);
+    const int64_t n_w = static_cast<int64_t>(gridDim.x >> 3) * ROW_WAVES;
+    const int b = group * 8 + (blockIdx.x & 7);
+    if (b >= n_blocks) return;
+    const int64_t t_end = first_task[static_cast<int64_t>(b + 1) * n_long];
+    for (int64_t t = first_task[static_cast<int64_t>(b) * n_long] + (blockIdx.x >> 3) * ROW_WAVES + wv; t < t_end; t += n_w) {
+        const Task tk = tasks[t];
+        const int len = static_cast<int>(tk.len_slot & 255u) + 1;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int e0 = 0; e0 < len; e0 += 64) {
+            int m = len - e0 < 64 ? len - e0 : 64;
+            int cl = col[tk.beg];          // dropped and padding lanes: the task's first column, an address inside the block
+            float vl = 0.0f;
+            const bool k = lane < m && keep[tk.beg + e0 + lane] != 0;
+            if (k) { cl = col[tk.beg + e0 + lane]; vl = val[tk.beg + e0 + lane] * scale; }
+            m = compact_kept(k, lane, cl, vl);
+            gather_block(X4, cl, vl, m, grp, sub, acc, ld4);
+        }
+        sum_groups(acc);
+        if (grp == 0) reinterpret_cast<float4*>(part)[static_cast<int64_t>(tk.part) * 16 + sub] = acc;   // (zeros when nothing was kept)
+    }
+}
+
 // ---- the densest rows: X streamed through LDS -------------------------------------------------------------------------
 // A row of the item side that names 3 .. 80 % of all users gathers most of X anyway -- row by row, 256 bytes at a time, out
 // of L2 at best.  Those rows (at most HOT_V "virtual" rows: a row far heavier than the others is cut into P pieces, piece p
@@ -1029,6 +1101,47 @@ int skr_spmm_plan_run_ex(const skr_spmm_plan* plan, const float* d_X, int dim, c
         }
         hipLaunchKernelGGL(spmm_reduce_kernel, dim3(plan->n_long), dim3(256), 0, st, plan->long_rows, plan->part_ptr, plan->part, ep,
                            d_row_mask, hot_flag);
+        SKR_LAUNCH_CHECK();
+    }
+    return SKR_OK;
+}
+
+int skr_spmm_plan_run_dropped(const skr_spmm_plan* plan, const float* d_X, int dim, const skr_spmm_epilogue* epi, const uint8_t* d_keep,
+                              float scale, void* stream) {
+    SKR_REQUIRE(plan && d_X && epi, "skr_spmm_plan_run_dropped: NULL argument");
+    SKR_REQUIRE(dim == D, "skr_spmm_plan_run_dropped: dim must be 64 (got %d)", dim);
+    const skr_spmm_epilogue ep = *epi;
+    const int ld = ep.ld ? ep.ld : D;
+    SKR_REQUIRE(ep.mode == SKR_EPI_PLAIN, "skr_spmm_plan_run_dropped: only the plain epilogue (got mode %d)", ep.mode);
+    SKR_REQUIRE(ld >= D && ld % 4 == 0, "skr_spmm_plan_run_dropped: the row stride must be a multiple of 4 floats and at least 64 (got %d)", ld);
+    SKR_REQUIRE(ep.Y != d_X, "skr_spmm_plan_run_dropped: in-place propagation is not supported");
+    SKR_REQUIRE(ep.Y || ep.accum, "skr_spmm_plan_run_dropped: the plain epilogue needs Y or accum");
+    SKR_REQUIRE(plan->n_win == 1, "skr_spmm_plan_run_dropped: plans with column windows are not supported");
+    SKR_REQUIRE(d_keep || plan->nnz == 0, "skr_spmm_plan_run_dropped: NULL keep flags");
+    if (plan->n_rows == 0) return SKR_OK;
+    hipStream_t st = skr::as_stream(stream);
+    // the launch shapes of skr_spmm_plan_run_ex (its tuning switches SKR_SPMM_ROWS_WGS / SKR_SPMM_TASK_WGS are honoured)
+    static const int rows_cap = [] { const char* e = getenv("SKR_SPMM_ROWS_WGS"); const int v = e ? atoi(e) : ROWS_WGS_MAX; return v < 256 ? 256 : v; }();
+    static const int task_cap = [] { const char* e = getenv("SKR_SPMM_TASK_WGS"); const int v = e ? atoi(e) : BLK_WGS_PER_XCD; return v < 8 ? 8 : v; }();
+    int64_t wgs = (static_cast<int64_t>(plan->n_rows) + ROW_WAVES - 1) / ROW_WAVES;
+    if (wgs > rows_cap) wgs = rows_cap;
+    int64_t task_wgs = plan->n_blocks > 0 ? (5 * plan->n_tasks / (4 * static_cast<int64_t>(plan->n_blocks)) + ROW_WAVES - 1) / ROW_WAVES : 1;
+    task_wgs = std::min<int64_t>(std::max<int64_t>(task_wgs, 8), task_cap);
+    const dim3 rgrid(static_cast<unsigned>(wgs)), blk(ROW_WAVES * 64), tgrid(static_cast<unsigned>(8 * task_wgs));
+    hipLaunchKernelGGL(spmm_rows_dropped_kernel, rgrid, blk, 0, st, plan->n_rows, plan->long_thr, plan->rowptr, plan->col, plan->val, d_keep,
+                       scale, d_X, ep);
+    SKR_LAUNCH_CHECK();
+    // every long row, the plan's hot rows included, goes through the task path: their block-major copies hold no flags
+    if (plan->n_long > 0) {
+        if (plan->n_tasks > 0) {
+            const int groups = (plan->n_blocks + 7) / 8;
+            for (int g = 0; g < groups; ++g)
+                hipLaunchKernelGGL(spmm_tasks_dropped_kernel, tgrid, blk, 0, st, plan->first_task, plan->n_long, plan->n_blocks, g, plan->tasks,
+                                   plan->col, plan->val, d_keep, scale, d_X, plan->part, ld >> 2);
+            SKR_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(spmm_reduce_kernel, dim3(plan->n_long), dim3(256), 0, st, plan->long_rows, plan->part_ptr, plan->part, ep, nullptr,
+                           nullptr);
         SKR_LAUNCH_CHECK();
     }
     return SKR_OK;

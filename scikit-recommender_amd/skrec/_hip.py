@@ -138,6 +138,12 @@ SIGNATURES = {
     "skr_dens_workspace": (sz, [i32, i32]),
     "skr_dens_step": (i32, [vp, vp]),
     "skr_dens_step_timed": (i32, [vp, vp, vp]),
+    "skr_spmm_plan_run_dropped": (i32, [vp, vp, i32, vp, vp, f32, vp]),
+    "skr_selfcf_keeps": (i32, [vp, i64, vp, vp, f32, u64, u64, vp, vp, vp, vp, vp]),
+    "skr_selfcf_workspace": (sz, [i32, i32]),
+    "skr_selfcf_step": (i32, [vp, vp]),
+    "skr_selfcf_step_timed": (i32, [vp, vp, vp]),
+    "skr_selfcf_queries": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
 }
 
 
@@ -167,6 +173,15 @@ class DensStepArgs(C.Structure):
                 ("hop", vp * 3), ("G", vp * 4), ("ping", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
 
 
+class SelfCFStepArgs(C.Structure):
+    """skr_selfcf_step_args (include/skrec_hip.h): the parameters, the batch, the keep flags and the scratch of one SelfCF step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32),
+                ("n_layers", C.c_int32), ("n", C.c_int32), ("params", vp), ("users", vp), ("items", vp), ("keep_fu", vp),
+                ("keep_fi", vp), ("keep_bu", vp), ("keep_bi", vp), ("edge_scale", C.c_float), ("ku", vp), ("ki", vp),
+                ("dropout", C.c_float), ("reg", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("M", vp), ("ping", vp * 2),
+                ("G", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -178,6 +193,8 @@ SKR_CDAE_MAX_BATCH = 1024      # skr_cdae_step: users of a batch
 SKR_CDAE_IDENTITY, SKR_CDAE_SIGMOID, SKR_CDAE_LAUNCHES = 0, 1, 3
 SKR_LIGHTGCL_MAX_QUERIES, SKR_LIGHTGCL_MAX_Q, SKR_LIGHTGCL_GROUPS = 4096, 16, 8   # skr_lightgcl_cl / _step limits
 SKR_DENS_MAX_BATCH, SKR_DENS_MAX_NEGS, SKR_DENS_MAX_HOPS, SKR_DENS_GROUPS = 2048, 16, 3, 6   # skr_dens_step limits
+SKR_SELFCF_MAX_BATCH, SKR_SELFCF_MAX_LAYERS, SKR_SELFCF_GROUPS = 2048, 4, 4   # skr_selfcf_step limits
+SKR_SELFCF_PRED_FLOATS = 64 * 64 + 64    # the predictor's block of the flat parameter buffer: W [64 out][64 in], then b [64]
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64      # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 

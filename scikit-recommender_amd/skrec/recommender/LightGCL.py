@@ -120,6 +120,28 @@ def normalized_adjacency(rowptr, col, num_users, num_items):
     return A, At
 
 
+def selfcf_adjacency(rowptr, col, num_users, num_items):
+    """(A, A^T, perm) from the binary train CSR in HBM with SelfCF's normalisation (SelfCF.py:118-123): the float32 of
+    (rowdeg + 1e-7)^-0.5 * (coldeg + 1e-7)^-0.5, powers and product in float64, computed on the device.  ``perm`` (int32
+    [nnz]): the position in A^T's entry order of entry e of A's -- the inverse of the sort that builds the transpose"""
+    dev = rowptr.device
+    rowdeg = (rowptr[1:] - rowptr[:-1])
+    rows = torch.repeat_interleave(torch.arange(num_users, dtype=torch.int64, device=dev), rowdeg)
+    cols = col.to(torch.int64)
+    coldeg = torch.bincount(cols, minlength=num_items)
+    du = (rowdeg.to(torch.float64) + 1e-7).pow(-0.5)
+    di = (coldeg.to(torch.float64) + 1e-7).pow(-0.5)
+    val = (du[rows] * di[cols]).to(torch.float32)
+    A = _device_csr((num_users, num_items), rowptr, col, val)
+    order = torch.argsort(cols * num_users + rows)           # the transpose: by column, then by row
+    rp_t = torch.zeros(num_items + 1, dtype=torch.int64, device=dev)
+    rp_t[1:] = torch.cumsum(coldeg, 0)
+    At = _device_csr((num_items, num_users), rp_t, rows[order].to(torch.int32), val[order])
+    perm = torch.empty(order.numel(), dtype=torch.int32, device=dev)
+    perm[order] = torch.arange(order.numel(), dtype=torch.int32, device=dev)
+    return A, At, perm
+
+
 def _run_plan(mat, X, Y=None, addend=None, accum=None, accum_base=None):
     ep = _hip.SpmmEpilogue()
     ep.mode = _hip.EPI_PLAIN
