@@ -28,6 +28,12 @@ constexpr int G_HMAX = 128;
 constexpr int G_CH = 32;      // weights in flight per thread in the forward kernel (SKR tuning: 16 / 32 / 64)
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// sigmoid(x) and 1 - sigmoid(x) = sigmoid(-x), EACH to its own relative precision (1 - s loses everything once s rounds to 1)
+__device__ __forceinline__ void sigmoid_pair(float x, float& s, float& n) {
+    const float e = expf(-fabsf(x)), big = 1.0f / (1.0f + e), small = e * big;
+    s = x >= 0.0f ? big : small;
+    n = x >= 0.0f ? small : big;
+}
 __device__ __forceinline__ float hidden_act(float x, int act) { return act == 0 ? tanhf(x) : fmaxf(x, 0.0f); }
 // derivative of the hidden activation expressed through its OUTPUT c
 __device__ __forceinline__ float hidden_act_grad(float c, int act) { return act == 0 ? 1.0f - c * c : (c > 0.0f ? 1.0f : 0.0f); }
@@ -423,6 +429,10 @@ __global__ __launch_bounds__(T) void gru_bwd_rows_kernel(GruIn g, const float* _
         hh[r][j] = vh;
         rr[r][j] = vr;
     }
+    // H = 32: the products below run over 64 lanes, and lanes 32 .. 63 meet a zero WEIGHT -- their dc~ operand has to be a
+    // number too: whatever an earlier kernel left in LDS may be a NaN or an infinity, and 0 * NaN poisons the whole reduction
+    if constexpr (H < 64)
+        for (int idx = tid; idx < ROWS * (64 - H); idx += T) dcp[idx / (64 - H)][H + idx % (64 - H)] = 0.0f;
     __syncthreads();
     const int lane = tid & 63, wv = tid >> 6;
     constexpr int QN = 16 / ROWS;                      // weight rows per reduction group (ROWS is 4 or 16)
@@ -582,6 +592,9 @@ __global__ __launch_bounds__(G_T) void gru_bwd_weights_kernel(GruIn g, const flo
 //             dL/dl_b = -[ sum_y sig_y (1 - sig_y) s_y ] / (P + eps)
 //   top1_max: q_y = sig(l_y - l_b) + sig(l_y^2), L = sum s_y q_y
 //             dL/dl_y = s_y [ sig'(l_y - l_b) + 2 l_y sig'(l_y^2) ] + s_y (q_y - L) ;  dL/dl_b = -sum_y s_y sig'(l_y - l_b)
+//             carried as p_y = 2 - q_y = sig(l_b - l_y) + sig(-l_y^2) and 2 - L = sum s_y p_y, q_y - L = (2 - L) - p_y, sig' =
+//             sig(x) sig(-x): with large logits every q_y and L sit next to 2, where q_y - L is a difference of two roundings
+//             of 2 (a relative error of 1e-3 in dlogits at |logit| ~ 80) while the p_y keep their own precision
 // ------------------------------------------------------------------------------------------------
 constexpr int L_NY_MAX = 8192;
 
@@ -687,9 +700,11 @@ __global__ __launch_bounds__(G_T) void session_rowloss_kernel(int B, int n_y, in
             a1 += l * l * s;
             a2 += sg * (1.0f - sg) * s;
         } else {
-            const float s1 = sigmoidf_(l - pos), s2 = sigmoidf_(l * l);
-            a0 += (s1 + s2) * s;
-            a2 += s1 * (1.0f - s1) * s;
+            float s1, n1, s2, n2;
+            sigmoid_pair(l - pos, s1, n1);
+            sigmoid_pair(l * l, s2, n2);
+            a0 += (n1 + n2) * s;          // 2 - L
+            a2 += s1 * n1 * s;
         }
     }
     a0 = block_reduce(a0, red, false);
@@ -701,7 +716,7 @@ __global__ __launch_bounds__(G_T) void session_rowloss_kernel(int B, int n_y, in
         lb = -logf(a0 + 1e-24f) + bpr_reg * a1;
         gpos = -a2 / (a0 + 1e-24f);
     } else {
-        lb = a0;
+        lb = 2.0f - a0;
         gpos = -a2;
     }
     if (tid == 0) atomicAdd(loss, lb * invB);
@@ -718,8 +733,10 @@ __global__ __launch_bounds__(G_T) void session_rowloss_kernel(int B, int n_y, in
                 const float dR = 2.0f * l * s + s * (l * l - a1);
                 gy = -dP / (a0 + 1e-24f) + bpr_reg * dR;
             } else {
-                const float s1 = sigmoidf_(l - pos), s2 = sigmoidf_(l * l);
-                gy = s * (s1 * (1.0f - s1) + 2.0f * l * s2 * (1.0f - s2)) + s * ((s1 + s2) - a0);
+                float s1, n1, s2, n2;
+                sigmoid_pair(l - pos, s1, n1);
+                sigmoid_pair(l * l, s2, n2);
+                gy = s * (s1 * n1 + 2.0f * l * s2 * n2) + s * (a0 - (n1 + n2));
             }
         }
         row[y] = gy * invB * final_act_grad(l, fact);

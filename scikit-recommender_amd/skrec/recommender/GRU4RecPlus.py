@@ -71,6 +71,18 @@ class GRU4RecPlusConfig(ModelConfig):
         assert isinstance(self.early_stop, int)
 
 
+def row_block_ids(o, idx, d):
+    """int64 [k, n * c]: the 64-float blocks that rows ``idx`` [k, n] of a table of ``d``-float rows overlap, the table
+    starting at block ``o`` -- every block from (idx * d) >> 6 through (idx * d + d - 1) >> 6.  c is the largest number of
+    blocks a row can overlap (a row starts on a multiple of gcd(d, 64): 1 for d = 32 or 64, 2 for 128 or 48, 3 for 100); a
+    row that overlaps fewer repeats its last block, so that the count per step is fixed.  Runs on idx's device (CPU too)."""
+    start = idx.long() * d
+    last = (start + d - 1) >> 6
+    c = ((64 - int(np.gcd(d, 64)) + d - 1) >> 6) + 1
+    blocks = torch.minimum((start >> 6).unsqueeze(2) + torch.arange(c, device=idx.device), last.unsqueeze(2))
+    return o + blocks.reshape(idx.shape[0], -1)
+
+
 class SessionGRU(object):
     """Device state + one training / inference step of the GRU4RecPlus graph.  Parameters live in ONE flat
     buffer [E_in | E_out | b_out | (Wg, bg, Wc, bc) per layer], every section starting on a 64-float block,
@@ -145,12 +157,9 @@ class SessionGRU(object):
         o_in, o_out, o_b, o_cells = (o // 64 for o in self._offs[:4])
         hn = self.hids[-1]
 
-        def rows(o, idx, d):
-            first = o + ((idx.long() * d) >> 6)
-            c = max(1, d // 64)
-            return (first.unsqueeze(2) + torch.arange(c, device=dev)).reshape(k, -1)
         cells = torch.arange(o_cells, (self.flat.numel() + 63) // 64, device=dev).expand(k, -1)
-        return torch.cat([rows(o_in, xs, self.in_dim), rows(o_out, ys, hn), o_b + (ys.long() >> 6), cells], dim=1).int().contiguous()
+        return torch.cat([row_block_ids(o_in, xs, self.in_dim), row_block_ids(o_out, ys, hn), o_b + (ys.long() >> 6), cells],
+                         dim=1).int().contiguous()
 
     def begin_block(self, xs, ys):
         """xs int32 [k, b], ys int32 [k, b + n_sample] (device): the next k calls of train_step will be given exactly

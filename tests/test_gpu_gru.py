@@ -233,7 +233,7 @@ def test_training_trajectory_matches_oracle(layers, loss, fact, act, reg):
             _close(a.cpu().numpy(), w.detach().numpy(), 2e-4, 2e-6)
 
 
-@pytest.mark.parametrize("layers,in_dim", [([128], 128), ([64, 32], 32)])
+@pytest.mark.parametrize("layers,in_dim", [([128], 128), ([64, 32], 32), ([64], 48), ([32], 100)])
 def test_blocked_adam_steps_are_bit_identical_to_dense_steps(layers, in_dim):
     """SessionGRU.begin_block: the TF-arithmetic dense Adam blocked over k steps (cold rows in one pass on a side stream,
     the step's rows by the hot launch) == one dense skr_adam_step_tf per step, BIT FOR BIT -- every parameter, both
