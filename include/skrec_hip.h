@@ -604,6 +604,15 @@ int skr_fused_census(uint64_t* h_counts, int n_counts, int reset);
  * [3] / [4] controls that took the general / the scaling-free form ([4] must be 0).  (Test hook; synchronises the stream.) */
 int skr_selftest_grad_math(uint64_t n_tuples, float lr, float beta1, float beta2, float eps, int64_t step_t0, int k, int tf,
                            int run_len, uint64_t* h_counts5, void* stream);
+/* skr_selftest_step_chain: the catch-up of skr_bpr_fused_step's kernel -- the block's per-step scalars held in lanes and read
+ * with v_readlane_b32, the reciprocal of the second bias correction refined once per step (chain_advance, adam_math.h) --
+ * against the forms skr_selftest_grad_math tests, bits of p, m and v, on the same hashed tuples and controls,
+ * every wavefront at step s_from of the block: with_grad != 0: the gradient update s_from and the zero-gradient updates
+ * behind it, otherwise zero-gradient updates alone, up to step s_from + run_len (as far as the block goes).  h_counts5 as
+ * there: [2] counts the non-control wavefronts on the scaling-free form, [3] / [4] the controls on the general / the
+ * scaling-free form.  (Test hook; synchronises the stream.) */
+int skr_selftest_step_chain(uint64_t n_tuples, float lr, float beta1, float beta2, float eps, int64_t step_t0, int k, int s_from,
+                            int run_len, int with_grad, uint64_t* h_counts5, void* stream);
 
 /* Sparse exchange of a replicated table's gradient between ranks (no reference counterpart -- the
  * reference is single-process).  A BPR step touches at most 2*batch item rows, so instead of all-reducing the

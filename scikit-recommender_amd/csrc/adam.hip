@@ -302,6 +302,78 @@ __global__ __launch_bounds__(256) void selftest_grad_math_kernel(uint64_t n_grou
     if (ctl_fast) atomicAdd(&out[4], ctl_fast);
 }
 
+// skr_selftest_step_chain: the step kernel's catch-up on the lane tables (chain_advance, adam_math.h: the very function the
+// kernel inlines) against adam_grad_run / adam_zero_run, bits of p, m and v.  The generator and the controls of
+// selftest_grad_math_kernel; every wavefront at step s_from of the block: with_grad: the gradient update s_from and the
+// zero-gradient updates behind it, otherwise the zero-gradient updates alone, up to s_from + run_len (as far as the block goes)
+__global__ __launch_bounds__(256) void selftest_step_chain_kernel(uint64_t n_groups, AdamBlockArgs a, int s_from, int run_len,
+                                                                  int with_grad, unsigned long long* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_waves = static_cast<uint64_t>(gridDim.x) * 4;
+    const AdamChainArgs ca = adam_chain_args(a);
+    unsigned long long bad = 0, fast = 0, ctl_general = 0, ctl_fast = 0, tested = 0;
+    for (uint64_t gi = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); gi < n_groups; gi += n_waves) {
+        auto mix = [](uint64_t h) {      // splitmix64
+            h *= 0x9E3779B97F4A7C15ull;
+            h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+            return h ^ (h >> 31);
+        };
+        const uint64_t h1 = mix(2 * (gi * 64 + lane) + 1), h2 = mix(2 * (gi * 64 + lane) + 2);
+        auto make = [](uint32_t h, int e_lo, int e_n) {      // random sign and mantissa, exponent in [e_lo, e_lo + e_n)
+            return __uint_as_float((h & 0x807fffffu) | ((127 + e_lo + (h >> 23 & 0xff) % e_n) << 23));
+        };
+        float p = make(static_cast<uint32_t>(h1), -20, 30), m = make(static_cast<uint32_t>(h1 >> 32), -40, 50);
+        float v = fabsf(make(static_cast<uint32_t>(h2), -60, 70)), g = make(static_cast<uint32_t>(h2 >> 32), -30, 36);
+        {
+            const int de = static_cast<int>(__float_as_uint(g) >> 23 & 0xff) - static_cast<int>(__float_as_uint(m) >> 23 & 0xff);
+            if (de >= 1 && de <= 5) g = copysignf(g, m);
+        }
+        const int kind = static_cast<int>(gi & 15);
+        const bool control = kind == 7 || kind == 3;
+        if (kind == 3) {
+            if ((lane & 7) == 1) {
+                m = 0.0f, v = 0.0f, g = (lane & 8) ? -0.0f : 0.0f;
+                if (lane & 16) p = (lane & 32) ? -0.0f : 0.0f;
+            } else if ((lane & 7) == 2) {
+                m = copysignf(0x1p-95f, m), g = (lane & 8) ? -0.0f : 0.0f;
+                v = 0x1p-20f * (1.0f + 0x1p-3f * (lane >> 3));
+                p = copysignf(fmaxf(fabsf(p), 0x1p-10f), p);
+            }
+        } else if (kind == 7 && lane == 5) {
+            switch (static_cast<int>(gi >> 4 & 3)) {
+                case 0: m = -0.0f, v = 0.0f, g = 0.0f, p = 0.0f; break;
+                case 1: m = 0.0f, v = 0.0f, g = 0.0f, p = __uint_as_float(0x7fc00001u); break;
+                case 2: v = __uint_as_float(0x7f800000u); break;
+                default: m = __uint_as_float(0x00000123u), g = 0.0f, p = 0x1p-70f; break;
+            }
+        }
+        const int s_to = s_from + run_len < a.k ? s_from + run_len : a.k;
+        float wp = p, wm = m, wv = v;
+        if (with_grad)
+            adam_grad_run(wp, g, wm, wv, a, s_from, s_to, FC_END);
+        else
+            adam_zero_run(wp, wm, wv, a, s_from, s_to, FC_END);
+        const AdamRowState r = chain_advance(p, g, m, v, with_grad ? s_from + 1 : 0, s_from, s_to, FC_END, ca);
+        bad += (__float_as_uint(r.p) != __float_as_uint(wp)) || (__float_as_uint(r.m) != __float_as_uint(wm)) ||
+               (__float_as_uint(r.v) != __float_as_uint(wv));
+        tested += 1;
+        if (lane == 0) {
+            if (control) {
+                ctl_fast += r.cls == FC_ORD;
+                ctl_general += r.cls == FC_GENERAL;
+            } else {
+                fast += r.cls == FC_ORD;
+            }
+        }
+    }
+    if (tested) atomicAdd(&out[0], tested);
+    if (bad) atomicAdd(&out[1], bad);
+    if (fast) atomicAdd(&out[2], fast);
+    if (ctl_general) atomicAdd(&out[3], ctl_general);
+    if (ctl_fast) atomicAdd(&out[4], ctl_fast);
+}
+
 // cold pass, one wavefront per 64-float block (= one embedding row), with a cheap exact path for rows AT REST.
 //
 // A zero-gradient update is p += (nss*m') / (sqrt(v')/bc2 + eps) with m' = m + c1*(0 - m), v' = v*b2.  A row that
@@ -804,6 +876,30 @@ int skr_selftest_grad_math(uint64_t n_tuples, float lr, float beta1, float beta2
     SKR_HIP(hipMalloc(&d_out, 5 * sizeof(unsigned long long)));
     SKR_HIP(hipMemsetAsync(d_out, 0, 5 * sizeof(unsigned long long), skr::as_stream(stream)));
     hipLaunchKernelGGL(selftest_grad_math_kernel, dim3(256 * 4), dim3(256), 0, skr::as_stream(stream), n_tuples / 64, a, run_len, d_out);
+    SKR_LAUNCH_CHECK();
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    SKR_HIP(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, skr::as_stream(stream)));
+    SKR_HIP(hipStreamSynchronize(skr::as_stream(stream)));
+    (void)hipFree(d_out);
+    for (int q = 0; q < 5; ++q) h_counts5[q] = h[q];
+    return SKR_OK;
+}
+
+int skr_selftest_step_chain(uint64_t n_tuples, float lr, float beta1, float beta2, float eps, int64_t step_t0, int k, int s_from,
+                            int run_len, int with_grad, uint64_t* h_counts5, void* stream) {
+    SKR_REQUIRE(h_counts5, "skr_selftest_step_chain: NULL argument");
+    SKR_REQUIRE(step_t0 >= 0 && k >= 1 && k <= AB_KMAX && s_from >= 0 && s_from < k && run_len >= 1,
+                "skr_selftest_step_chain: need 0 <= s_from < k <= %d, run_len >= 1", AB_KMAX);
+    AdamBlockArgs a{};
+    adam_shared_fields(a, beta1, beta2, eps);
+    a.k = k;
+    adam_block_scalars(a, lr, beta1, beta2, step_t0, k, false);
+    adam_block_thresholds(a, lr, beta1, beta2, eps, k);
+    unsigned long long* d_out = nullptr;
+    SKR_HIP(hipMalloc(&d_out, 5 * sizeof(unsigned long long)));
+    SKR_HIP(hipMemsetAsync(d_out, 0, 5 * sizeof(unsigned long long), skr::as_stream(stream)));
+    hipLaunchKernelGGL(selftest_step_chain_kernel, dim3(256 * 4), dim3(256), 0, skr::as_stream(stream), n_tuples / 64, a, s_from,
+                       run_len, with_grad, d_out);
     SKR_LAUNCH_CHECK();
     unsigned long long h[5] = {0, 0, 0, 0, 0};
     SKR_HIP(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, skr::as_stream(stream)));

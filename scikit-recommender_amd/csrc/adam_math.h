@@ -5,6 +5,7 @@
 #pragma once
 #include "skr_common.h"
 
+#include <cassert>
 #include <cmath>
 
 namespace skr {
@@ -56,6 +57,7 @@ struct AdamBlockArgs {
     float fast_vlo, fast_mlo, fast_mhi;
     unsigned long long* stats;   // optional census: the cold pass's (SKR_COLD_STATS=1: blocks at rest / ordinary / general) or,
                                  // in the fused step's launches, theirs (SKR_FUSED_STATS=1: FC_* below)
+    int first_unit;              // the smallest s with bc2_sqrt[s] == 1.0f, k if there is none (from there on it stays 1.0f)
 };
 
 // Square root and division for ORDINARY MAGNITUDES, bit-identical to sqrtf(x) and n / d as compiled under
@@ -270,6 +272,178 @@ __device__ __forceinline__ void adam_pair_run(f32x2& p, f32x2& m, f32x2& v, cons
     }
 }
 
+// ---- the lazy rows' updates with the block's per-step scalars held in LANES (bpr_fused_step_kernel) ------------------------
+// The forms above read a.neg_step_size[s], a.bc2_sqrt[s] and a.nss_bound[s] from the kernel-argument segment: a scalar load
+// and a full wait each time, on the critical path of the one wavefront a SIMD holds.  Here lane l of four registers holds
+// step l's scalars (AB_KMAX is the wavefront size), loaded once per wavefront; a step's scalar is then one v_readlane_b32.
+// The fourth register holds the refined reciprocal of bc2_sqrt[l] -- the first three instructions of div_ordinary(x, bc2),
+// which depend on the step only -- so that a division by bc2 starts at q = n * r (div_ordinary_r).  first_unit replaces the
+// comparisons of bc2_sqrt with 1.0f.  Same operations on the same values as adam_grad_run / adam_zero_run
+// (skr_selftest_step_chain compares the two, bits of p, m and v).
+static_assert(AB_KMAX == 64, "the lane tables hold one step per lane of a 64-wide wavefront");
+
+// div_ordinary with the refined reciprocal r of d handed in: r = rcp(d); r = fma(fma(-d, r, 1), r, r)
+__device__ __forceinline__ float div_ordinary_r(float n, float d, float r) {
+    float q = n * r;
+    float t = __builtin_fmaf(-d, q, n);
+    q = __builtin_fmaf(t, r, q);
+    t = __builtin_fmaf(-d, q, n);
+    return __builtin_fmaf(t, r, q);
+}
+
+// what the chain reads: AdamBlockArgs' scalars (in scalar registers) and the four lane tables
+struct AdamChainArgs {
+    float one_minus_b1, b2, one_minus_b2, eps;
+    float rest_eps, rest_b2k, fast_vlo, fast_mlo, fast_mhi;
+    int first_unit;
+    unsigned long long* stats;
+    float t_nss, t_bc2, t_bound, t_rbc2;      // lane l: neg_step_size[l], bc2_sqrt[l], nss_bound[l], refined 1 / bc2_sqrt[l]
+};
+
+// (lanes k .. 63 hold the arrays' zero padding and what its reciprocal gives: no step reads them)
+__device__ __forceinline__ AdamChainArgs adam_chain_args(const AdamBlockArgs& a) {
+    const int l = threadIdx.x & 63;
+    AdamChainArgs c;
+    c.one_minus_b1 = a.one_minus_b1, c.b2 = a.b2, c.one_minus_b2 = a.one_minus_b2, c.eps = a.eps;
+    c.rest_eps = a.rest_eps, c.rest_b2k = a.rest_b2k, c.fast_vlo = a.fast_vlo, c.fast_mlo = a.fast_mlo, c.fast_mhi = a.fast_mhi;
+    c.first_unit = a.first_unit;
+    c.stats = a.stats;
+    c.t_nss = a.neg_step_size[l], c.t_bc2 = a.bc2_sqrt[l], c.t_bound = a.nss_bound[l];
+    const float r = __builtin_amdgcn_rcpf(c.t_bc2);
+    c.t_rbc2 = __builtin_fmaf(__builtin_fmaf(-c.t_bc2, r, 1.0f), r, r);
+    return c;
+}
+
+// step s's entry of a lane table (s is wave-uniform)
+__device__ __forceinline__ float lane_scalar(float table, int s) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(table), s));
+}
+
+// lane_at_rest / lane_ordinary / fused_count on the chain's copy of the thresholds: the same tests
+__device__ __forceinline__ bool lane_at_rest(float pp, float mm, float vv, float nss0, const AdamChainArgs& c) {
+    const float ap = fabsf(pp), n0 = nss0 * fabsf(mm);
+    const float r = ap * 0x1p-29f;
+    const float bound = (r * r) * (vv * c.rest_b2k);
+    const bool small = n0 < ap * c.rest_eps || (n0 * n0 < bound && bound >= 0x1p-120f);
+    return __float_as_uint(vv) <= 0x7f800000u && ap >= 0x1p-60f && small;
+}
+
+__device__ __forceinline__ bool lane_ordinary(float mm, float vv, const AdamChainArgs& c) {
+    const float am = fabsf(mm);
+    return vv >= c.fast_vlo && vv <= 0x1p20f && am >= c.fast_mlo && am <= c.fast_mhi;
+}
+
+__device__ __forceinline__ void fused_count(const AdamChainArgs& c, int ck, int kind, int cls) {
+    if (c.stats && (threadIdx.x & 63) == 0) atomicAdd(&c.stats[8 * ck + 4 * kind + cls], 1ull);
+}
+
+// adam_quot_ordinary with step s's scalars from the lane tables
+template <bool UNIT_BC2>
+__device__ __forceinline__ float chain_quot_ordinary(float m, float v, const AdamChainArgs& c, int s) {
+    float sq = sqrt_ordinary(v);
+    if (!UNIT_BC2) sq = div_ordinary_r(sq, lane_scalar(c.t_bc2, s), lane_scalar(c.t_rbc2, s));
+    return div_ordinary(lane_scalar(c.t_nss, s) * m, sq + c.eps);
+}
+
+// ordinary_run: four chains side by side, then the rest one by one
+template <bool UNIT_BC2>
+__device__ __forceinline__ void chain_ordinary_run(float& p, float& m, float& v, const AdamChainArgs& c, int& s, int s_to, bool& updated) {
+    for (; s + 4 <= s_to; s += 4) {
+        float ms[4], vs[4], q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (u > 0 || !updated) {
+                m = m + c.one_minus_b1 * (0.0f - m);
+                v = v * c.b2;
+            }
+            ms[u] = m;
+            vs[u] = v;
+        }
+        updated = false;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = chain_quot_ordinary<UNIT_BC2>(ms[u], vs[u], c, s + u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p = p + q[u];
+    }
+    for (; s < s_to; ++s) {
+        if (!updated) {
+            m = m + c.one_minus_b1 * (0.0f - m);
+            v = v * c.b2;
+        }
+        updated = false;
+        p = p + chain_quot_ordinary<UNIT_BC2>(m, v, c, s);
+    }
+}
+
+// fast_run: the updates below first_unit on the non-unit form, the others on the unit form (a run is all of one kind
+// except, once, around step 16 600: then the first loop hands over to the second where bc2_sqrt turns 1.0f)
+__device__ __forceinline__ void chain_fast_run(float& p, float& m, float& v, const AdamChainArgs& c, int s, int s_to, bool updated) {
+    chain_ordinary_run<false>(p, m, v, c, s, s_to < c.first_unit ? s_to : c.first_unit, updated);
+    chain_ordinary_run<true>(p, m, v, c, s, s_to, updated);
+}
+
+// one update's general quotient from the updated moments (the last line of adam_elem / adam_elem_unit_bc2)
+__device__ __forceinline__ float chain_quot_general(float m, float v, const AdamChainArgs& c, int s) {
+    const float nss = lane_scalar(c.t_nss, s), bc2 = lane_scalar(c.t_bc2, s);
+    return s >= c.first_unit ? adam_quot<true>(m, v, nss, bc2, c.eps) : adam_quot<false>(m, v, nss, bc2, c.eps);
+}
+
+// adam_zero_run.  Returns the class the wavefront took (FC_REST / FC_ORD / FC_GENERAL), -1 for an empty run
+__device__ __forceinline__ int chain_zero_run(float& p, float& m, float& v, const AdamChainArgs& c, int s, int s_to, int ck) {
+    if (s >= s_to) return -1;
+    if (__builtin_amdgcn_ballot_w64(!lane_at_rest(p, m, v, lane_scalar(c.t_bound, s), c)) == 0) {
+        fused_count(c, ck, FC_RUN, FC_REST);
+        for (; s < s_to; ++s) {
+            m = m + c.one_minus_b1 * (0.0f - m);
+            v = v * c.b2;
+        }
+        return FC_REST;
+    }
+    if (__builtin_amdgcn_ballot_w64(!lane_ordinary(m, v, c)) == 0) {
+        fused_count(c, ck, FC_RUN, FC_ORD);
+        chain_fast_run(p, m, v, c, s, s_to, false);
+        return FC_ORD;
+    }
+    fused_count(c, ck, FC_RUN, FC_GENERAL);
+    for (; s < s_to; ++s) {
+        adam_moments(0.0f, m, v, c);
+        p = p + chain_quot_general(m, v, c, s);
+    }
+    return FC_GENERAL;
+}
+
+// adam_grad_run.  Returns FC_ORD when the wavefront took the scaling-free evaluation, FC_GENERAL otherwise
+__device__ __forceinline__ int chain_grad_run(float& p, float g, float& m, float& v, const AdamChainArgs& c, int s, int s_to, int ck) {
+    adam_moments(g, m, v, c);
+    if (__builtin_amdgcn_ballot_w64(!lane_ordinary(m, v, c)) == 0) {
+        fused_count(c, ck, FC_GRAD, FC_ORD);
+        if (s + 1 < s_to) fused_count(c, ck, FC_RUN, FC_ORD);
+        chain_fast_run(p, m, v, c, s, s_to, true);
+        return FC_ORD;
+    }
+    fused_count(c, ck, FC_GRAD, FC_GENERAL);
+    p = p + chain_quot_general(m, v, c, s);
+    chain_zero_run(p, m, v, c, s + 1, s_to, ck);
+    return FC_GENERAL;
+}
+
+// fused_advance (bpr_fused.hip) on the lane tables: prev1 > 0: index prev1 - 1 with gradient g, then the zero-gradient indices
+// [prev1, s_to);  prev1 == 0: the zero-gradient indices [s_from, s_to) only
+struct AdamRowState {
+    float p, m, v;
+    int cls;      // what chain_grad_run / chain_zero_run returned
+};
+
+__device__ __forceinline__ AdamRowState chain_advance(float p, float g, float m, float v, int prev1, int s_from, int s_to, int ck,
+                                                      const AdamChainArgs& c) {
+    AdamRowState r{p, m, v, -1};
+    if (prev1 > 0)
+        r.cls = chain_grad_run(r.p, g, r.m, r.v, c, prev1 - 1, s_to, ck);
+    else
+        r.cls = chain_zero_run(r.p, r.m, r.v, c, s_from, s_to, ck);
+    return r;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------
 // SKR_COLD_STATS=1: the device census of how the cold passes sorted their blocks, or NULL (defined in adam.hip)
 __attribute__((visibility("hidden"))) unsigned long long* cold_stats_buffer();
@@ -308,6 +482,13 @@ static inline void adam_block_scalars(AdamBlockArgs& a, float lr, float beta1, f
     for (int s = k - 1; s >= 0; --s) {
         mx = std::fmax(mx, std::fabs(a.neg_step_size[s]));
         a.nss_bound[s] = mx;
+    }
+    // sqrt(1 - beta2^t) rises with t and stays at 1.0f once it gets there (TF's is 1.0f throughout): the forms that choose
+    // between the unit and the non-unit quotient by `s >= first_unit` rely on it
+    a.first_unit = k;
+    for (int s = 0; s < k; ++s) {
+        if (a.bc2_sqrt[s] == 1.0f && a.first_unit == k) a.first_unit = s;
+        assert((s >= a.first_unit) == (a.bc2_sqrt[s] == 1.0f) && "bc2_sqrt left 1.0f again");
     }
 }
 

@@ -75,6 +75,8 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
     // 7 and more: the step kernel finds no room, 21.5 us)
     if (!(dbg & 16)) __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // the block's per-step scalars, one step per lane (adam_math.h): loaded once, ahead of the ids, and read with v_readlane
+    const AdamChainArgs ca = adam_chain_args(a);
     float acc_loss = 0.0f, acc_l2 = 0.0f;
     for (int b = blockIdx.x * BPR_WAVES + wv; b < n; b += gridDim.x * BPR_WAVES) {
         const int64_t u = u_ids[b], i = i_ids[b], j = j_ids[b];
@@ -119,7 +121,9 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 const int prev1 = (mt[r] >> 24) & 0x7f;
-                fused_advance(row[r], prev1, from[r], s_now, a, r < 3 ? FC_STEP_ROW : FC_STEP_BIAS);
+                const AdamRowState o = chain_advance(row[r].p, row[r].g, row[r].m, row[r].v, prev1, from[r], s_now,
+                                                     r < 3 ? FC_STEP_ROW : FC_STEP_BIAS, ca);
+                row[r].p = o.p, row[r].m = o.m, row[r].v = o.v;
             }
         }
         if (!(dbg & 4)) {

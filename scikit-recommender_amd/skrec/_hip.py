@@ -67,6 +67,7 @@ SIGNATURES = {
     "skr_selftest_cold_math": (i32, [u64, C.POINTER(u64), vp]),
     "skr_fused_census": (i32, [C.POINTER(u64), i32, i32]),
     "skr_selftest_grad_math": (i32, [u64, f32, f32, f32, f32, i64, i32, i32, i32, C.POINTER(u64), vp]),
+    "skr_selftest_step_chain": (i32, [u64, f32, f32, f32, f32, i64, i32, i32, i32, i32, C.POINTER(u64), vp]),
     "skr_pack_grad_rows": (i32, [vp, i32, vp, vp, i32, vp, vp]),
     "skr_unpack_grad_rows": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
     "skr_unpack_grad_rows_sorted": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
