@@ -52,6 +52,9 @@ __device__ __forceinline__ void fused_advance(FusedRow& r, int prev1, int s_from
         adam_zero_run(r.p, r.m, r.v, a, s_from, s_to, ck);
 }
 
+// an address put together from two scalars: in the global address space by its type, so that the load is a global_load
+typedef const float __attribute__((address_space(1)))* GlobalFloats;
+
 struct FusedWork {
     float *wp, *wm, *wv, *g;   // wp / wm / wv: [2][cap][64];  g: [3][cap][64]
     int64_t cap;
@@ -61,68 +64,125 @@ struct FusedWork {
 // workgroup of five wavefronts per interaction (one per row, the rows meeting in LDS) was tried and is slower (18.4 vs 12.7 us
 // per launch alone on the chip): a CU holds four interactions either way, so the catch-up arithmetic per SIMD is the same,
 // and the barrier and the second id load come on top.
+//
+// The load phase.  A wavefront's time is a chain of memory round trips, and the launch lasts as long as its slowest
+// wavefront, so the phase is written to make exactly three of them, whatever the rows' sources:
+//   1. the arguments the first loads need (the id and word columns, n);
+//   2. the first interaction's ids and words (two loads: one row per group of four lanes) and the per-step tables, with
+//      every other argument fetched beside them in one round of scalar loads;
+//   3. all twenty row loads (p, m, v and the gradient word of the five rows), issued back to back with no wait between
+//      the first and the last.  Lane 4 r + q computes the address of plane q of row r -- the row's source (pre buffer,
+//      dense tables, workspace) selects the BASE, nothing is loaded from a source that is not the row's (pre may be NULL) --
+//      and the loads take their bases from the lanes with v_readlane.
+// What a source does not supply is put in afterwards by selects: {1, 0, 0} for the lanes of the last bias block that lie
+// past the end of the dense buffer (they load the last element inside), 0 for the gradient of a row that has none pending.
+// Written with a branch per source the same loads compile to a wait at every join of the branches (the defaults written
+// on one path are load destinations on the others, so all older loads must have returned first): up to five dependent
+// trips for the rows, and four for the arguments and tables in front of them.  The values that reach chain_advance are
+// the same: the kernel stays bit-identical.
 __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
     const float* __restrict__ P, const float* __restrict__ M, const float* __restrict__ V, int64_t n_par, FusedWork w,
     const int32_t* __restrict__ u_ids, const int32_t* __restrict__ i_ids, const int32_t* __restrict__ j_ids,
     const int32_t* __restrict__ meta, int n, int64_t ublk0, int64_t iblk0, int64_t bblk0, int s_now, AdamBlockArgs a,
     float reg, float* __restrict__ loss, int loss_slots, int dbg, const float* __restrict__ pre) {
     __shared__ float s_loss[BPR_WAVES], s_l2[BPR_WAVES];
-    // Issue priority over the cold pass that shares the SIMDs (side stream); dbg & 16 switches it off.  Round 2 measured it
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // round 1: the ids and the words in two loads -- lane L works for row L >> 2 (lanes 20 .. 63: row 4 again) and fetches
+    // that row's id and word.  The first interaction's are issued here, before anything branches and beside the tables below
+    // (an index past the batch is clamped: the wavefront then loads what it will not use), the next one's inside the loop
+    const int lr = lane < 16 ? lane >> 2 : 4, lq = lane & 3;
+    const int32_t* my_ids = lr == 0 ? u_ids : (lr & 1) ? i_ids : j_ids;
+    const int32_t* my_meta = meta + static_cast<int64_t>(lr) * n;
+    const int b0 = blockIdx.x * BPR_WAVES + wv, b_step = gridDim.x * BPR_WAVES;
+    int32_t next_id = my_ids[b0 < n ? b0 : n - 1], next_mt = my_meta[b0 < n ? b0 : n - 1];
+    // the block's per-step scalars, one step per lane (adam_math.h): loaded once, beside the ids, and read with v_readlane
+    const AdamChainArgs ca = adam_chain_args(a);
+    // every other argument is fetched here too, in one round of scalar loads beside the vector loads above: left alone the
+    // compiler fetches each where it is first used -- behind the branches below, one dependent round after the other.  (An
+    // empty statement that names them as operands: they must be in registers when it is reached.)
+    asm volatile("" ::"s"(P), "s"(M), "s"(V), "s"(n_par), "s"(w.wp), "s"(w.wm), "s"(w.wv), "s"(w.g), "s"(w.cap), "s"(pre), "s"(loss));
+    asm volatile("" ::"s"(ublk0), "s"(iblk0), "s"(bblk0), "s"(s_now), "s"(reg), "s"(loss_slots), "s"(dbg), "s"(ca.stats), "s"(ca.first_unit));
+    asm volatile("" ::"s"(ca.one_minus_b1), "s"(ca.b2), "s"(ca.one_minus_b2), "s"(ca.eps), "s"(ca.rest_eps), "s"(ca.rest_b2k), "s"(ca.fast_vlo),
+                 "s"(ca.fast_mlo), "s"(ca.fast_mhi));
+    // Issue priority over the cold pass that shares the SIMDs (side stream); dbg & 16 switches it off.  (Set behind the
+    // argument loads: in front of them its test of dbg is a dependent scalar round of its own.)  Round 2 measured it
     // alone (the step +6 %, but the cold pass 0.47 -> 0.57 ms, which then bounded the block) and left it off; round 3 pairs it
     // with one more cold-pass workgroup per CU (SKR_COLD_BPC 4 -> 5), which gives the pass back what the priority takes:
     // step launch 18.7 -> 15.3 us, cold pass 0.56 -> 0.54 ms, epoch 1.083 -> 1.010 s, the 20-step slice 36.2 -> 40.2 M
     // interactions/s on the same box (tools/cold_bpc_sweep.sh; 6 per CU: epoch 0.965 s but the short slice scatters 32-40 M,
     // 7 and more: the step kernel finds no room, 21.5 us)
     if (!(dbg & 16)) __builtin_amdgcn_s_setprio(3);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // the block's per-step scalars, one step per lane (adam_math.h): loaded once, ahead of the ids, and read with v_readlane
-    const AdamChainArgs ca = adam_chain_args(a);
     float acc_loss = 0.0f, acc_l2 = 0.0f;
-    for (int b = blockIdx.x * BPR_WAVES + wv; b < n; b += gridDim.x * BPR_WAVES) {
-        const int64_t u = u_ids[b], i = i_ids[b], j = j_ids[b];
+    for (int b = b0; b < n; b += b_step) {
+        const int32_t my_id = next_id;
+        int32_t my_mt = next_mt;
+        // round 2, the addresses: lane L computes ONE of the twenty, plane L & 3 (p, m, v, gradient) of its row -- the row's
+        // source decides the base of p / m / v; the gradient word always comes from the workspace (any n0 field, 7
+        // included, gives a buffer index 0 .. 2: inside w.g)
+        int my_lim, my_from;      // my_lim, dense source: the last lane inside the buffer (the last bias block's tail; -1: none); 63 otherwise
+        uint64_t my_addr;
+        {
+            const int64_t blk = lr == 0 ? ublk0 + my_id : lr < 3 ? iblk0 + my_id : bblk0 + (my_id >> 6);
+            const int64_t slot = my_mt & ((1 << FUSED_SLOT_BITS) - 1);
+            const int n0 = (my_mt >> FUSED_SLOT_BITS) & 7, prev1 = (my_mt >> 24) & 0x7f;
+            // n0 == FUSED_PRE: the row's first naming in the block, and the row was cold in the block before: its zero-gradient
+            // updates up to this step were applied ahead of time, beside the previous block (bpr_fused_pre_kernel) -- same bits
+            const bool is_pre = n0 == FUSED_PRE, is_dense = !is_pre && prev1 == 0;
+            const int64_t tail = n_par - 1 - blk * 64;
+            const bool in_dense = is_dense && tail >= 0;      // (a block wholly past the end reads its slot and keeps nothing)
+            my_lim = is_dense && tail < 63 ? (tail < 0 ? -1 : static_cast<int>(tail)) : 63;
+            my_from = is_pre ? s_now : prev1;
+            if (is_pre) my_mt &= ~(7 << FUSED_SLOT_BITS);        // n0 = 0 from here on
+            const uint64_t b_dense = reinterpret_cast<uint64_t>(lq == 0 ? P : lq == 1 ? M : V);
+            const uint64_t b_work = reinterpret_cast<uint64_t>(lq == 0 ? w.wp : lq == 1 ? w.wm : lq == 2 ? w.wv : w.g);
+            const uint64_t b_pre = reinterpret_cast<uint64_t>(pre) + static_cast<uint64_t>(lq * w.cap) * 256;
+            const int64_t e_work = lq == 3 ? ((n0 + 2) % 3) * w.cap + slot : (n0 & 1) * w.cap + slot;
+            my_addr = lq == 3 ? b_work + e_work * 256 : is_pre ? b_pre + slot * 256 : in_dense ? b_dense + blk * 256 : b_work + e_work * 256;
+        }
+        // ... the scalars the rest of the kernel works with, and the twenty loads, issued back to back
+        const int64_t i = __builtin_amdgcn_readlane(my_id, 4), j = __builtin_amdgcn_readlane(my_id, 8);
         int32_t mt[5];
-        int64_t blk[5] = {ublk0 + u, iblk0 + i, iblk0 + j, bblk0 + (i >> 6), bblk0 + (j >> 6)};
-#pragma unroll
-        for (int r = 0; r < 5; ++r) mt[r] = __builtin_amdgcn_readfirstlane(meta[static_cast<int64_t>(r) * n + b]);
         FusedRow row[5];
         int from[5];      // first zero-gradient index still to apply
+        int lim[5];
 #pragma unroll
         for (int r = 0; r < 5; ++r) {
-            const int64_t slot = mt[r] & ((1 << FUSED_SLOT_BITS) - 1);
-            int n0 = (mt[r] >> FUSED_SLOT_BITS) & 7;
-            row[r] = FusedRow{1.0f, 0.0f, 0.0f, 0.0f};
-            from[r] = (mt[r] >> 24) & 0x7f;
-            if (n0 == FUSED_PRE) {
-                // the row's first naming in the block, and the row was cold in the block before: its zero-gradient updates up
-                // to this step were applied ahead of time, beside the previous block (bpr_fused_pre_kernel) -- same bits
-                const int64_t e = slot * 64 + lane;
-                row[r].p = pre[e];
-                row[r].m = pre[w.cap * 64 + e];
-                row[r].v = pre[2 * w.cap * 64 + e];
-                from[r] = s_now;
-                mt[r] &= ~(7 << FUSED_SLOT_BITS);        // n0 = 0 from here on
-                n0 = 0;
-            } else if (((mt[r] >> 24) & 0x7f) == 0) {
-                const int64_t e = blk[r] * 64 + lane;
-                if (e < n_par) {
-                    row[r].p = P[e];
-                    row[r].m = M[e];
-                    row[r].v = V[e];
-                }
-            } else {
-                const int64_t e = ((n0 & 1) * w.cap + slot) * 64 + lane;
-                row[r].p = w.wp[e];
-                row[r].m = w.wm[e];
-                row[r].v = w.wv[e];
-                row[r].g = w.g[(((n0 + 2) % 3) * w.cap + slot) * 64 + lane];
-            }
-        }
-        if (!(dbg & 1)) {
+            mt[r] = __builtin_amdgcn_readlane(my_mt, 4 * r);
+            from[r] = __builtin_amdgcn_readlane(my_from, 4 * r);
+            lim[r] = __builtin_amdgcn_readlane(my_lim, 4 * r);
+            const uint32_t lo = lane < lim[r] ? lane : (lim[r] < 0 ? 0 : lim[r]);      // a lane past the end loads the last element inside
+            GlobalFloats src[4];
 #pragma unroll
-            for (int r = 0; r < 5; ++r) {
+            for (int q = 0; q < 4; ++q)
+                src[q] = reinterpret_cast<GlobalFloats>(
+                    static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(my_addr), 4 * r + q))) |
+                    static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(my_addr >> 32), 4 * r + q))) << 32);
+            row[r].p = src[0][lo];
+            row[r].m = src[1][lo];
+            row[r].v = src[2][lo];
+            // (a relaxed load of wavefront scope: the plain load instruction, but one the compiler may not sink into the
+            // branch of its only use, behind the waits for the other rows; other wavefronts may be adding to the word)
+            row[r].g = __hip_atomic_load(src[3] + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        next_id = my_ids[b + b_step < n ? b + b_step : n - 1], next_mt = my_meta[b + b_step < n ? b + b_step : n - 1];
+        // the refined reciprocal of the bias-correction table (adam_chain_args' own three operations) is made here, behind the
+        // rows' loads: made ahead of the loop it puts the wait for the tables in front of all the set-up the loop needs
+        AdamChainArgs cb = ca;
+        asm volatile("" : "+v"(cb.t_bc2));
+        const float rb = __builtin_amdgcn_rcpf(cb.t_bc2);
+        cb.t_rbc2 = __builtin_fmaf(__builtin_fmaf(-cb.t_bc2, rb, 1.0f), rb, rb);
+        // (selects, never products: a gradient word that does not count may be mid-accumulation by other wavefronts)
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const bool past = lane > lim[r];
+            row[r].p = past ? 1.0f : row[r].p;
+            row[r].m = past ? 0.0f : row[r].m;
+            row[r].v = past ? 0.0f : row[r].v;
+            row[r].g = ((mt[r] >> 24) & 0x7f) != 0 ? row[r].g : 0.0f;      // (a pre-buffer row is a first naming: no previous step)
+            if (!(dbg & 1)) {
                 const int prev1 = (mt[r] >> 24) & 0x7f;
                 const AdamRowState o = chain_advance(row[r].p, row[r].g, row[r].m, row[r].v, prev1, from[r], s_now,
-                                                     r < 3 ? FC_STEP_ROW : FC_STEP_BIAS, ca);
+                                                     r < 3 ? FC_STEP_ROW : FC_STEP_BIAS, cb);
                 row[r].p = o.p, row[r].m = o.m, row[r].v = o.v;
             }
         }
