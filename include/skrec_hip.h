@@ -1084,6 +1084,84 @@ int skr_selfcf_step_timed(const skr_selfcf_step_args* args, void* stream, float*
 int skr_selfcf_queries(const float* d_pred, const float* d_M, int n_users, int n_items, float* d_Q, float* d_item_bias,
                        float* d_user_const, void* stream);
 
+/* ============================================================================================
+ * J -- BM3, bootstrapped multi-modal recommendation (csrc/bm3.hip)
+ * replaces: _BM3.forward / calculate_loss / full_sort_predict and BM3.fit's step (recommender/BM3.py:142-210, 236-243) at
+ * embed_dim <= 64, with trainable item feature tables of up to SKR_BM3_MAX_FEAT columns per modality.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  params = the [n_users + n_items, 64] rows, then the predictor's W row-major [64 out][64 in] and b [64]
+ * (SKR_BM3_PRED_FLOATS), zero beyond dim; grad has the same layout.  Modality 0 is the image block, 1 the text block
+ * (feat_dim 0 = absent): a feature table is [n_items][feat_ld] floats, feat_ld = feat_dim rounded up to a multiple of 4,
+ * zero beyond feat_dim; its projection block is W [64 out][feat_ld], then b [64], zero beyond dim and feat_dim.
+ * A is the plan of the normalised train matrix (BM3.py:116-140; the same values as SelfCF's), At the plan of its transpose.
+ * ========================================================================================== */
+#define SKR_BM3_MAX_BATCH 2048
+#define SKR_BM3_MAX_LAYERS 4
+#define SKR_BM3_MAX_FEAT 4096
+#define SKR_BM3_PRED_FLOATS (64 * 64 + 64)
+/* the tables of the target draws, in the order the reference draws them (BM3.py:168-177) */
+enum { SKR_BM3_DRAW_USER = 0, SKR_BM3_DRAW_ITEM = 1, SKR_BM3_DRAW_TEXT = 2, SKR_BM3_DRAW_IMAGE = 3 };
+/* d_Y[r, :] = X[ids[r], :feat_dim] W^T + b for r < n (nn.Linear on the batch's rows of an nn.Embedding, BM3.py:160-162): d_X
+ * [n_rows][feat_ld], d_trs = W [64][feat_ld] then b [64], d_Y [n][64].  16-row tiles on v_mfma_f32_16x16x4_f32, fp32 operands,
+ * one wavefront per tile walking the feat_dim terms 64 at a time in a fixed order (the range is not split over workgroups).
+ * A row whose id is outside [0, n_rows) gets b alone. */
+int skr_bm3_project(const float* d_X, int n_rows, int feat_dim, int feat_ld, const float* d_trs, const int32_t* d_ids, int n,
+                    float* d_Y, void* stream);
+/* The keep flags of the device draws: d_out[r][c] (uint8 [n][64]) = 1 iff a 24-bit uniform keyed by (seed, step, table,
+ * ids[r], c) is >= rate -- rows of one node are identical.  F.dropout's mask in law only. */
+int skr_bm3_draws(const int32_t* d_ids, int n, int table, float rate, uint64_t seed, uint64_t step, uint8_t* d_out, void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   M = mean_{k=0..n_layers} A-hat^k X_0 through skr_spmm_plan_run_ex (2 n_layers runs), then M_items += X_0 items (BM3.py:153);
+ *   T = skr_bm3_project of the text block at the batch's items, V of the image block; P(x) = W x + b;
+ *   targets x keep / (1 - dropout) of M_u, M_i, T, V at the batch's rows, no gradient; c = F.cosine_similarity (eps 1e-8);
+ *   loss[0] = (1 - mean c(P(M_u[u]), i_tgt)) + (1 - mean c(P(M_i[i]), u_tgt))
+ *   loss[1] = cl_weight * sum over the present X in (T, V) of (1 - mean c(P(X[i]), i_tgt)) + (1 - mean c(P(X[i]), x_tgt))
+ *   loss[2] = reg * (|M_u|_F + |M_i|_F) / n_items over the WHOLE tables;  loss[3] = their sum          WRITTEN
+ *   grad, trs_grad[m]: the gradient of loss[3], every element                                          WRITTEN
+ *   feat_grad[m]: first the rows named by clear_items are zeroed (the rows the previous step wrote: the table is never
+ *   filled as a whole), then the row of every distinct item of the batch is written; all other rows are left as they are
+ *   (zero, if every step hands in the previous step's items).
+ * keep[t] ([n, 64] bytes per table of SKR_BM3_DRAW_*; a repeated node must carry equal rows) are handed in together or all
+ * NULL: drawn on the device, keyed by (seed, step, table, node id, column).  Rows whose user or item is out of range
+ * contribute nothing.  The predictor's and the projections' products run on v_mfma_f32_16x16x4_f32 with fp32 operands.  No
+ * floating-point atomic, every sum in a fixed order: the step is bit-reproducible. */
+typedef struct skr_bm3_step_args {
+    const skr_spmm_plan* plan_a;       /* A [n_users, n_items]; may be NULL if n_layers == 0 */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    int32_t n_users, n_items, dim, n_layers, n;
+    int32_t feat_dim[2];               /* image, text; 0 = the modality is absent */
+    int32_t feat_ld[2];
+    const float* params;
+    const float* trs[2];               /* W [64][feat_ld], then b [64] */
+    const float* feat[2];              /* [n_items][feat_ld] */
+    const int32_t* users;              /* [n] */
+    const int32_t* items;              /* [n] */
+    const int32_t* clear_items;        /* [n_clear] item ids whose feat_grad rows are zeroed first; may be NULL if n_clear == 0 */
+    int32_t n_clear;
+    const uint8_t* keep[4];            /* [n, 64] each, indexed by SKR_BM3_DRAW_*; all NULL: device draws */
+    float dropout, reg, cl_weight;
+    uint64_t seed, step;               /* key of the device draws */
+    float* M;                          /* [n_users + n_items, 64] */
+    float* ping[2];                    /* scratch, [n_users + n_items, 64] each; NULL if n_layers < 2 */
+    float* G;                          /* scratch, [n_users + n_items, 64]; not used if n_layers == 0 */
+    float* grad;
+    float* trs_grad[2];
+    float* feat_grad[2];
+    float* loss;                       /* [4] */
+    void* work;                        /* skr_bm3_workspace(n) bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_bm3_step_args;
+size_t skr_bm3_workspace(int n);
+int skr_bm3_step(const skr_bm3_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_BM3_GROUPS launch groups (forward plan runs; + h and the sums of squares;
+ * projections; batch kernel, predictor reduction and loss; projection backward; dense regulariser, rank and seg_add; backward
+ * plan runs): h_ms[k] (host) = milliseconds of group k; synchronises the stream (timing tools). */
+#define SKR_BM3_GROUPS 7
+int skr_bm3_step_timed(const skr_bm3_step_args* args, void* stream, float* h_ms);
+/* Ranking (BM3.py:206-210): d_Qu[r] = W M_r + b for the n_users user rows, d_Qi[t] = W M_(n_users + t) + b for the item rows
+ * (zero beyond dim): skr_eval_fused_topk ranks <d_Qu[u], d_Qi[i]>.  d_pred: SKR_BM3_PRED_FLOATS floats. */
+int skr_bm3_queries(const float* d_pred, const float* d_M, int n_users, int n_items, float* d_Qu, float* d_Qi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,12 @@ SIGNATURES = {
     "skr_selfcf_step": (i32, [vp, vp]),
     "skr_selfcf_step_timed": (i32, [vp, vp, vp]),
     "skr_selfcf_queries": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "skr_bm3_project": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "skr_bm3_draws": (i32, [vp, i32, i32, f32, u64, u64, vp, vp]),
+    "skr_bm3_workspace": (sz, [i32]),
+    "skr_bm3_step": (i32, [vp, vp]),
+    "skr_bm3_step_timed": (i32, [vp, vp, vp]),
+    "skr_bm3_queries": (i32, [vp, vp, i32, i32, vp, vp, vp]),
 }
 
 
@@ -183,6 +189,17 @@ class SelfCFStepArgs(C.Structure):
                 ("G", vp), ("grad", vp), ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
 
 
+class BM3StepArgs(C.Structure):
+    """skr_bm3_step_args (include/skrec_hip.h): the parameters, the feature blocks (image, text), the batch, the keep flags and
+    the scratch of one BM3 step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32),
+                ("n_layers", C.c_int32), ("n", C.c_int32), ("feat_dim", C.c_int32 * 2), ("feat_ld", C.c_int32 * 2), ("params", vp),
+                ("trs", vp * 2), ("feat", vp * 2), ("users", vp), ("items", vp), ("clear_items", vp), ("n_clear", C.c_int32),
+                ("keep", vp * 4), ("dropout", C.c_float), ("reg", C.c_float), ("cl_weight", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_uint64), ("M", vp), ("ping", vp * 2), ("G", vp), ("grad", vp), ("trs_grad", vp * 2), ("feat_grad", vp * 2),
+                ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -196,7 +213,10 @@ SKR_LIGHTGCL_MAX_QUERIES, SKR_LIGHTGCL_MAX_Q, SKR_LIGHTGCL_GROUPS = 4096, 16, 8 
 SKR_DENS_MAX_BATCH, SKR_DENS_MAX_NEGS, SKR_DENS_MAX_HOPS, SKR_DENS_GROUPS = 2048, 16, 3, 6   # skr_dens_step limits
 SKR_SELFCF_MAX_BATCH, SKR_SELFCF_MAX_LAYERS, SKR_SELFCF_GROUPS = 2048, 4, 4   # skr_selfcf_step limits
 SKR_SELFCF_PRED_FLOATS = 64 * 64 + 64    # the predictor's block of the flat parameter buffer: W [64 out][64 in], then b [64]
-SKR_DENS_GATE_FLOATS = 64 * 64 + 64      # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
+SKR_BM3_MAX_BATCH, SKR_BM3_MAX_LAYERS, SKR_BM3_MAX_FEAT, SKR_BM3_GROUPS = 2048, 4, 4096, 7   # skr_bm3_step limits
+SKR_BM3_PRED_FLOATS = 64 * 64 + 64       # the predictor's block of BM3's parameter buffer
+SKR_BM3_DRAW_USER, SKR_BM3_DRAW_ITEM, SKR_BM3_DRAW_TEXT, SKR_BM3_DRAW_IMAGE = 0, 1, 2, 3   # the tables of the target draws
+SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 
 def hgn_gate_floats(L):

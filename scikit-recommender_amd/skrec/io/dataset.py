@@ -16,7 +16,7 @@ import numpy as np
 import pandas as pd
 import scipy.sparse as sp
 
-__all__ = ["ImplicitFeedback", "KnowledgeGraph", "RSDataset", "UserGroup", "group_users_by_interactions"]
+__all__ = ["ImplicitFeedback", "KnowledgeGraph", "MMData", "RSDataset", "UserGroup", "group_users_by_interactions"]
 
 _USER, _ITEM, _RATING, _TIME = "user", "item", "rating", "time"
 _DColumns = {"UI": [_USER, _ITEM], "UIR": [_USER, _ITEM, _RATING], "UIT": [_USER, _ITEM, _TIME],
@@ -213,6 +213,37 @@ def _read_table(path, sep, names, missing):
     return pd.DataFrame()
 
 
+class MMData(object):
+    """Per-item feature tables of the multimodal models (reference: dataset.py:544-575): ``<prefix>.img.npz``,
+    ``<prefix>.txt.npz`` and ``<prefix>.audio.npz``, the first array of each file; a missing file gives ``None``.  A table
+    whose row count is not ``num_items`` is an error (the reference fails later, inside the model)."""
+
+    def __init__(self, file_prefix, num_items):
+        for key in ("img", "txt", "audio"):
+            features, dim = self._load_npz_features(f"{file_prefix}.{key}.npz", num_items)
+            setattr(self, key + "_features", features)
+            setattr(self, key + "_dim", dim)
+
+    @staticmethod
+    def _load_npz_features(file_path, num_items):
+        if not os.path.exists(file_path):
+            return None, None
+        with np.load(file_path, allow_pickle=True) as feat_obj:
+            features = feat_obj[feat_obj.files[0]]
+        if features.ndim < 1 or features.shape[0] != num_items:
+            raise ValueError(f"'{file_path}' holds {features.shape[0] if features.ndim else 0} rows, the data set has {num_items} items")
+        return features, features.shape[-1]
+
+    @property
+    def statistic_info(self) -> str:
+        lines = [""]
+        for key, label in (("img", "image"), ("txt", "txt"), ("audio", "audio")):
+            features = getattr(self, key + "_features")
+            if features is not None:
+                lines.append(f"The shape of {label} features: {features.shape}")
+        return "\n".join(lines)
+
+
 class RSDataset(object):
     """``RSDataset(data_dir, sep, columns)``; splits are loaded lazily on first access
     (reference: dataset.py:582-600, CFData._load_cf_data :388-425)."""
@@ -297,6 +328,38 @@ class RSDataset(object):
     def num_ratings(self) -> int:
         self._load()
         return self._num_ratings
+
+    # ---- item features (reference: dataset.py:647-677); loaded on first access, the shapes logged once -------------
+    @property
+    def mm_data(self) -> MMData:
+        if not hasattr(self, "_mm_data"):
+            self._mm_data = MMData(self.file_prefix, self.num_items)
+            self._log_print(self._mm_data.statistic_info)
+        return self._mm_data
+
+    @property
+    def img_features(self) -> np.ndarray:
+        return self.mm_data.img_features
+
+    @property
+    def img_dim(self) -> int:
+        return self.mm_data.img_dim
+
+    @property
+    def txt_features(self) -> np.ndarray:
+        return self.mm_data.txt_features
+
+    @property
+    def txt_dim(self) -> int:
+        return self.mm_data.txt_dim
+
+    @property
+    def audio_features(self) -> np.ndarray:
+        return self.mm_data.audio_features
+
+    @property
+    def audio_dim(self) -> int:
+        return self.mm_data.audio_dim
 
     @property
     def statistic_info(self) -> str:

@@ -1,0 +1,399 @@
+"""BM3 on MI355X (reference: skrec/recommender/BM3.py).
+
+Paper: Bootstrap Latent Representations for Multi-modal Recommendation (Zhou, Zhou, Liu, Zeng, Miao, Wang, You and Jiang, WWW
+2023).  Same config, same initialisation, same loss (BM3.py:142-204): a LightGCN encoder over the normalised square adjacency
+(no dropout on the graph) whose item rows get their own embedding added once more (``+ h``); per present modality a TRAINABLE
+item feature table, initialised from ``<prefix>.img.npz`` / ``<prefix>.txt.npz``, and an ``nn.Linear(F, embed_dim)``; one shared
+64 x 64 predictor; six cosine terms between the predictor of one row set and a dropped-out, detached copy of another; and
+``reg`` times the Frobenius norms of the WHOLE propagated tables divided by the number of items.  There are no negatives.
+``feat_dim`` is accepted and ignored, as in the reference: the projections are ``embed_dim`` wide.
+
+One training step is ``skr_bm3_step`` (csrc/bm3.hip: 2 n_layers plan runs forward, the norms, the gather-and-project product
+of the batch's items -- the reference's [I, d] projected tables are never formed --, the batch kernel with the predictor on
+the fp32 matrix pipe, the projection backward, the ordered segment adds, the dense regulariser gradient, 2 n_layers plan runs
+backward) and one dense Adam launch over the flat buffer
+
+    [U + I, 64] rows | W 64 x 64 | b 64 | image: trs W [64, ld] | trs b 64 | table [I, ld] | text: the same three
+
+with ``weight_decay = 0`` (``ld`` = the feature width rounded up to a multiple of 4, zero beyond it).  The feature tables
+receive a dense gradient that is zero outside the batch's items; their other rows still move by leftover momentum, as under
+``torch.optim.Adam``.  The step zeroes only the gradient rows the previous step wrote.  The reference's ``LambdaLR`` factor is
+``1.0 ** (epoch / 50) = 1``: the learning rate is constant, and no scheduler is kept.
+
+The four target masks are drawn on the device (``draws = "device"``, the only mode: not a reference option), keyed by (seed,
+step, table, node id): equal to the reference's ``F.dropout`` draws in law only; a node that occurs twice in a batch has one
+mask.  ``gradient_step(..., target_keep)`` takes recorded flags instead and replays a recorded run.
+
+``evaluate()`` propagates the CURRENT parameters and ranks ``(W M_u + b) . (W M_i + b)`` (BM3.py:206-210) through the fused
+top-K path: the two factor tables come from ``skr_bm3_queries``.
+
+Limits (NotImplementedError): embed_dim <= 64, n_layers <= 4, batch_size <= 2048, 1 <= F <= 4096 per modality, one GPU.
+"""
+import ctypes
+from typing import Dict
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _hip
+from ..io import InteractionIterator
+from ..run_config import RunConfig
+from ..utils.py import EarlyStopping, ModelConfig
+from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from .LightGCL import selfcf_adjacency
+
+__all__ = ["BM3", "BM3Config"]
+
+MAX_BATCH, MAX_LAYERS, MAX_FEAT = _hip.SKR_BM3_MAX_BATCH, _hip.SKR_BM3_MAX_LAYERS, _hip.SKR_BM3_MAX_FEAT
+PRED_FLOATS = _hip.SKR_BM3_PRED_FLOATS
+# (key, the reference's prefix, index of the kernel's modality slot): the reference registers the image block first
+MODALITIES = (("img", "image", 0), ("txt", "text", 1))
+
+
+class BM3Config(ModelConfig):
+    def __init__(self, lr=1e-3, reg=0.1, embed_dim=64, feat_dim=64, n_layers=1, dropout=0.3, cl_weight=2.0, batch_size=2048,
+                 epochs=1000, early_stop=200, draws="device", **kwargs):
+        super().__init__()
+        self.lr: float = lr
+        self.reg: float = reg
+        self.embed_dim: int = embed_dim
+        self.feat_dim: int = feat_dim          # accepted and ignored, as in the reference (BM3.py:79)
+        self.n_layers: int = n_layers
+        self.cl_weight: float = cl_weight
+        self.dropout: float = dropout
+        self.batch_size: int = batch_size
+        self.epochs: int = epochs
+        self.early_stop: int = early_stop
+        # how the target masks are made (not a reference option): "device"
+        self.draws: str = draws
+
+    @classmethod
+    def param_space(cls):
+        return {"n_layers": [1, 2], "reg": [0.1, 0.01], "dropout": [0.3, 0.5]}
+
+    def _validate(self):
+        assert isinstance(self.lr, float) and self.lr > 0
+        assert isinstance(self.reg, float) and self.reg >= 0
+        assert isinstance(self.embed_dim, int) and self.embed_dim > 0
+        assert isinstance(self.feat_dim, int)
+        assert isinstance(self.n_layers, int) and self.n_layers >= 0
+        assert isinstance(self.cl_weight, float) and self.cl_weight >= 0
+        assert isinstance(self.dropout, float) and 0 <= self.dropout < 1
+        assert isinstance(self.batch_size, int) and self.batch_size > 0
+        assert isinstance(self.epochs, int) and self.epochs >= 0
+        assert isinstance(self.early_stop, int)
+        assert self.draws == "device"
+
+
+def check_limits(config, world=1, img_dim=None, txt_dim=None):
+    """raises NotImplementedError, naming the limit, for a config or a feature width this implementation does not run"""
+    if config.embed_dim > 64:
+        raise NotImplementedError(f"BM3: embed_dim <= 64 (got {config.embed_dim}): rows are 64 floats and the predictor 64 x 64")
+    if config.n_layers > MAX_LAYERS:
+        raise NotImplementedError(f"BM3: n_layers <= {MAX_LAYERS} (got {config.n_layers})")
+    if config.batch_size > MAX_BATCH:
+        raise NotImplementedError(f"BM3: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_bm3_step takes {MAX_BATCH} rows")
+    for name, F in (("image", img_dim), ("text", txt_dim)):
+        if F is not None and not 1 <= F <= MAX_FEAT:
+            raise NotImplementedError(f"BM3: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
+    if world > 1:
+        raise NotImplementedError("BM3 runs on one GPU (one rank): there is no sharded engine for it")
+
+
+def _linear_xavier(fan_in, d):
+    lin = nn.Linear(fan_in, d)
+    nn.init.xavier_normal_(lin.weight)
+    return lin.weight.detach().clone(), lin.bias.detach().clone()
+
+
+def init_parameters(num_users, num_items, d, img_dim=None, txt_dim=None):
+    """CPU-side draws in the reference's order (BM3.py:95-114): the two nn.Embedding tables (whose own normal draws are
+    consumed and overwritten), xavier-uniform user table, xavier-uniform item table, nn.Linear(d, d) then xavier_normal_ on
+    its weight, then per present modality -- image first -- nn.Linear(F, d) then xavier_normal_ -> {name: tensor} in the
+    reference's names, without the feature tables"""
+    eu, ei = nn.Embedding(num_users, d), nn.Embedding(num_items, d)
+    nn.init.xavier_uniform_(eu.weight)
+    nn.init.xavier_uniform_(ei.weight)
+    P = {"user_embedding.weight": eu.weight.detach().clone(), "item_id_embedding.weight": ei.weight.detach().clone()}
+    P["predictor.weight"], P["predictor.bias"] = _linear_xavier(d, d)
+    for prefix, F in (("image", img_dim), ("text", txt_dim)):
+        if F is not None:
+            P[prefix + "_trs.weight"], P[prefix + "_trs.bias"] = _linear_xavier(F, d)
+    return P
+
+
+def _features(a, num_items, name):
+    if a is None:
+        return None
+    if not torch.is_tensor(a):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if a.dim() != 2 or a.shape[0] != num_items:
+        raise ValueError(f"BM3: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
+    return a.to(torch.float32)
+
+
+class BM3(AbstractRecommender):
+    config_class = BM3Config
+
+    def __init__(self, run_config: RunConfig, model_config: Dict):
+        """limits: see ``check_limits``"""
+        self.config = BM3Config(**model_config)
+        from ..parallel import init_from_env
+        self.dist = init_from_env()
+        check_limits(self.config, self.dist.world)
+        super().__init__(run_config, self.config)
+        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
+        img, txt = self.dataset.img_features, self.dataset.txt_features
+        check_limits(self.config, self.dist.world, None if img is None else img.shape[1], None if txt is None else txt.shape[1])
+        self.device = _hip.require_gpu()
+        csr = self.dataset.train_data.to_csr_matrix().tocsr()
+        csr.sum_duplicates()
+        csr.sort_indices()
+        self._build(csr.indptr, csr.indices, img, txt, int(getattr(run_config, "seed", 0) or 0))
+
+    @classmethod
+    def detached(cls, num_users, num_items, model_config, csr, img=None, txt=None, seed=0):
+        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
+        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
+        device tensors); ``img`` / ``txt``: [num_items, F] feature tables or None; ``seed``: the key of the device draws"""
+        self = cls.__new__(cls)
+        self.config = cls.config_class(**model_config)
+        check_limits(self.config, 1, None if img is None else int(img.shape[1]), None if txt is None else int(txt.shape[1]))
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.device = _hip.require_gpu()
+        self._build(csr[0], csr[1], img, txt, int(seed))
+        return self
+
+    def _build(self, rowptr, items, img, txt, seed):
+        cfg, dev = self.config, self.device
+        nu, ni, d, L = self.num_users, self.num_items, cfg.embed_dim, cfg.n_layers
+        N = nu + ni
+        if torch.is_tensor(rowptr):
+            rp, col = rowptr.to(dev, torch.int64).contiguous(), items.to(dev, torch.int32).contiguous()
+        else:
+            rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
+            col = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(dev)
+        assert rp.numel() == nu + 1
+        self.adj, self.adj_t, _ = selfcf_adjacency(rp, col, nu, ni)      # BM3.py:116-140 normalises as SelfCF does
+        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
+        self.feat_dim = {k: 0 if v is None else int(v.shape[1]) for k, v in feats.items()}
+        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
+        P = init_parameters(nu, ni, d, self.feat_dim["img"] or None, self.feat_dim["txt"] or None)
+        # float offsets of the blocks of the flat buffer
+        self._off = {"pred": N * 64}
+        o = N * 64 + PRED_FLOATS
+        for key, _, _ in MODALITIES:
+            if self.feat_dim[key]:
+                ld = self.feat_ld[key]
+                self._off[key + "_trs"], self._off[key + "_tab"] = o, o + 64 * ld + 64
+                o += 64 * ld + 64 + ni * ld
+        self._total = o
+        self._flat = torch.zeros(o, dtype=torch.float32, device=dev)
+        self.optimizer = DenseAdam(self._flat, lr=cfg.lr)         # Adam(weight_decay=0), a constant learning rate (BM3.py:221-225)
+        self._grad = self.optimizer.grad
+        self.X0 = self._flat[:N * 64].view(N, 64)
+        self._pred = self._flat[N * 64:N * 64 + PRED_FLOATS]
+        for key, prefix, _ in MODALITIES:
+            if feats[key] is not None:
+                P[prefix + "_embedding.weight"] = feats[key]
+        self.load_parameters(P)
+        z = lambda: torch.zeros((N, 64), dtype=torch.float32, device=dev)        # noqa: E731
+        self.M = z()                                              # the layer means (+ h) of the last step's forward
+        self.pooled = z()                                         # the layer means (+ h) of the last propagate()
+        self._ping = (z(), z()) if L > 1 else (None, None)
+        self._G = z() if L > 0 else None
+        self._Qu = torch.zeros((nu, 64), dtype=torch.float32, device=dev)
+        self._Qi = torch.zeros((ni, 64), dtype=torch.float32, device=dev)
+        self._work = torch.empty(int(_hip.lib().skr_bm3_workspace(min(cfg.batch_size, MAX_BATCH))), dtype=torch.uint8, device=dev)
+        self._seed, self._step = seed, 0
+        self._prev_items = None        # the item ids whose feature-gradient rows the previous step wrote
+        self.step_losses = []          # (graph cosines, modal cosines, reg, total) per training step, device tensors [4]
+
+    # ---- the flat buffer's blocks ----------------------------------------------------------------
+    def _views(self, flat):
+        """{name: view} of ``flat`` in the reference's names and shapes"""
+        d, nu, ni = self.config.embed_dim, self.num_users, self.num_items
+        N = nu + ni
+        rows = flat[:N * 64].view(N, 64)
+        blk = flat[N * 64:N * 64 + PRED_FLOATS]
+        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d],
+               "predictor.weight": blk[:4096].view(64, 64)[:d, :d], "predictor.bias": blk[4096:4096 + d]}
+        for key, prefix, _ in MODALITIES:
+            F, ld = self.feat_dim[key], self.feat_ld[key]
+            if F:
+                t, e = self._off[key + "_trs"], self._off[key + "_tab"]
+                out[prefix + "_embedding.weight"] = flat[e:e + ni * ld].view(ni, ld)[:, :F]
+                out[prefix + "_trs.weight"] = flat[t:t + 64 * ld].view(64, ld)[:d, :F]
+                out[prefix + "_trs.bias"] = flat[t + 64 * ld:t + 64 * ld + d]
+        return out
+
+    def parameters(self):
+        """{name: tensor} in the reference's names and shapes (copies): user_embedding.weight, item_id_embedding.weight,
+        predictor.weight, predictor.bias and, per present modality, image_ / text_embedding.weight, _trs.weight, _trs.bias"""
+        return {k: v.contiguous().clone() for k, v in self._views(self._flat).items()}
+
+    def gradients(self):
+        """the gradient buffer in the shapes of ``parameters()`` (copies)"""
+        return {k: v.contiguous().clone() for k, v in self._views(self._grad).items()}
+
+    def load_parameters(self, named):
+        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
+        views = self._views(self._flat)
+        assert set(named) == set(views), sorted(set(named) ^ set(views))
+        for k, v in named.items():
+            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+            views[k].copy_(t.detach().to(self.device, torch.float32))
+
+    # ---- training --------------------------------------------------------------------------------
+    def _ids(self, t):
+        if torch.is_tensor(t):
+            return t.to(self.device, torch.int32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
+
+    def _flags(self, t, shape):
+        if not torch.is_tensor(t):
+            t = torch.from_numpy(np.ascontiguousarray(t).astype(np.uint8))
+        t = t.to(self.device, torch.uint8).contiguous()
+        assert tuple(t.shape) == tuple(shape), f"keep flags of shape {tuple(t.shape)}, expected {tuple(shape)}"
+        return t
+
+    def target_draws(self, ids, table, step=None):
+        """the device draws of one target table at the nodes ``ids`` (``skr_bm3_draws``) -> uint8 [n, 64]; ``table``: one of
+        _hip.SKR_BM3_DRAW_*; keyed by (seed, step, table, node id), ``step`` None: the coming step"""
+        d_ids = self._ids(ids)
+        out = torch.empty((int(d_ids.numel()), 64), dtype=torch.uint8, device=self.device)
+        _hip.check(_hip.lib().skr_bm3_draws(_hip.ptr(d_ids), int(d_ids.numel()), int(table), self.config.dropout, self._seed,
+                                            self._step if step is None else int(step), _hip.ptr(out), _hip.stream()))
+        return out
+
+    def gradient_step(self, users, items, target_keep=None, h_ms=None):
+        """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer,
+        the layer means (+ h) in ``self.M`` -> device tensor (graph cosines, modal cosines, reg, total).
+        ``target_keep`` = (ku, ki, kt, kv), [n, 64] each -- the flags of the user, item, text and image targets at the
+        batch's rows (the entries of an absent modality may be None) -- instead of the device draws;
+        ``h_ms``: a ctypes float array of SKR_BM3_GROUPS entries that receives the milliseconds of each launch group"""
+        cfg = self.config
+        du, di = self._ids(users), self._ids(items)
+        n, L = int(du.numel()), cfg.n_layers
+        if n > MAX_BATCH:
+            raise NotImplementedError(f"BM3: a batch holds at most {MAX_BATCH} rows (got {n})")
+        assert di.numel() == n
+        need = int(_hip.lib().skr_bm3_workspace(n))
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        loss = torch.empty(4, dtype=torch.float32, device=self.device)
+        a = _hip.BM3StepArgs()
+        keeps = None
+        if target_keep is not None:
+            ones = None
+            keeps = []
+            for k in target_keep:
+                if k is None:      # an absent modality: the kernel wants all four or none, and does not read this one
+                    ones = torch.ones((n, 64), dtype=torch.uint8, device=self.device) if ones is None else ones
+                    k = ones
+                keeps.append(self._flags(k, (n, 64)))
+            for t in range(4):
+                a.keep[t] = _hip.ptr(keeps[t])
+        if L > 0:
+            a.plan_a, a.plan_at = self.adj._plan_handle(), self.adj_t._plan_handle()
+        a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, n
+        a.params, a.users, a.items = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(di)
+        a.grad = _hip.ptr(self._grad)
+        for key, _, m in MODALITIES:
+            if not self.feat_dim[key]:
+                continue
+            t, e = self._off[key + "_trs"], self._off[key + "_tab"]
+            a.feat_dim[m], a.feat_ld[m] = self.feat_dim[key], self.feat_ld[key]
+            a.trs[m], a.feat[m] = _hip.ptr(self._flat[t:]), _hip.ptr(self._flat[e:])
+            a.trs_grad[m], a.feat_grad[m] = _hip.ptr(self._grad[t:]), _hip.ptr(self._grad[e:])
+        prev = self._prev_items
+        if prev is not None:
+            a.clear_items, a.n_clear = _hip.ptr(prev), int(prev.numel())
+        a.dropout, a.reg, a.cl_weight, a.seed, a.step = cfg.dropout, cfg.reg, cfg.cl_weight, self._seed, self._step
+        a.M, a.G, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(loss)
+        a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
+        a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        if h_ms is None:
+            _hip.check(_hip.lib().skr_bm3_step(ctypes.byref(a), _hip.stream()))
+        else:
+            _hip.check(_hip.lib().skr_bm3_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
+        if n > 0:
+            self._prev_items = di
+        self._step += 1
+        return loss
+
+    @on_compute_stream
+    def train_step(self, users, items, target_keep=None):
+        """one step on the pairs (users [n], items [n]) (sequences or int32 device tensors) -> device tensor of the loss
+        components (graph cosines, modal cosines, reg, their sum)"""
+        loss = self.gradient_step(users, items, target_keep=target_keep)
+        self.optimizer.step()
+        self._prev_items = None        # the Adam launch zeroes the gradient it has read: nothing is left to clear
+        self.step_losses.append(loss)
+        return loss
+
+    @on_compute_stream
+    def fit(self):
+        cfg = self.config
+        data_iter = InteractionIterator(self.dataset.train_data, batch_size=cfg.batch_size, shuffle=True, drop_last=False)
+        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
+        early_stopping = EarlyStopping(metric="NDCG@10", patience=cfg.early_stop)
+        for epoch in range(cfg.epochs):
+            self.step_losses = []
+            for users, items in data_iter:
+                self.train_step(users, items)
+            result = self.evaluate()
+            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
+            if early_stopping(result):
+                self.logger.info("early stop")
+                break
+        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
+        return early_stopping.best_result
+
+    # ---- ranking ---------------------------------------------------------------------------------
+    def propagate(self):
+        """the propagation of the CURRENT parameters, the layer means and the item rows' + h (BM3.py:142-153), then the two
+        factor tables W M + b (``skr_bm3_queries``) -> pooled"""
+        nu, ni, L = self.num_users, self.num_items, self.config.n_layers
+        L_ = _hip.lib()
+        if L == 0:
+            self.pooled.copy_(self.X0)
+        else:
+            s = 1.0 / (L + 1)
+            X = self.X0
+            for k in range(1, L + 1):
+                Y = None if k == L else self._ping[(k - 1) & 1]
+                base = self.X0 if k == 1 else None          # pooled = s X_0 + s X_1, then pooled += s X_k
+                for mat, lo, hi, xs in ((self.adj, 0, nu, X[nu:]), (self.adj_t, nu, None, X[:nu])):
+                    ep = _hip.SpmmEpilogue()
+                    ep.mode = _hip.EPI_PLAIN
+                    ep.Y, ep.accum = _hip.ptr(None if Y is None else Y[lo:hi]), _hip.ptr(self.pooled[lo:hi])
+                    ep.accum_base = _hip.ptr(None if base is None else base[lo:hi])
+                    ep.accum_scale = s
+                    _hip.check(L_.skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(xs), 64, ctypes.byref(ep), None, None, _hip.stream()))
+                X = Y
+        _hip.check(L_.skr_axpy(1.0, _hip.ptr(self.X0[nu:]), _hip.ptr(self.pooled[nu:]), ni * 64, _hip.stream()))     # + h
+        _hip.check(L_.skr_bm3_queries(_hip.ptr(self._pred), _hip.ptr(self.pooled), nu, ni, _hip.ptr(self._Qu), _hip.ptr(self._Qi),
+                                      _hip.stream()))
+        return self.pooled
+
+    @on_compute_stream
+    def evaluate(self, test_users=None):
+        self.propagate()
+        self._pooled_current = True
+        try:
+            return self.evaluator.evaluate(self, test_users)
+        finally:
+            self._pooled_current = False
+
+    def predict_factors(self):
+        """(W M_u + b [U, 64], W M_i + b [I, 64], None) of the current parameters"""
+        if not getattr(self, "_pooled_current", False):
+            self.propagate()
+        return self._Qu, self._Qi, None
+
+    def predict(self, users) -> np.ndarray:
+        """dense [len(users), num_items] scores (BM3.py:206-210)"""
+        uf, vf, _ = self.predict_factors()
+        return _hip.score_matrix(uf, list(users), vf, None).cpu().numpy()
