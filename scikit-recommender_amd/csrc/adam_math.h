@@ -345,34 +345,120 @@ __device__ __forceinline__ float chain_quot_ordinary(float m, float v, const Ada
     return div_ordinary(lane_scalar(c.t_nss, s) * m, sq + c.eps);
 }
 
-// ordinary_run: four chains side by side, then the rest one by one
+// The same three forms on TWO values at once: every multiply, add and fused multiply-add is one packed instruction
+// (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) on both halves, v_rsq_f32 and v_rcp_f32 stay per half.  Operation for
+// operation the scalar forms -- under -ffp-contract=off a vector `*` or `+` stays unfused and __builtin_elementwise_fma
+// stays fused, exactly as there -- so each half sees the same IEEE operations on the same values.  Measured for one
+// wavefront alone on its SIMD (profiles/fused_pack_timing.json): a packed FMA holds the issue as long as two plain ones,
+// but in a DEPENDENT chain it costs 9.3 ticks against 6.3 -- two updates for one and a half times the price of one.
+__device__ __forceinline__ f32x2 sqrt_ordinary(f32x2 x) {
+    f32x2 r;
+    r.x = __builtin_amdgcn_rsqf(x.x);
+    r.y = __builtin_amdgcn_rsqf(x.y);
+    const f32x2 s = x * r, h = 0.5f * r;
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(-s, s, x), h, s);
+}
+
+__device__ __forceinline__ f32x2 div_ordinary_r(f32x2 n, f32x2 d, f32x2 r) {
+    f32x2 q = n * r;
+    f32x2 t = __builtin_elementwise_fma(-d, q, n);
+    q = __builtin_elementwise_fma(t, r, q);
+    t = __builtin_elementwise_fma(-d, q, n);
+    return __builtin_elementwise_fma(t, r, q);
+}
+
+__device__ __forceinline__ f32x2 div_ordinary(f32x2 n, f32x2 d) {
+    f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(d.x);
+    r.y = __builtin_amdgcn_rcpf(d.y);
+    const f32x2 one = {1.0f, 1.0f};
+    const f32x2 e = __builtin_elementwise_fma(-d, r, one);
+    r = __builtin_elementwise_fma(e, r, r);
+    return div_ordinary_r(n, d, r);
+}
+
+// steps s0 and s1's entries of a lane table in the two halves
+__device__ __forceinline__ f32x2 lane_scalar2(float table, int s0, int s1) {
+    f32x2 t;
+    t.x = lane_scalar(table, s0);
+    t.y = lane_scalar(table, s1);
+    return t;
+}
+
+// chain_quot_ordinary for two updates of one row: .x holds the moments of update s0, .y those of update s1 (both of one
+// form: a pair never straddles first_unit, see chain_fast_run)
+template <bool UNIT_BC2>
+__device__ __forceinline__ f32x2 chain_quot_ordinary(f32x2 m, f32x2 v, const AdamChainArgs& c, int s0, int s1) {
+    f32x2 sq = sqrt_ordinary(v);
+    if (!UNIT_BC2) sq = div_ordinary_r(sq, lane_scalar2(c.t_bc2, s0, s1), lane_scalar2(c.t_rbc2, s0, s1));
+    return div_ordinary(lane_scalar2(c.t_nss, s0, s1) * m, sq + c.eps);
+}
+
+// Updates [s, s + n) of a row of ordinary magnitudes as NP pairs side by side, n = 2 NP - 1 or 2 NP (wave-uniform).  The
+// quotient of an update depends on that update's m and v only -- not on p -- so the moments are produced in order, the
+// square-root / division chains of the NP pairs are independent of each other, and p takes the quotients in order: the same
+// operations on the same values as update after update.  With n odd the last pair's second half is no update: it repeats
+// the first half's moments and step index (a valid lane of the tables, whatever s + n is -- index 63 has no successor
+// lane), and its quotient goes nowhere.
+template <bool UNIT_BC2, int NP>
+__device__ __forceinline__ void chain_ordinary_group(float& p, float& m, float& v, const AdamChainArgs& c, int s, int n, bool& updated) {
+    const bool full = n == 2 * NP;
+    f32x2 ms[NP], vs[NP], q[NP];
+#pragma unroll
+    for (int u = 0; u < NP; ++u) {
+        if (u > 0 || !updated) {
+            m = m + c.one_minus_b1 * (0.0f - m);
+            v = v * c.b2;
+        }
+        ms[u].x = m;
+        vs[u].x = v;
+        if (u + 1 < NP || full) {
+            m = m + c.one_minus_b1 * (0.0f - m);
+            v = v * c.b2;
+        }
+        ms[u].y = m;
+        vs[u].y = v;
+    }
+    updated = false;
+#pragma unroll
+    for (int u = 0; u < NP; ++u)
+        q[u] = chain_quot_ordinary<UNIT_BC2>(ms[u], vs[u], c, s + 2 * u, u + 1 < NP || full ? s + 2 * u + 1 : s + 2 * u);
+#pragma unroll
+    for (int u = 0; u < NP; ++u) {
+        p = p + q[u].x;
+        if (u + 1 < NP || full) p = p + q[u].y;
+    }
+}
+
+// ordinary_run: CHAIN_G pairs (2 CHAIN_G updates) side by side while that many are left, then what is left as ONE narrower
+// group; a single update takes the scalar chain.  (4: the step kernel's five rows no longer stay in registers)
+constexpr int CHAIN_G = 2;
+static_assert(CHAIN_G == 2 || CHAIN_G == 4, "chain_ordinary_run spells out the groups of one to four pairs");
+
 template <bool UNIT_BC2>
 __device__ __forceinline__ void chain_ordinary_run(float& p, float& m, float& v, const AdamChainArgs& c, int& s, int s_to, bool& updated) {
-    for (; s + 4 <= s_to; s += 4) {
-        float ms[4], vs[4], q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (u > 0 || !updated) {
-                m = m + c.one_minus_b1 * (0.0f - m);
-                v = v * c.b2;
-            }
-            ms[u] = m;
-            vs[u] = v;
-        }
-        updated = false;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = chain_quot_ordinary<UNIT_BC2>(ms[u], vs[u], c, s + u);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p = p + q[u];
+    while (s_to - s >= 2 * CHAIN_G - 1) {
+        const int n = s_to - s < 2 * CHAIN_G ? s_to - s : 2 * CHAIN_G;
+        chain_ordinary_group<UNIT_BC2, CHAIN_G>(p, m, v, c, s, n, updated);
+        s += n;
     }
-    for (; s < s_to; ++s) {
+    const int n = s_to - s;
+    if (n <= 0) return;
+    if (n == 1) {
         if (!updated) {
             m = m + c.one_minus_b1 * (0.0f - m);
             v = v * c.b2;
         }
         updated = false;
         p = p + chain_quot_ordinary<UNIT_BC2>(m, v, c, s);
+    } else if (n <= 2) {
+        chain_ordinary_group<UNIT_BC2, 1>(p, m, v, c, s, n, updated);
+    } else if (CHAIN_G > 2 && n <= 4) {
+        chain_ordinary_group<UNIT_BC2, 2>(p, m, v, c, s, n, updated);
+    } else if (CHAIN_G > 2) {
+        chain_ordinary_group<UNIT_BC2, 3>(p, m, v, c, s, n, updated);
     }
+    s = s_to;
 }
 
 // fast_run: the updates below first_unit on the non-unit form, the others on the unit form (a run is all of one kind

@@ -2,7 +2,10 @@
 SKR_FUSED_DBG (one-wavefront kernel only; results are then wrong, timing only): 1 no catch-up arithmetic, 2 no gradient
 atomics, 4 no owner stores, 8 no loss atomics.  SKR_FUSED_STATS=1: prints the census of the evaluations (skr_fused_census;
 its counters slow the launches -- not for timing).
-usage: python tools/fused_lab.py [k] [blocks]"""
+--per-step: an event pair around EACH of the k step launches of a block, and the mean launch time per step index 0 .. k - 1
+(the events between the launches cost time themselves: compare builds step by step, not with the figure without the option);
+tools/fused_quotients.py counts the catch-up work per step index for the same id distributions.
+usage: python tools/fused_lab.py [k] [blocks] [--per-step]"""
 import os
 import sys
 
@@ -12,8 +15,10 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "scikit-recommender_amd"))
 from skrec import _hip  # noqa: E402
 
-k = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-n_blocks = int(sys.argv[2]) if len(sys.argv) > 2 else 12
+per_step = "--per-step" in sys.argv[1:]
+argv = [x for x in sys.argv[1:] if not x.startswith("--")]
+k = int(argv[0]) if len(argv) > 0 else 32
+n_blocks = int(argv[1]) if len(argv) > 1 else 12
 nU, nI, b = 1_000_000, 100_000, 1024
 dev = torch.device("cuda:0")
 L, st = _hip.lib(), _hip.stream()
@@ -34,7 +39,7 @@ nfb = (n_par + 63) // 64
 scratch = torch.zeros(28 * nfb // 8 + 1, dtype=torch.int64, device=dev)
 loss = torch.zeros(64, device=dev)
 ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-t_plan, t_steps, t_end = [], [], []
+t_plan, t_steps, t_end, t_each = [], [], [], []
 t = 0
 for blk in range(n_blocks):
     o = 4 * blk * k * b
@@ -44,11 +49,16 @@ for blk in range(n_blocks):
                                     meta.data_ptr(), sb.data_ptr(), sf.data_ptr(), ns.data_ptr(), st))
     e[1].record()
     rc = 0
+    es = [ev() for _ in range(k + 1)] if per_step else None
     for s in range(k):
+        if per_step:
+            es[s].record()
         q = o + 4 * s * b
         rc |= L.skr_bpr_fused_step(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, u.data_ptr() + q,
                                    i.data_ptr() + q, j.data_ptr() + q, meta.data_ptr() + 20 * s * b, b, 0, nU, nU + nI, 1e-3, 0.9, 0.999,
                                    1e-8, t, k, s, 1e-3, loss.data_ptr(), st)
+    if per_step:
+        es[k].record()
     e[2].record()
     rc |= L.skr_bpr_fused_end(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, sb.data_ptr(), sf.data_ptr(),
                               ns.data_ptr(), 1e-3, 0.9, 0.999, 1e-8, t, k, None, 0, 0, st)
@@ -57,10 +67,15 @@ for blk in range(n_blocks):
     t += k
     torch.cuda.synchronize()
     t_plan.append(e[0].elapsed_time(e[1])); t_steps.append(e[1].elapsed_time(e[2])); t_end.append(e[2].elapsed_time(e[3]))
+    if per_step:
+        t_each.append([es[s].elapsed_time(es[s + 1]) for s in range(k)])
 h = n_blocks // 2
 print(f"k={k} dbg={os.environ.get('SKR_FUSED_DBG', '0')}: "
       f"plan {np.mean(t_plan[h:]) * 1e3:.1f} us/block, steps {np.mean(t_steps[h:]) * 1e3 / k:.2f} us/step, end {np.mean(t_end[h:]) * 1e3:.1f} us/block"
       f"  (slots {int(ns)})")
+if per_step:
+    each = np.mean(np.array(t_each[h:]), axis=0) * 1e3
+    print("per-step us, step index 0 .. k-1: " + " ".join(f"{x:.2f}" for x in each))
 if os.environ.get("SKR_FUSED_STATS") == "1":
     import ctypes
     cen = (ctypes.c_uint64 * 34)()
