@@ -544,11 +544,11 @@ static int bpr_step_launch(const float* d_P, const float* d_Q, const float* d_bi
                 shard_world);
     SKR_REQUIRE(n >= 0, "skr_bpr_step: negative batch size");
     SKR_REQUIRE(!d_touch || d_touch_base, "skr_bpr_step: d_touch needs d_touch_base");
+    SKR_REQUIRE(dim == 64 || dim == 128 || dim == 192 || dim == 256, "skr_bpr_step: dim must be 64, 128, 192 or 256 (got %d); pad narrower "
+                "rows with zeros", dim);
     if (n == 0) return SKR_OK;
     int blocks = (n + BPR_WAVES - 1) / BPR_WAVES;
     if (blocks > 4096) blocks = 4096;
-    SKR_REQUIRE(dim == 64 || dim == 128 || dim == 192 || dim == 256, "skr_bpr_step: dim must be 64, 128, 192 or 256 (got %d); pad narrower "
-                "rows with zeros", dim);
 #define SKR_BPR_LAUNCH(C_)                                                                                                       \
     hipLaunchKernelGGL(bpr_step_kernel<C_>, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_P, d_Q, d_bias,     \
                        d_RP, d_RQ, d_u, d_i, d_j, n, loss_scale, reg, reg_scale, d_gP, d_gQ, d_gb, d_gRP, d_gRQ, d_loss,        \

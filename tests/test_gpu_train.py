@@ -733,6 +733,21 @@ def test_unpack_grad_rows_sorted_equals_per_rank_launches(n_ranks, cap, n_items)
     assert torch.equal(outs[0][0].view(torch.int32), outs[1][0].view(torch.int32))
     assert torch.equal(outs[0][1], outs[1][1])
     assert not torch.equal(outs[0][0], flat())                             # something was added
+    # ... and both are the float32 sum in rank order, ((g0 + r0) + r1) + ..., done in numpy: dense rows, bias words; the touch bytes
+    # are exactly the blocks of the ids present (a mistake the two kernels share -- the bias word, the id column, the touch index
+    # of the bias -- does not cancel here)
+    want, pk, idn = flat().cpu().numpy(), packs.cpu().numpy(), ids.cpu().numpy()
+    V, b = want[:n_items * 64].reshape(n_items, 64), want[n_items * 64:]
+    want_t = np.zeros((len(want) + 63) // 64, np.uint8)
+    for r in range(n_ranks):
+        v = idn[r] >= 0
+        V[idn[r][v]] = V[idn[r][v]] + pk[r][v, 1:65]
+        b[idn[r][v]] = b[idn[r][v]] + pk[r][v, 65]
+        want_t[idn[r][v]] = 1
+        want_t[n_items + idn[r][v] // 64] = 1
+    for buf, touch in outs:
+        assert np.array_equal(buf.cpu().numpy().view(np.int32), want.view(np.int32))
+        assert np.array_equal(touch.cpu().numpy(), want_t)
 
 
 @pytest.mark.gpu

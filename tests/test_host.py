@@ -414,3 +414,79 @@ def test_on_compute_stream_is_a_passthrough_without_a_gpu(monkeypatch):
     assert M().fit(1, b=5) == 6 and M.fit.__doc__ == "doc"
     monkeypatch.setenv("SKR_COMPUTE_STREAM", "0")
     assert M().fit(1) == 3
+
+
+def test_bpr_step_argument_checks():
+    """skr_bpr_step and its siblings refuse a bad width (96, 320: also on an empty batch), loss_slots other than 1 or 32, a shard
+    rank outside its world, touch bytes without their base and a negative batch size; every check returns before any HIP call, and an
+    empty batch of a valid width returns SKR_OK without touching anything"""
+    from skrec import _hip
+    L = _hip.lib()
+    bufs = [np.full(256, 3.0, np.float32) for _ in range(8)]
+    ids = [np.zeros(4, np.int32) for _ in range(3)]
+    loss = np.full(64, 3.0, np.float32)
+    touch = np.full(8, 3, np.uint8)
+    P, Q, b, gP, gQ, gb = (x.ctypes.data for x in bufs[:6])
+    u, i, j = (x.ctypes.data for x in ids)
+    lw, tw = loss.ctypes.data, touch.ctypes.data
+
+    def dim_(n=4, dim=64, slots=1, touch_=None, base=None):
+        return L.skr_bpr_step_dim(P, Q, b, P, Q, u, i, j, n, dim, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, slots, touch_, base, 1.0, None)
+
+    def sharded(n=4, world=2, rank=0, touch_=None, base=None):
+        return L.skr_bpr_step_sharded(P, Q, b, P, Q, u, i, j, n, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, touch_, base, world, rank, 1.0, None)
+    for n in (4, 0):
+        for dim in (96, 320, 0, 65, -64):
+            assert dim_(n=n, dim=dim) == -1 and str(dim).encode() in L.skr_last_error()
+    assert dim_(slots=2) == -1 and dim_(slots=0) == -1 and dim_(slots=33) == -1
+    assert sharded(rank=2) == -1 and sharded(rank=3) == -1 and sharded(world=0) == -1 and sharded(rank=-1) == -1
+    assert sharded(world=1, rank=1) == -1
+    assert dim_(touch_=tw) == -1 and sharded(touch_=tw) == -1
+    assert L.skr_bpr_step(P, Q, b, P, Q, u, i, j, 4, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, tw, None, None) == -1
+    assert L.skr_bpr_step_spread(P, Q, b, P, Q, u, i, j, 4, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, tw, None, None) == -1
+    assert dim_(n=-1) == -1 and sharded(n=-1) == -1
+    assert L.skr_bpr_step(P, Q, b, P, Q, u, i, j, -5, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, None, None, None) == -1
+    assert L.skr_bpr_step(None, Q, b, P, Q, u, i, j, 0, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, None, None, None) == -1
+    # the empty batch of a valid width: SKR_OK from every entry point, nothing written
+    for dim in (64, 128, 192, 256):
+        for slots in (1, 32):
+            assert dim_(n=0, dim=dim, slots=slots, touch_=tw, base=gP) == 0
+    assert sharded(n=0, world=3, rank=2, touch_=tw, base=gP) == 0
+    assert L.skr_bpr_step(P, Q, None, P, Q, u, i, j, 0, 1.0, 1e-3, 1.0, gP, gQ, None, gP, gQ, lw, None, None, None) == 0
+    assert L.skr_bpr_step_spread(P, Q, b, P, Q, u, i, j, 0, 1.0, 1e-3, 1.0, gP, gQ, gb, gP, gQ, lw, tw, gP, None) == 0
+    assert all((x == 3.0).all() for x in bufs) and (loss == 3.0).all() and (touch == 3).all()
+
+
+def test_row_helper_and_exchange_argument_checks():
+    """the width and NULL checks of the row helpers, the exchange and the plan-free product return before any HIP call; their empty
+    calls are SKR_OK"""
+    from skrec import _hip
+    L = _hip.lib()
+    a = np.full(256, 3.0, np.float32)
+    ids = np.zeros(4, np.int32)
+    p, q = a.ctypes.data, ids.ctypes.data
+    assert L.skr_pack_grad_rows(q, 4, p, None, 128, p, None) == -1 and L.skr_pack_grad_rows(None, 4, p, None, 64, p, None) == -1
+    assert L.skr_pack_grad_rows(q, 0, p, None, 64, p, None) == 0
+    for fn in (L.skr_unpack_grad_rows, L.skr_unpack_grad_rows_sorted):
+        assert fn(p, 4, 2, p, None, 32, None, None, None) == -1 and fn(None, 4, 2, p, None, 64, None, None, None) == -1
+        assert fn(p, 4, 2, p, None, 64, p, None, None) == -1 and fn(p, 4, 2, p, None, 64, None, p, None) == -1    # touch: both or neither
+        assert fn(p, 0, 2, p, None, 64, None, None, None) == 0 and fn(p, 4, 0, p, None, 64, None, None, None) == 0
+    assert L.skr_gather_rows(p, q, 4, 0, p, None) == -1 and L.skr_scatter_rows(p, q, 4, 0, p, None) == -1
+    assert L.skr_gather_rows(p, None, 4, 64, p, None) == -1 and L.skr_scatter_rows(None, q, 4, 64, p, None) == -1
+    assert L.skr_gather_rows(p, q, 0, 64, p, None) == 0 and L.skr_scatter_rows(p, q, 0, 7, p, None) == 0
+    assert L.skr_sum_blocks(p, 0, 4, p, None) == -1 and L.skr_sum_blocks(p, 2, -1, p, None) == -1 and L.skr_sum_blocks(p, 2, 0, p, None) == 0
+    assert L.skr_axpy(1.0, None, p, 4, None) == -1 and L.skr_scale(1.0, None, 4, None) == -1 and L.skr_scale_copy(1.0, p, None, 4, None) == -1
+    assert L.skr_axpy(1.0, p, p, 0, None) == 0 and L.skr_scale(1.0, p, 0, None) == 0 and L.skr_scale_copy(1.0, p, p, 0, None) == 0
+    assert L.skr_clear_marked_rows(p, 4, 1, p, 0, None) == -1 and L.skr_clear_marked_rows(p, -1, 1, p, 64, None) == -1
+    assert L.skr_clear_marked_rows(None, 0, 1, None, 64, None) == 0
+    for dim in (32, 96, 320):
+        assert L.skr_layer_refine_fwd(p, p, 4, dim, p, p, None, None) == -1
+        assert L.skr_layer_refine_bwd(p, p, p, p, 4, dim, p, p, None) == -1
+        assert L.skr_layer_refine_bwd_masked(p, p, p, p, 4, dim, p, p, None, 0, None) == -1
+    assert L.skr_layer_refine_fwd(p, p, 0, 128, p, p, None, None) == 0 and L.skr_layer_refine_bwd(p, p, p, p, 0, 192, p, p, None) == 0
+    rp = np.zeros(5, np.int64).ctypes.data
+    assert L.skr_csr_spmm_strided(4, rp, q, p, p, 64, 32, 0, None, a[64:].ctypes.data, None, 1.0, None) == -1     # stride below 64
+    assert L.skr_csr_spmm_strided(4, rp, q, p, p, 128, 128, 0, None, a[64:].ctypes.data, None, 1.0, None) == -1   # dim is always 64
+    assert L.skr_csr_spmm_strided(4, rp, q, p, p, 64, 128, 0, None, p, None, 1.0, None) == -1                     # in place
+    assert L.skr_csr_spmm_strided(0, rp, q, p, p, 64, 128, 0, None, a[64:].ctypes.data, None, 1.0, None) == 0
+    assert (a == 3.0).all()
