@@ -1162,6 +1162,28 @@ int skr_bm3_step_timed(const skr_bm3_step_args* args, void* stream, float* h_ms)
  * (zero beyond dim): skr_eval_fused_topk ranks <d_Qu[u], d_Qi[i]>.  d_pred: SKR_BM3_PRED_FLOATS floats. */
 int skr_bm3_queries(const float* d_pred, const float* d_M, int n_users, int n_items, float* d_Qu, float* d_Qi, void* stream);
 
+/* ============================================================================================
+ * K -- k-nearest-neighbour lists of a feature table by cosine similarity (csrc/knn.hip)
+ * replaces: the item-graph construction of the reference's multimodal models -- X / |X|, torch.mm(X, X^T) as a dense
+ * [I, I] matrix and torch.topk per row (recommender/FREEDOM.py:126-129, LATTICE.py:67-90, MGCN.py:61-110).
+ * d_X is a feature table in the layout of section J: [n_rows][feat_ld] floats, 16-byte aligned, feat_ld a multiple of 4,
+ * zero beyond feat_dim.
+ * ========================================================================================== */
+#define SKR_KNN_MAX_K 32
+/* Bytes of d_work for skr_knn_topk (the rows' inverse norms); 0 unless n_rows > 0 and 1 <= k <= min(SKR_KNN_MAX_K, n_rows). */
+size_t skr_knn_workspace(int n_rows, int k);
+/* d_ids[i][0..k) = the k rows j with the largest s(i, j) = <X_i, X_j> / (max(|X_i|, 1e-12) max(|X_j|, 1e-12)), row i itself
+ * included, in descending order of s; equal similarities rank by ascending j.  d_sims[i][0..k) = those similarities, or NULL.
+ * WRITTEN: all n_rows * k entries of d_ids (and of d_sims), nothing else.
+ * The one deviation from the reference: a norm is clamped at 1e-12, so an all-zero row has similarity 0 to every row (its own
+ * list is the k lowest ids) where the reference's division yields NaN.
+ * Limits: 1 <= feat_dim <= SKR_BM3_MAX_FEAT, feat_dim <= feat_ld <= SKR_BM3_MAX_FEAT, 1 <= k <= SKR_KNN_MAX_K, k <= n_rows.
+ * The products run on v_mfma_f32_16x16x4_f32 with fp32 operands; the inverse norms (one small launch) scale the finished
+ * 64 x 256 tile, the table is never copied.  No [n_rows, n_rows] array nor any O(n_rows^2) array is formed: d_work holds
+ * n_rows floats.  Every sum has a fixed order and there is no atomic: two calls give the same bits. */
+int skr_knn_topk(const float* d_X, int n_rows, int feat_dim, int feat_ld, int k, int32_t* d_ids, float* d_sims, void* d_work,
+                 size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,8 @@ SIGNATURES = {
     "skr_bm3_step": (i32, [vp, vp]),
     "skr_bm3_step_timed": (i32, [vp, vp, vp]),
     "skr_bm3_queries": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "skr_knn_workspace": (sz, [i32, i32]),
+    "skr_knn_topk": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
 }
 
 
@@ -216,6 +218,7 @@ SKR_SELFCF_PRED_FLOATS = 64 * 64 + 64    # the predictor's block of the flat par
 SKR_BM3_MAX_BATCH, SKR_BM3_MAX_LAYERS, SKR_BM3_MAX_FEAT, SKR_BM3_GROUPS = 2048, 4, 4096, 7   # skr_bm3_step limits
 SKR_BM3_PRED_FLOATS = 64 * 64 + 64       # the predictor's block of BM3's parameter buffer
 SKR_BM3_DRAW_USER, SKR_BM3_DRAW_ITEM, SKR_BM3_DRAW_TEXT, SKR_BM3_DRAW_IMAGE = 0, 1, 2, 3   # the tables of the target draws
+SKR_KNN_MAX_K = 32                       # skr_knn_topk: neighbours per row
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 
