@@ -27,16 +27,20 @@
 //   2L plan runs     acc = G; acc = A-hat acc + G (the addend epilogue); the last writes acc / (L + 1) into the gradient
 //   addh_grad        the item rows' + h path: grad_i += G_i
 //
-// The MFMA operand mapping is selfcf.hip's: step kk of lane (r, g) carries k = 16 g + kk.  The cosine, its clamp and its
-// backward are selfcf.hip's expressions.
+// The MFMA operand mapping is mfma_tile.h's k = 16 g + kk.  The cosine, its clamp and its backward are selfcf.hip's
+// expressions.
 //
 // Determinism: there is no floating-point atomic anywhere in the step; every sum has a fixed order.
 #include "skr_common.h"
 #include "fast_rng.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <algorithm>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;          // columns of every table
 constexpr int LDP = 68;        // LDS row stride
@@ -48,81 +52,6 @@ constexpr int MAXF = SKR_BM3_MAX_FEAT;
 constexpr int PRED = SKR_BM3_PRED_FLOATS;
 constexpr int NB = 512;        // partial sums per side of the sums of squares
 constexpr float COS_EPS = 1e-8f;   // F.cosine_similarity's default
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__host__ __device__ inline int64_t round4(int64_t x) { return (x + 3) & ~static_cast<int64_t>(3); }
-
-// keep iff a 24-bit uniform keyed by (seed, step, table, idx) is >= rate
-__device__ __forceinline__ bool draw_keep(uint64_t seed, uint64_t step, uint64_t table, uint64_t idx, float rate) {
-    Xoshiro128pp g;
-    g.seed(seed, step, (table << 60) | idx);
-    return static_cast<float>(g.next() >> 8) * (1.0f / 16777216.0f) >= rate;
-}
-
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// a[kk] = row[16 g + kk] of the table's row `node` (zeros for node < 0): the lane's share of an A operand
-__device__ __forceinline__ void load_row_a(float a[16], const float* __restrict__ X, int64_t node, int g) {
-    if (node < 0) {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) a[kk] = 0.0f;
-        return;
-    }
-    const float4* p = reinterpret_cast<const float4*>(X + node * D + 16 * g);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-// acc[nb][rr] += sum_k A[4 g + rr][k] * B[16 nb + r][k]: a[] the lane's share of A's row r, sB rows of stride LDP
-__device__ __forceinline__ void tile_product(f32x4 acc[4], const float a[16], const float* __restrict__ sB, int r, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float4 w[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) w[nb] = *reinterpret_cast<const float4*>(sB + (nb * 16 + r) * LDP + 16 * g + 4 * q);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 0], w[nb].x, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 1], w[nb].y, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 2], w[nb].z, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 3], w[nb].w, acc[nb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void zero_acc(f32x4 acc[4]) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-}
-
-__device__ __forceinline__ int64_t checked(int id, int limit) { return id >= 0 && id < limit ? id : -1; }
-
-__device__ __forceinline__ void load_slab(float a[16], const float* __restrict__ s, int row, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(s + row * LDP + 16 * g + 4 * q);
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ float column_sum(const float* __restrict__ sXT, int col) {
-    float t = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(sXT + col * LDP + 4 * q);
-        t += (v.x + v.y) + (v.z + v.w);
-    }
-    return t;
-}
 
 // ------------------------------------------------------------------------------------------------
 // the device draws on their own (tests)
@@ -415,7 +344,7 @@ __global__ __launch_bounds__(HW * 64) void bm_batch_kernel(BatchParams p) {
         else load_row_a(xa, set == 2 ? p.Yt : p.Yv, validA ? bA : -1, g);
         f32x4 P[4];
         zero_acc(P);
-        tile_product(P, xa, sW, r, g);
+        tile_product<LDP>(P, xa, sW, r, g);
         // ---- D layout: lane (r, g) holds column 16 nb + r of the rows 4 g + rr
         f32x4 gp[4];
 #pragma unroll
@@ -474,10 +403,10 @@ __global__ __launch_bounds__(HW * 64) void bm_batch_kernel(BatchParams p) {
         for (int kk = 0; kk < 16; ++kk) sXT[(16 * g + kk) * LDP + wv * 16 + r] = xa[kk];
         __syncthreads();
         float ga[16];
-        load_slab(ga, sG, wv * 16 + r, g);
+        load_slab<LDP>(ga, sG, wv * 16 + r, g);
         f32x4 gx[4];
         zero_acc(gx);
-        tile_product(gx, ga, sWT, r, g);
+        tile_product<LDP>(gx, ga, sWT, r, g);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int bD = b0 + 4 * g + rr;
@@ -486,9 +415,9 @@ __global__ __launch_bounds__(HW * 64) void bm_batch_kernel(BatchParams p) {
             for (int nb = 0; nb < 4; ++nb) p.Gx[(static_cast<int64_t>(set) * p.n4 + bD) * D + nb * 16 + r] = gx[nb][rr];
         }
         float slab[16];
-        load_slab(slab, sGT, wv * 16 + r, g);
-        tile_product(dW, slab, sXT, r, g);
-        if (threadIdx.x < D) db += column_sum(sGT, threadIdx.x);
+        load_slab<LDP>(slab, sGT, wv * 16 + r, g);
+        tile_product<LDP>(dW, slab, sXT, r, g);
+        if (threadIdx.x < D) db += column_sum<LDP>(sGT, threadIdx.x);
     }
     float* out = p.part + static_cast<int64_t>(blockIdx.x) * PRED;
 #pragma unroll
@@ -497,27 +426,6 @@ __global__ __launch_bounds__(HW * 64) void bm_batch_kernel(BatchParams p) {
         for (int rr = 0; rr < 4; ++rr) out[(wv * 16 + 4 * g + rr) * D + nb * 16 + r] = dW[nb][rr];
     }
     if (threadIdx.x < D) out[D * D + threadIdx.x] = db;
-}
-
-// the predictor's gradient = the workgroups' partial sums in workgroup order
-__global__ __launch_bounds__(256) void bm_pred_reduce_kernel(const float* __restrict__ part, int n_wg, float* __restrict__ out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= PRED) return;
-    float t = 0.0f;
-    for (int w = 0; w < n_wg; ++w) t += part[static_cast<int64_t>(w) * PRED + e];
-    out[e] = t;
-}
-
-__device__ __forceinline__ float block_sum_1024(float v, float* s) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    s[t] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) s[t] += s[t + o];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 // loss[0] = the graph cosines, loss[1] = cl_weight * the modal cosines, loss[2] = reg (|M_u| + |M_i|) / I, loss[3] = their sum
@@ -562,22 +470,6 @@ __global__ __launch_bounds__(256) void bm_reg_fill_kernel(const float* __restric
         const float4 v = reinterpret_cast<const float4*>(M)[e];
         reinterpret_cast<float4*>(G)[e] = make_float4(c * v.x, c * v.y, c * v.z, c * v.w);
     }
-}
-
-// order_u [n] / order_i [n]: the positions of the user / item list sorted by (id, position) -- a rank by counting
-__global__ __launch_bounds__(256) void bm_rank_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ items, int n,
-                                                      int32_t* __restrict__ order_u, int32_t* __restrict__ order_i) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= 2 * n) return;
-    const int32_t* ids = k < n ? users : items;
-    const int kk = k < n ? k : k - n;
-    const int id = ids[kk];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-        const int o = ids[j];
-        rank += (o < id || (o == id && j < kk)) ? 1 : 0;
-    }
-    (k < n ? order_u : order_i)[rank] = kk;
 }
 
 // G[id] += the sum of the g_x rows whose list entry is id, in rank order, by the wavefront of the id's first rank: one
@@ -644,20 +536,6 @@ __global__ __launch_bounds__(HW * 64) void bm_queries_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct Marker {                // h_ms: an event after every launch group (the profiling entry); otherwise nothing
-    float* h_ms;
-    hipStream_t st;
-    hipEvent_t ev[SKR_BM3_GROUPS + 1];
-    int n_ev;
-    hipError_t mark() {
-        if (h_ms == nullptr) return hipSuccess;
-        if (n_ev > SKR_BM3_GROUPS) return hipErrorInvalidValue;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    }
-};
-
 struct StepLayout {            // float offsets into the step's workspace
     int64_t Gx, Y, lossb, part, ordu, ordi, Gseg, head, npart, ss, total;
 };
@@ -736,7 +614,7 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
     const float* pred = a->params + N * D;
     const float s = 1.0f / static_cast<float>(L + 1);
     float* Y[2] = {a->feat_dim[0] ? w + W.Y : nullptr, a->feat_dim[1] ? w + W.Y + n4 * D : nullptr};
-    Marker mk = {h_ms, st, {}, 0};
+    StepTimer<SKR_BM3_GROUPS + 1> mk(h_ms, st);        // h_ms: an event after every launch group; otherwise nothing
     SKR_HIP(mk.mark());
     if (a->n_clear > 0 && (a->feat_dim[0] || a->feat_dim[1])) {
         ClearParams cp = {{a->feat_dim[0] ? a->feat_grad[0] : nullptr, a->feat_dim[1] ? a->feat_grad[1] : nullptr}, {a->feat_ld[0], a->feat_ld[1]}};
@@ -788,13 +666,13 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
     bp.seed = a->seed; bp.step = a->step;
     bp.Gx = w + W.Gx; bp.lossb = w + W.lossb; bp.part = w + W.part;
     hipLaunchKernelGGL(bm_batch_kernel, dim3(n_wg), dim3(HW * 64), 0, st, bp);
-    hipLaunchKernelGGL(bm_pred_reduce_kernel, dim3((PRED + 255) / 256), dim3(256), 0, st, w + W.part, n_wg, a->grad + N * D);
+    hipLaunchKernelGGL(part_reduce_kernel<PRED>, dim3((PRED + 255) / 256), dim3(256), 0, st, w + W.part, n_wg, a->grad + N * D);
     hipLaunchKernelGGL(bm_loss_kernel, dim3(1), dim3(1024), 0, st, w + W.lossb, n, n4, Y[1] != nullptr ? 1 : 0, Y[0] != nullptr ? 1 : 0, a->cl_weight,
                        a->reg, I, w + W.ss, a->loss);
     SKR_LAUNCH_CHECK();
     SKR_HIP(mk.mark());
     // ---- the projection backward: dY = the g_x rows of the modality's row set (text: 2, image: 3)
-    hipLaunchKernelGGL(bm_rank_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, st, a->users, a->items, n, ordu, ordi);
+    hipLaunchKernelGGL(rank_lists_kernel<256>, dim3((2 * n + 255) / 256), dim3(256), 0, st, a->users, a->items, n, ordu, ordi);
     const int blocks = (n + HW - 1) / HW;
     for (int m = 0; m < 2; ++m) {
         if (a->feat_dim[m] == 0) continue;
@@ -846,11 +724,7 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
         SKR_LAUNCH_CHECK();
     }
     SKR_HIP(mk.mark());
-    if (h_ms != nullptr) {
-        SKR_HIP(hipEventSynchronize(mk.ev[mk.n_ev - 1]));
-        for (int k = 0; k + 1 < mk.n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], mk.ev[k], mk.ev[k + 1]));
-        for (int k = 0; k < mk.n_ev; ++k) SKR_HIP(hipEventDestroy(mk.ev[k]));
-    }
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 

@@ -16,10 +16,14 @@
 // Gradient rows are WRITTEN, not added to: the rows a batch does not name stay as the optimiser left them (zero).
 #include "skr_common.h"
 #include "fast_rng.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <cmath>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;
 constexpr int HW = 4;          // wavefronts per workgroup: item side (thousands of distinct items) and queries
@@ -40,12 +44,6 @@ __device__ __forceinline__ float4 fma4(float s, const float4& a, const float4& b
     return make_float4(fmaf(s, a.x, b.x), fmaf(s, a.y, b.y), fmaf(s, a.z, b.z), fmaf(s, a.w, b.w));
 }
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-// sum over the 16 lanes of a row group: every lane of the group gets it
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // the four row groups' partial sums: (g0 + g1) + (g2 + g3) in every lane
 __device__ __forceinline__ float groups(float v) {
     v += __shfl_xor(v, 16, 64);
@@ -65,12 +63,6 @@ __device__ __forceinline__ float4 act4(const float4& v) {
     return make_float4(sigmoidf(v.x), sigmoidf(v.y), sigmoidf(v.z), sigmoidf(v.w));
 }
 
-__device__ __forceinline__ bool keep_draw(uint64_t seed, uint64_t step, int user, int item, float keep_prob) {
-    Xoshiro128pp g;
-    g.seed(seed, step, (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(item));
-    return static_cast<float>(g.next() >> 8) * 0x1p-24f < keep_prob;
-}
-
 // sum of v over the workgroup's threads in a fixed order (a tree over the thread index); the result in thread 0
 __device__ __forceinline__ float block_sum(float v, float* s) {
     const int t = threadIdx.x;
@@ -88,7 +80,6 @@ __device__ __forceinline__ float block_sum(float v, float* s) {
 struct Work {                  // float offsets into the workspace
     int64_t h, dpre, dr, bce, l2u, l2i, total;
 };
-__host__ __device__ inline int64_t round4(int64_t x) { return (x + 3) & ~static_cast<int64_t>(3); }
 inline Work work_layout(int n, int64_t n_pairs) {
     Work w;
     int64_t o = 0;
@@ -331,50 +322,25 @@ static int cdae_run_step(const float* d_E_en, const float* d_E_de, const float* 
     float* w = static_cast<float*>(d_work);
     hipStream_t st = skr::as_stream(stream);
     const float inv_keep = 1.0f / keep_prob;
-    hipEvent_t ev[SKR_CDAE_LAUNCHES + 1] = {};
-    int n_ev = 0;
-    auto mark = [&]() -> hipError_t {
-        if (h_ms == nullptr) return hipSuccess;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    };
-    auto drop = [&]() {                                                // the timed variant's events, on every way out
-        for (int k = 0; k < n_ev; ++k) (void)hipEventDestroy(ev[k]);
-        n_ev = 0;
-    };
-#define SKR_CDAE_MARK()                                                  \
-    do {                                                                 \
-        const hipError_t e_ = mark();                                    \
-        if (e_ != hipSuccess) {                                          \
-            drop();                                                      \
-            SKR_HIP(e_);                                                 \
-        }                                                                \
-    } while (0)
-    SKR_CDAE_MARK();
+    StepTimer<SKR_CDAE_LAUNCHES + 1> mk(h_ms, st);     // h_ms: an event after every launch; otherwise nothing
+    SKR_HIP(mk.mark());
 #define SKR_CDAE_USER(A_)                                                                                                         \
     hipLaunchKernelGGL(cdae_user_kernel<A_>, dim3((n + UW - 1) / UW), dim3(UW * 64), 0, st, d_E_en, d_E_de, d_bias, d_offset, d_U, \
                        d_users, d_uptr, d_pitem, d_plabel, d_pkeep, n, n_pairs, n_users, n_items, dim, inv_keep, reg, d_gU,       \
                        w + W.h, w + W.dpre, w + W.dr, w + W.bce, w + W.l2u)
     if (act == SKR_CDAE_SIGMOID) SKR_CDAE_USER(1); else SKR_CDAE_USER(0);
 #undef SKR_CDAE_USER
-    SKR_CDAE_MARK();
+    SKR_HIP(mk.mark());
     if (n_distinct > 0)
         hipLaunchKernelGGL(cdae_item_kernel, dim3((n_distinct + HW - 1) / HW), dim3(HW * 64), 0, st, d_E_en, d_E_de, d_bias, d_uptr,
                            d_pkeep, d_puser, d_ditems, d_iptr, d_ipair, n, n_pairs, n_distinct, n_items, inv_keep, reg, w + W.h,
                            w + W.dpre, w + W.dr, d_gE_en, d_gE_de, d_gbias, w + W.l2i);
-    SKR_CDAE_MARK();
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(cdae_finish_kernel, dim3(1), dim3(1024), 0, st, d_offset, n, n_distinct, reg, w + W.dpre, w + W.bce,
                        w + W.l2u, w + W.l2i, d_goffset, d_loss);
-    SKR_CDAE_MARK();
-#undef SKR_CDAE_MARK
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && h_ms != nullptr) {
-        e = hipEventSynchronize(ev[n_ev - 1]);
-        for (int k = 0; e == hipSuccess && k + 1 < n_ev; ++k) e = hipEventElapsedTime(&h_ms[k], ev[k], ev[k + 1]);
-    }
-    drop();
-    SKR_HIP(e);
+    SKR_HIP(mk.mark());
+    SKR_LAUNCH_CHECK();
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 

@@ -24,17 +24,19 @@
 //   rank, seg_add  the gradient rows into G_h, per distinct node id, in rank order
 //   2H plan runs   acc = G_H; acc = A-hat acc + G_h for h = H-1 .. 0 (the addend epilogue); the last writes the gradient
 //
-// A lane's slice of a product's K dimension: the fp32 MFMA sums over four k per step, one per 16-lane group g; step kk of
-// lane (r, g) carries k = 16 g + kk, so that the 16 steps of a lane read 16 CONSECUTIVE floats of an operand row -- four
-// 16-byte LDS reads instead of sixteen 4-byte ones, and A operands come straight from global rows as four float4.
+// The MFMA operand mapping is mfma_tile.h's k = 16 g + kk.
 //
 // Determinism: there is no floating-point atomic anywhere in the step.
 #include "skr_common.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;          // columns of every table
 constexpr int LDP = 68;        // LDS row stride
@@ -47,11 +49,7 @@ constexpr int GATE = D * D + D;   // floats of one gate block
 constexpr int NGATE = 4;          // user, item, pos, neg
 constexpr int MAX_WG = SKR_DENS_MAX_WG;
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 struct Tables { const float* x[MAXH + 1]; };
-
-__host__ __device__ inline int64_t round4(int64_t x) { return (x + 3) & ~static_cast<int64_t>(3); }
 
 __device__ __forceinline__ const float* hop_table(const Tables& T, int h) {
     return h == 0 ? T.x[0] : h == 1 ? T.x[1] : h == 2 ? T.x[2] : T.x[3];
@@ -59,12 +57,6 @@ __device__ __forceinline__ const float* hop_table(const Tables& T, int h) {
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
-
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // the four gates into LDS: sW[m][row][col], row stride LDP; transposed: sW[m][in][out] = W_m[out][in]
 __device__ __forceinline__ void load_gates(float* __restrict__ sW, const float* __restrict__ gates, bool transposed) {
@@ -82,46 +74,6 @@ __device__ __forceinline__ void load_gates(float* __restrict__ sW, const float* 
         }
     }
 }
-
-// a[kk] = row[16 g + kk] of the table's row `node` (zeros for node < 0): the lane's share of an A operand
-__device__ __forceinline__ void load_row_a(float a[16], const float* __restrict__ X, int64_t node, int g) {
-    if (node < 0) {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) a[kk] = 0.0f;
-        return;
-    }
-    const float4* p = reinterpret_cast<const float4*>(X + node * D + 16 * g);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-// acc[nb][rr] += sum_k A[4 g + rr][k] * B[16 nb + r][k]: a[] the lane's share of A's row r, sB rows of stride LDP
-__device__ __forceinline__ void tile_product(f32x4 acc[4], const float a[16], const float* __restrict__ sB, int r, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float4 w[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) w[nb] = *reinterpret_cast<const float4*>(sB + (nb * 16 + r) * LDP + 16 * g + 4 * q);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 0], w[nb].x, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 1], w[nb].y, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 2], w[nb].z, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 3], w[nb].w, acc[nb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void zero_acc(f32x4 acc[4]) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-}
-
-__device__ __forceinline__ int64_t checked(int id, int limit) { return id >= 0 && id < limit ? id : -1; }
 
 // ------------------------------------------------------------------------------------------------
 // select: gates, scores and the arg-max of (64 batch rows, one hop)
@@ -162,8 +114,8 @@ __global__ __launch_bounds__(HW * 64) void dn_select_kernel(Tables T, const floa
     __syncthreads();
     f32x4 acc[4];
     zero_acc(acc);
-    tile_product(acc, pa, sW + 1 * D * LDP, r, g);
-    tile_product(acc, sa, sW + 0 * D * LDP, r, g);
+    tile_product<LDP>(acc, pa, sW + 1 * D * LDP, r, g);
+    tile_product<LDP>(acc, sa, sW + 0 * D * LDP, r, g);
     f32x4 sD[4];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
@@ -187,7 +139,7 @@ __global__ __launch_bounds__(HW * 64) void dn_select_kernel(Tables T, const floa
     }
     f32x4 qv[4];
     zero_acc(qv);
-    tile_product(qv, pra, sW + 2 * D * LDP, r, g);
+    tile_product<LDP>(qv, pra, sW + 2 * D * LDP, r, g);
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
         const int col = nb * 16 + r;
@@ -209,7 +161,7 @@ __global__ __launch_bounds__(HW * 64) void dn_select_kernel(Tables T, const floa
         f32x4 z[4];
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) z[nb] = qv[nb];
-        tile_product(z, ca, sW + 3 * D * LDP, r, g);
+        tile_product<LDP>(z, ca, sW + 3 * D * LDP, r, g);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int64_t cD = bD[rr] < n ? checked(cand[static_cast<int64_t>(bD[rr]) * K + k], I) : -1;
@@ -310,18 +262,6 @@ __global__ __launch_bounds__(HW * 64) void dn_pool_kernel(Tables T, const int32_
     }
 }
 
-__device__ __forceinline__ float block_sum_1024(float v, float* s) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    s[t] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) s[t] += s[t + o];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 // loss[0] = mf (DENS.py:333, :361-366), loss[1] = emb (:369-372), loss[2] = their sum
 __global__ __launch_bounds__(1024) void dn_loss_kernel(const float* __restrict__ lossb, int n, float gamma, float l2,
                                                        float* __restrict__ loss) {
@@ -347,24 +287,6 @@ __global__ __launch_bounds__(1024) void dn_loss_kernel(const float* __restrict__
 __device__ __forceinline__ void store_transposed(float* __restrict__ sXT, const float a[16], int row, int g) {
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) sXT[(16 * g + kk) * LDP + row] = a[kk];
-}
-
-__device__ __forceinline__ void load_slab(float a[16], const float* __restrict__ sXT, int row, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(sXT + row * LDP + 16 * g + 4 * q);
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ float column_sum(const float* __restrict__ sXT, int col) {
-    float t = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(sXT + col * LDP + 4 * q);
-        t += (v.x + v.y) + (v.z + v.w);
-    }
-    return t;
 }
 
 __device__ __forceinline__ void load_vec_a(float a[16], const float* __restrict__ rows, int64_t row, int g) {
@@ -421,15 +343,15 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
         store_transposed(sX1, tmp, wv * 16 + r, g);
         __syncthreads();
         float slab[16];
-        load_slab(slab, sG, wv * 16 + r, g);
-        if (threadIdx.x < D) dbz += column_sum(sG, threadIdx.x);
-        tile_product(dW[3], slab, sX0, r, g);
-        tile_product(dW[2], slab, sX1, r, g);
+        load_slab<LDP>(slab, sG, wv * 16 + r, g);
+        if (threadIdx.x < D) dbz += column_sum<LDP>(sG, threadIdx.x);
+        tile_product<LDP>(dW[3], slab, sX0, r, g);
+        tile_product<LDP>(dW[2], slab, sX1, r, g);
         f32x4 mm1[4], mm2[4];
         zero_acc(mm1);
         zero_acc(mm2);
-        tile_product(mm1, dz, sWT + 3 * D * LDP, r, g);
-        tile_product(mm2, dz, sWT + 2 * D * LDP, r, g);
+        tile_product<LDP>(mm1, dz, sWT + 3 * D * LDP, r, g);
+        tile_product<LDP>(mm2, dz, sWT + 2 * D * LDP, r, g);
         // ---- D layout: rows 4 g + rr, column 16 nb + r
         f32x4 daD[4], dpg[4], pDv[4];
         int64_t rowD[4];
@@ -475,17 +397,17 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
         load_row_a(tmp, XA, uA, g);                                      // s
         store_transposed(sX1, tmp, wv * 16 + r, g);
         __syncthreads();
-        load_slab(slab, sG, wv * 16 + r, g);
+        load_slab<LDP>(slab, sG, wv * 16 + r, g);
         float daA[16];
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) daA[kk] = sG[(16 * g + kk) * LDP + wv * 16 + r];
-        if (threadIdx.x < D) dba += column_sum(sG, threadIdx.x);
-        tile_product(dW[1], slab, sX0, r, g);
-        tile_product(dW[0], slab, sX1, r, g);
+        if (threadIdx.x < D) dba += column_sum<LDP>(sG, threadIdx.x);
+        tile_product<LDP>(dW[1], slab, sX0, r, g);
+        tile_product<LDP>(dW[0], slab, sX1, r, g);
         zero_acc(mm1);
         zero_acc(mm2);
-        tile_product(mm1, daA, sWT + 1 * D * LDP, r, g);
-        tile_product(mm2, daA, sWT + 0 * D * LDP, r, g);
+        tile_product<LDP>(mm1, daA, sWT + 1 * D * LDP, r, g);
+        tile_product<LDP>(mm2, daA, sWT + 0 * D * LDP, r, g);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             if (rowD[rr] >= R) continue;
@@ -520,15 +442,6 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
         out[2 * GATE + D * D + threadIdx.x] = dbz;
         out[3 * GATE + D * D + threadIdx.x] = dbz;
     }
-}
-
-// the gates' gradient = the workgroups' partial sums in workgroup order
-__global__ __launch_bounds__(256) void dn_gate_reduce_kernel(const float* __restrict__ part, int n_wg, float* __restrict__ out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= NGATE * GATE) return;
-    float t = 0.0f;
-    for (int w = 0; w < n_wg; ++w) t += part[static_cast<int64_t>(w) * NGATE * GATE + e];
-    out[e] = t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -602,20 +515,6 @@ __global__ __launch_bounds__(HW * 64) void dn_seg_add_kernel(GradTables G, const
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct Marker {                // h_ms: an event after every launch group (the profiling entry); otherwise nothing
-    float* h_ms;
-    hipStream_t st;
-    hipEvent_t ev[SKR_DENS_GROUPS + 1];
-    int n_ev;
-    hipError_t mark() {
-        if (h_ms == nullptr) return hipSuccess;
-        if (n_ev > SKR_DENS_GROUPS) return hipErrorInvalidValue;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    }
-};
-
 struct StepLayout {            // float offsets into the step's workspace
     int64_t gp, gn, PG, Gs, Gp, Gc, lossb, part, selitem, ordu, ordi, total;
 };
@@ -685,7 +584,7 @@ int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
     Tables T = {};
     T.x[0] = a->params;
     for (int h = 1; h <= MAXH; ++h) T.x[h] = h <= H ? a->hop[h - 1] : a->params;
-    Marker mk = {h_ms, st, {}, 0};
+    StepTimer<SKR_DENS_GROUPS + 1> mk(h_ms, st);       // h_ms: an event after every launch group; otherwise nothing
     SKR_HIP(mk.mark());
     // ---- forward (DENS.py:125-134): X_h = A-hat X_(h-1)
     for (int h = 1; h <= H; ++h) {
@@ -709,7 +608,7 @@ int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
     const int chunks = static_cast<int>((static_cast<int64_t>(n) * (H + 1) + TB - 1) / TB);
     hipLaunchKernelGGL(dn_back_kernel, dim3(n_wg), dim3(HW * 64), 0, st, T, gates, a->uids, a->pos, selitem, n, U, I, H,
                        a->l2 / static_cast<float>(n), w + L.gp, w + L.gn, w + L.PG, w + L.Gs, w + L.Gp, w + L.Gc, w + L.part, chunks);
-    hipLaunchKernelGGL(dn_gate_reduce_kernel, dim3((NGATE * GATE + 255) / 256), dim3(256), 0, st, w + L.part, n_wg, a->grad + N * D);
+    hipLaunchKernelGGL(part_reduce_kernel<NGATE * GATE>, dim3((NGATE * GATE + 255) / 256), dim3(256), 0, st, w + L.part, n_wg, a->grad + N * D);
     SKR_LAUNCH_CHECK();
     SKR_HIP(mk.mark());
     // ---- the gradient rows into the cleared hop tables (hop 0's is the gradient itself when there is no propagation)
@@ -735,11 +634,7 @@ int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
         }
     }
     SKR_HIP(mk.mark());
-    if (h_ms != nullptr) {
-        SKR_HIP(hipEventSynchronize(mk.ev[mk.n_ev - 1]));
-        for (int k = 0; k + 1 < mk.n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], mk.ev[k], mk.ev[k + 1]));
-        for (int k = 0; k < mk.n_ev; ++k) SKR_HIP(hipEventDestroy(mk.ev[k]));
-    }
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 

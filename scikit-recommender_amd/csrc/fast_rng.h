@@ -1,5 +1,7 @@
-// fast_rng.h -- the counter-keyed generator of the fast sampler (sampler.hip) and of MultVAE's device draws
-// (multvae.hip): splitmix64 turns (seed, epoch, slot) into the state of a xoshiro128++ stream of that slot alone.
+// fast_rng.h -- the counter-keyed generator of the fast sampler (sampler.hip) and of the models' device draws:
+// splitmix64 turns (seed, epoch, slot) into the state of a xoshiro128++ stream of that slot alone.  The two dropout
+// draws below key a slot by what they drop: draw_keep an element of a numbered stream (selfcf.hip, bm3.hip), keep_draw
+// a (user, item) pair (cdae.hip, multvae.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,3 +36,17 @@ struct Xoshiro128pp {
         return r;
     }
 };
+
+// keep iff a 24-bit uniform is >= rate.  Slot: the stream's number in the top 4 bits, the element's index below them.
+__device__ __forceinline__ bool draw_keep(uint64_t seed, uint64_t step, uint64_t stream, uint64_t idx, float rate) {
+    Xoshiro128pp g;
+    g.seed(seed, step, (stream << 60) | idx);
+    return static_cast<float>(g.next() >> 8) * (1.0f / 16777216.0f) >= rate;
+}
+
+// keep iff a 24-bit uniform is < keep_prob.  Slot: the user in the upper 32 bits, the item in the lower 32.
+__device__ __forceinline__ bool keep_draw(uint64_t seed, uint64_t step, int user, int item, float keep_prob) {
+    Xoshiro128pp g;
+    g.seed(seed, step, (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(item));
+    return static_cast<float>(g.next() >> 8) * 0x1p-24f < keep_prob;
+}

@@ -20,13 +20,16 @@
 //
 // No [n, n] array and no O(n^2) array exists anywhere: the similarities live in accumulators and one LDS tile.
 //
-// The MFMA operand mapping is bm3.hip's: step kk of lane (r, g) carries k = 8 g + kk of the chunk.
+// The MFMA operand mapping is mfma_tile.h's k = 8 g + kk of the chunk.
 //
 // Determinism: every dot product is summed in one fixed order by one wavefront, a row's list is owned by one wavefront,
 // and the order (similarity descending, id ascending) is total: two calls are bit-identical.  No atomic of any kind.
 #include "skr_common.h"
+#include "mfma_tile.h"
 
 namespace {
+
+using namespace skr;
 
 constexpr int TQ = 64;         // query rows of a workgroup: 16 per wavefront
 constexpr int TC = 256;        // table rows of a column block
@@ -42,8 +45,6 @@ constexpr float NORM_EPS = 1e-12f;
 static_assert(TQ * LDS_S <= TC * LDP, "the similarity tile takes the column tile's place");
 static_assert((TQ + TC) * LDP * 4 + TQ * MAXK * 8 <= 65536, "64 KiB of LDS per workgroup");
 static_assert(MAXK <= 32, "a row's list is held by the lower half of a wavefront");
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __global__ __launch_bounds__(HW * 64) void knn_inv_norm_kernel(const float* __restrict__ X, int n, int ld, float* __restrict__ inv) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -82,24 +83,6 @@ __device__ __forceinline__ Chunk fetch(const float* __restrict__ X, int n, int l
     v.b6 = fetch_row(X, n, ld, c + 192, kq);
     v.b7 = fetch_row(X, n, ld, c + 224, kq);
     return v;
-}
-
-// acc[nb][rr] += sum_k A[4 g + rr][k] * B[16 nb + r][k] over the chunk: a[] the lane's share of A's row r
-__device__ __forceinline__ void tile_product(f32x4 acc[4], const float a[8], const float* __restrict__ sB, int r, int g) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        float4 w[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) w[nb] = *reinterpret_cast<const float4*>(sB + (nb * 16 + r) * LDP + 8 * g + 4 * q);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 0], w[nb].x, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 1], w[nb].y, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 2], w[nb].z, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 3], w[nb].w, acc[nb], 0, 0, 0);
-    }
 }
 
 // The 64 columns col0.. of the finished tile, scaled by inv[q] inv[c], go through LDS into the lists of the wavefront's 16 rows,
@@ -194,7 +177,7 @@ __global__ __launch_bounds__(HW * 64, 2) void knn_topk_kernel(const float* __res
                 a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
             }
 #pragma unroll
-            for (int h = 0; h < 4; ++h) tile_product(acc[h], a, sB + h * 64 * LDP, r, g);
+            for (int h = 0; h < 4; ++h) tile_product<LDP>(acc[h], a, sB + h * 64 * LDP, r, g);
             if ((kc & (FLUSH - 1)) == FLUSH - 1 || wrap) {
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {

@@ -28,18 +28,23 @@
 //   2L plan runs   h^(l-1) = addend + A h^(l) (other side), the last one writes the gradient of E_0
 //   seg_add        dQ into the gradient of E_0 at the batch's rows
 //
-// The InfoNCE kernels are multvae.hip's decoder passes with the roles renamed: a wavefront owns 16 query rows (the A operand
-// of v_mfma_f32_16x16x4_f32, exact fp32), a workgroup of four a chunk of 64; workgroups are persistent over tiles of 64 table
-// rows; a tile is staged in LDS once per tile and chunk.  dE[tile] is written by the one workgroup that owns the tile (first
-// chunk stores, later chunks add -- the same thread every time), dQ is per-workgroup partials added in workgroup order.
+// The InfoNCE kernels are multvae.hip's decoder passes with the roles renamed (the MFMA operand mapping is mfma_tile.h's
+// k = 4 kk + g): a wavefront owns 16 query rows (the A operand of v_mfma_f32_16x16x4_f32, exact fp32), a workgroup of four a
+// chunk of 64; workgroups are persistent over tiles of 64 table rows; a tile is staged in LDS once per tile and chunk.
+// dE[tile] is written by the one workgroup that owns the tile (first chunk stores, later chunks add -- the same thread every
+// time), dQ is per-workgroup partials added in workgroup order.
 //
 // Determinism: there is no floating-point atomic anywhere in the step.
 #include "skr_common.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;          // columns of every table
 constexpr int QF = SKR_LIGHTGCL_MAX_Q;   // columns of a factor table
@@ -53,10 +58,6 @@ constexpr int MAX_N = SKR_LIGHTGCL_MAX_QUERIES;
 constexpr int LR_BLOCKS = 256; // row blocks of the low-rank reductions
 constexpr int SQ_BLOCKS = 1024;
 constexpr float LOG_EPS = -18.420680743952367f;   // log(1e-8)
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__host__ __device__ inline int64_t round4(int64_t x) { return (x + 3) & ~static_cast<int64_t>(3); }
 
 inline int n_workgroups(int n_rows) {
     const int tiles = (n_rows + TI - 1) / TI;
@@ -79,57 +80,6 @@ inline ClLayout cl_layout(int n, int n_wg) {
 // ------------------------------------------------------------------------------------------------
 // the InfoNCE term of one side
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tile_range(int tiles, int& t0, int& t1) {
-    t0 = static_cast<int>(static_cast<int64_t>(blockIdx.x) * tiles / gridDim.x);
-    t1 = static_cast<int>(static_cast<int64_t>(blockIdx.x + 1) * tiles / gridDim.x);
-}
-
-// E[row0 .. row0 + 64) into LDS, rows beyond the table as zeros
-__device__ __forceinline__ void load_tile(float* __restrict__ sW, const float* __restrict__ E, int row0, int n_rows) {
-    const float4* W4 = reinterpret_cast<const float4*>(E);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
-        const int gr = row0 + row;
-        v[i] = gr < n_rows ? W4[static_cast<int64_t>(gr) * 16 + c4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<float4*>(sW + row * LDP + c4 * 4) = v[i];
-    }
-}
-
-// the wavefront's query rows as the A operand of 16 k-steps: lane (r, g) holds Q[query r][4 kk + g]
-__device__ __forceinline__ void load_a(float a[16], const float* __restrict__ Q, int qb, int n, int r, int g) {
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) a[kk] = qb + r < n ? Q[static_cast<int64_t>(qb + r) * D + 4 * kk + g] : 0.0f;
-}
-
-// acc[nb][rr] = <Q[query 4 g + rr], E[row 16 nb + r]>
-__device__ __forceinline__ void logits_tile(f32x4 acc[4], const float a[16], const float* __restrict__ sW, int r, int g) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], sW[(nb * 16 + r) * LDP + 4 * kk + g], acc[nb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ float max16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // pass 1: part[wg][query] = (max, sum exp(s - max)) over the workgroup's tiles, s = <Q, E> / temp
 __global__ __launch_bounds__(HW * 64) void cl_pass1_kernel(const float* __restrict__ E, const float* __restrict__ Q, int n, int n4,
                                                            int n_rows, int tiles, float inv_temp, float* __restrict__ part) {
@@ -146,10 +96,10 @@ __global__ __launch_bounds__(HW * 64) void cl_pass1_kernel(const float* __restri
         for (int rr = 0; rr < 4; ++rr) { m[rr] = -INFINITY; s[rr] = 0.0f; }
         for (int t = t0; t < t1; ++t) {
             __syncthreads();
-            load_tile(sW, E, t * TI, n_rows);
+            load_tile<LDP, HW>(sW, E, t * TI, n_rows);
             __syncthreads();
             f32x4 acc[4];
-            logits_tile(acc, a, sW, r, g);
+            logits_tile<LDP>(acc, a, sW, r, g);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 float v[4];
@@ -238,10 +188,10 @@ __global__ __launch_bounds__(HW * 64) void cl_pass2_kernel(const float* __restri
         for (int t = t0; t < t1; ++t) {
             const int row0 = t * TI;
             __syncthreads();                               // the previous tile's products still read sW and sG
-            load_tile(sW, E, row0, n_rows);
+            load_tile<LDP, HW>(sW, E, row0, n_rows);
             __syncthreads();
             f32x4 acc[4];
-            logits_tile(acc, a, sW, r, g);
+            logits_tile<LDP>(acc, a, sW, r, g);
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
                 const bool in = row0 + nb * 16 + r < n_rows;
@@ -593,18 +543,6 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
     if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
-__device__ __forceinline__ float block_sum_1024(float v, float* s) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    s[t] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) s[t] += s[t + o];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 // loss[0] = the BPR mean, loss[1] = lambda1 (neg_score - pos_score), loss[2] = lambda2 |E_0|^2, loss[3] = their sum
 // (LightGCL.py:149-168); cl_loss[0 / 1] = lambda1 * the mean lse of the user / item side
 __global__ __launch_bounds__(1024) void bk_loss_kernel(const float* __restrict__ s_bpr, const float* __restrict__ s_posu,
@@ -634,23 +572,11 @@ __global__ __launch_bounds__(1024) void bk_loss_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct Marker {                // h_ms: an event after every launch group (the profiling entry); otherwise nothing
-    float* h_ms;
-    hipStream_t st;
-    hipEvent_t ev[SKR_LIGHTGCL_GROUPS + 1];
-    int n_ev;
-    hipError_t mark() {
-        if (h_ms == nullptr) return hipSuccess;
-        if (n_ev > SKR_LIGHTGCL_GROUPS) return hipErrorInvalidValue;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    }
-};
+using Timer = StepTimer<SKR_LIGHTGCL_GROUPS + 1>;   // h_ms: an event after every launch group; otherwise nothing
 
 // the launches of one side's InfoNCE term; mk (may be NULL) gets a mark behind pass 1 + merge and one behind pass 2 + reduce
 int cl_run(const float* d_Q, int n, const float* d_E, int n_rows, float inv_temp, float weight, float* d_dQ, float* d_dE,
-           float* d_loss, float* w, hipStream_t st, Marker* mk) {
+           float* d_loss, float* w, hipStream_t st, Timer* mk) {
     const int n_wg = n_workgroups(n_rows), tiles = (n_rows + TI - 1) / TI, n4 = static_cast<int>(round4(n));
     const ClLayout L = cl_layout(n, n_wg);
     hipLaunchKernelGGL(cl_pass1_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_E, d_Q, n, n4, n_rows, tiles, inv_temp, w + L.part);
@@ -739,7 +665,7 @@ int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
     int32_t* ordi = reinterpret_cast<int32_t*>(w + L.ordi);
     const int64_t UO = static_cast<int64_t>(U) * D;          // the item rows' offset in a flat table
     const int64_t N = static_cast<int64_t>(U) + I;
-    Marker mk = {h_ms, st, {}, 0};
+    Timer mk(h_ms, st);
     SKR_HIP(mk.mark());
     // ---- forward (LightGCL.py:117-137): layer l reads layer l - 1 of the other side; below = sum_{l<L}, sum = sum_{l<=L}
     const float* below = Ly == 1 ? a->E0 : a->below;
@@ -824,11 +750,7 @@ int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
         SKR_LAUNCH_CHECK();
     }
     SKR_HIP(mk.mark());
-    if (h_ms != nullptr) {
-        SKR_HIP(hipEventSynchronize(mk.ev[mk.n_ev - 1]));
-        for (int k = 0; k + 1 < mk.n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], mk.ev[k], mk.ev[k + 1]));
-        for (int k = 0; k < mk.n_ev; ++k) SKR_HIP(hipEventDestroy(mk.ev[k]));
-    }
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 

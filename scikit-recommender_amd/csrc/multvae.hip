@@ -30,10 +30,14 @@
 // dWp / dbp to the gradient in chunk order; dz, the softmax partials, neg_ll and kl are summed in fixed orders.
 #include "skr_common.h"
 #include "fast_rng.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <cmath>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;          // latent columns (narrower models zero-padded)
 constexpr int E2 = 2 * D;      // an encoder row: mu | logvar
@@ -43,10 +47,6 @@ constexpr int HW = 4;          // wavefronts per workgroup
 constexpr int LDP = 68;        // LDS row stride: 16-byte rows, and row r, k-group g of an operand read fall on bank 4 r + g
 constexpr int R_WAVES = 16;
 constexpr int MAX_WG = SKR_MULTVAE_MAX_WG;
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
 
 struct Layout {                // float offsets into the workspace
     int64_t e, eps, z, de, scale, klu, possum, lse, part, dzpart, off, total;
@@ -76,13 +76,7 @@ inline Layout layout(int n, int n_wg) {
     return L;
 }
 
-// ---- device draws: keyed by (seed, step, user, item) and (seed, step, user, column) -----------------------------
-__device__ __forceinline__ bool keep_draw(uint64_t seed, uint64_t step, int user, int item, float keep_prob) {
-    Xoshiro128pp g;
-    g.seed(seed, step, (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(item));
-    return static_cast<float>(g.next() >> 8) * 0x1p-24f < keep_prob;
-}
-
+// ---- device draws: fast_rng.h's keep_draw, keyed by (seed, step, user, item), and the one keyed by (seed, step, user, column)
 __device__ __forceinline__ float normal_draw(uint64_t seed, uint64_t step, int user, int col) {
     Xoshiro128pp g;
     g.seed(seed, step, (1ull << 63) | (static_cast<uint64_t>(static_cast<uint32_t>(user)) << 32) | static_cast<uint32_t>(col));
@@ -221,57 +215,6 @@ __global__ __launch_bounds__(HW * 64) void mv_queries_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // decoder tiles
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tile_range(int tiles, int& t0, int& t1) {
-    t0 = static_cast<int>(static_cast<int64_t>(blockIdx.x) * tiles / gridDim.x);
-    t1 = static_cast<int>(static_cast<int64_t>(blockIdx.x + 1) * tiles / gridDim.x);
-}
-
-// Wp[item0 .. item0 + 64) into LDS, rows beyond the catalogue as zeros
-__device__ __forceinline__ void load_tile(float* __restrict__ sW, const float* __restrict__ Wp, int item0, int n_items) {
-    const float4* W4 = reinterpret_cast<const float4*>(Wp);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
-        const int item = item0 + row;
-        v[i] = item < n_items ? W4[static_cast<int64_t>(item) * 16 + c4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = threadIdx.x + i * HW * 64, row = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<float4*>(sW + row * LDP + c4 * 4) = v[i];
-    }
-}
-
-// the wavefront's z rows as the A operand of 16 k-steps: lane (r, g) holds z[user r][4 kk + g]
-__device__ __forceinline__ void load_a(float a[16], const float* __restrict__ z, int ub, int n, int r, int g) {
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) a[kk] = ub + r < n ? z[static_cast<int64_t>(ub + r) * D + 4 * kk + g] : 0.0f;
-}
-
-// acc[nb][rr] = <z[user 4 g + rr], Wp[item 16 nb + r]>
-__device__ __forceinline__ void logits_tile(f32x4 acc[4], const float a[16], const float* __restrict__ sW, int r, int g) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], sW[(nb * 16 + r) * LDP + 4 * kk + g], acc[nb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ float max16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // pass 1: part[wg][user] = (max, sum exp(logit - max)) over the workgroup's tiles
 __global__ __launch_bounds__(HW * 64) void mv_pass1_kernel(const float* __restrict__ Wp, const float* __restrict__ bp,
                                                            const float* __restrict__ z, int n, int n4, int n_items,
@@ -289,7 +232,7 @@ __global__ __launch_bounds__(HW * 64) void mv_pass1_kernel(const float* __restri
         for (int rr = 0; rr < 4; ++rr) { m[rr] = -INFINITY; s[rr] = 0.0f; }
         for (int t = t0; t < t1; ++t) {
             __syncthreads();
-            load_tile(sW, Wp, t * TI, n_items);
+            load_tile<LDP, HW>(sW, Wp, t * TI, n_items);
             __syncthreads();
             float bpv[4];
 #pragma unroll
@@ -298,7 +241,7 @@ __global__ __launch_bounds__(HW * 64) void mv_pass1_kernel(const float* __restri
                 bpv[nb] = item < n_items ? bp[item] : -INFINITY;      // items beyond the catalogue: exp(-inf) = 0
             }
             f32x4 acc[4];
-            logits_tile(acc, a, sW, r, g);
+            logits_tile<LDP>(acc, a, sW, r, g);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 float v[4];
@@ -425,7 +368,7 @@ __global__ __launch_bounds__(HW * 64) void mv_pass2_kernel(
         for (int t = t0; t < t1; ++t) {
             const int item0 = t * TI;
             __syncthreads();                               // the previous tile's products still read sW and sG
-            load_tile(sW, Wp, item0, n_items);
+            load_tile<LDP, HW>(sW, Wp, item0, n_items);
             // this tile's entries of the 16 rows: requested before the products, used after them
             int its[16];
 #pragma unroll
@@ -442,7 +385,7 @@ __global__ __launch_bounds__(HW * 64) void mv_pass2_kernel(
                 bpv[nb] = item < n_items ? bp[item] : 0.0f;
             }
             f32x4 acc[4];
-            logits_tile(acc, a, sW, r, g);
+            logits_tile<LDP>(acc, a, sW, r, g);
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
                 const bool in = item0 + nb * 16 + r < n_items;
@@ -626,7 +569,7 @@ static int run_step(const float* d_WqT, const float* d_bq, const float* d_Wp, co
     SKR_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "skr_multvae_step: keep_prob = %g is not in (0, 1]", keep_prob);
     SKR_REQUIRE((d_keep == nullptr) == (d_eps == nullptr), "skr_multvae_step: d_keep and d_eps come together or not at all");
     if (n == 0) return SKR_OK;
-    const int n_wg = n_workgroups(n_items), tiles = (n_items + TI - 1) / TI, n4 = round4(n);
+    const int n_wg = n_workgroups(n_items), tiles = (n_items + TI - 1) / TI, n4 = static_cast<int>(round4(n));
     const Layout L = layout(n, n_wg);
     SKR_REQUIRE(work_bytes >= static_cast<size_t>(L.total) * sizeof(float),
                 "skr_multvae_step: d_work holds %zu bytes, skr_multvae_workspace(%d, %d) asks for %zu", work_bytes, n, n_items,
@@ -639,44 +582,33 @@ static int run_step(const float* d_WqT, const float* d_bq, const float* d_Wp, co
     const float invB = 1.0f / static_cast<float>(n);
     const int ub = (n + HW - 1) / HW;
     // h_ms: an event after every launch (the profiling entry); otherwise nothing but the eight launches
-    hipEvent_t ev[SKR_MULTVAE_LAUNCHES + 1] = {};
-    int n_ev = 0;
-    auto mark = [&]() -> hipError_t {
-        if (h_ms == nullptr) return hipSuccess;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    };
-    SKR_HIP(mark());
+    StepTimer<SKR_MULTVAE_LAUNCHES + 1> mk(h_ms, st);
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_prep_kernel, dim3(1), dim3(1024), 0, st, d_rowptr, d_users, n, n_users, off);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_encode_kernel, dim3(ub), dim3(HW * 64), 0, st, d_WqT, d_bq, d_Wp, d_bp, d_rowptr, d_items, d_users, n,
                        n_users, n_items, dim, keep_prob, d_keep, d_eps, seed, step, off, w + L.e, w + L.eps, w + L.z,
                        w + L.scale, w + L.klu, w + L.possum);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_pass1_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_Wp, d_bp, w + L.z, n, n4, n_items, tiles,
                        w + L.part);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_merge_kernel, dim3(1), dim3(1024), 0, st, w + L.part, n_wg, n, n4, d_rowptr, d_users, n_users,
                        w + L.possum, w + L.klu, w + L.lse, d_loss);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_pass2_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_Wp, d_bp, w + L.z, w + L.lse, d_rowptr, d_items,
                        d_users, n, n4, n_users, n_items, tiles, d_gWp, d_gbp, w + L.dzpart);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_reduce_kernel, dim3(n), dim3(R_WAVES * 64), 0, st, w + L.dzpart, n_wg, n4, dim, anneal, invB, w + L.e,
                        w + L.eps, w + L.de);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_encbwd_kernel, dim3(ub), dim3(HW * 64), 0, st, w + L.de, w + L.scale, d_rowptr, d_items, d_users, n,
                        n_users, n_items, keep_prob, d_keep, seed, step, off, d_gWqT);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     hipLaunchKernelGGL(mv_dbq_kernel, dim3(1), dim3(1024), 0, st, w + L.de, n, d_gbq);
-    SKR_HIP(mark());
+    SKR_HIP(mk.mark());
     SKR_LAUNCH_CHECK();
-    if (h_ms != nullptr) {
-        SKR_HIP(hipEventSynchronize(ev[n_ev - 1]));
-        for (int k = 0; k + 1 < n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], ev[k], ev[k + 1]));
-        for (int k = 0; k < n_ev; ++k) SKR_HIP(hipEventDestroy(ev[k]));
-    }
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 

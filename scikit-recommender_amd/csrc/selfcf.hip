@@ -27,15 +27,19 @@
 //   2L dropped runs  acc = G; acc = (A-hat')^T acc + G (the addend epilogue) with the backward keeps; the last writes
 //                    acc / (L + 1) into the gradient
 //
-// The MFMA operand mapping is dens.hip's: step kk of lane (r, g) carries k = 16 g + kk.
+// The MFMA operand mapping is mfma_tile.h's k = 16 g + kk.
 //
 // Determinism: there is no floating-point atomic anywhere in the step.
 #include "skr_common.h"
 #include "fast_rng.h"
+#include "mfma_tile.h"
+#include "step_common.h"
 
 #include <algorithm>
 
 namespace {
+
+using namespace skr;
 
 constexpr int D = 64;          // columns of every table
 constexpr int LDP = 68;        // LDS row stride
@@ -46,83 +50,8 @@ constexpr int MAXL = SKR_SELFCF_MAX_LAYERS;
 constexpr int PRED = SKR_SELFCF_PRED_FLOATS;
 constexpr float COS_EPS = 1e-8f;   // F.cosine_similarity's default
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__host__ __device__ inline int64_t round4(int64_t x) { return (x + 3) & ~static_cast<int64_t>(3); }
-
 // streams of the device draws: the two halves of the edge mask, the two target masks (the user side first)
 enum { DRAW_K1 = 0, DRAW_K2 = 1, DRAW_KU = 2, DRAW_KI = 3 };
-
-// keep iff a 24-bit uniform keyed by (seed, step, stream, idx) is >= rate
-__device__ __forceinline__ bool draw_keep(uint64_t seed, uint64_t step, uint64_t stream, uint64_t idx, float rate) {
-    Xoshiro128pp g;
-    g.seed(seed, step, (stream << 60) | idx);
-    return static_cast<float>(g.next() >> 8) * (1.0f / 16777216.0f) >= rate;
-}
-
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// a[kk] = row[16 g + kk] of the table's row `node` (zeros for node < 0): the lane's share of an A operand
-__device__ __forceinline__ void load_row_a(float a[16], const float* __restrict__ X, int64_t node, int g) {
-    if (node < 0) {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) a[kk] = 0.0f;
-        return;
-    }
-    const float4* p = reinterpret_cast<const float4*>(X + node * D + 16 * g);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-// acc[nb][rr] += sum_k A[4 g + rr][k] * B[16 nb + r][k]: a[] the lane's share of A's row r, sB rows of stride LDP
-__device__ __forceinline__ void tile_product(f32x4 acc[4], const float a[16], const float* __restrict__ sB, int r, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float4 w[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) w[nb] = *reinterpret_cast<const float4*>(sB + (nb * 16 + r) * LDP + 16 * g + 4 * q);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 0], w[nb].x, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 1], w[nb].y, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 2], w[nb].z, acc[nb], 0, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * q + 3], w[nb].w, acc[nb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void zero_acc(f32x4 acc[4]) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-}
-
-__device__ __forceinline__ int64_t checked(int id, int limit) { return id >= 0 && id < limit ? id : -1; }
-
-__device__ __forceinline__ void load_slab(float a[16], const float* __restrict__ s, int row, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(s + row * LDP + 16 * g + 4 * q);
-        a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ float column_sum(const float* __restrict__ sXT, int col) {
-    float t = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(sXT + col * LDP + 4 * q);
-        t += (v.x + v.y) + (v.z + v.w);
-    }
-    return t;
-}
 
 // ------------------------------------------------------------------------------------------------
 // the keep flags of a step's plan runs
@@ -197,7 +126,7 @@ __global__ __launch_bounds__(HW * 64) void sc_batch_kernel(const float* __restri
         }
         f32x4 P[4];
         zero_acc(P);
-        tile_product(P, xa, sW, r, g);
+        tile_product<LDP>(P, xa, sW, r, g);
         // ---- D layout: lane (r, g) holds column 16 nb + r of the rows 4 g + rr
         const uint8_t* __restrict__ karr = side == 0 ? ki : ku;
         const uint64_t kstream = side == 0 ? DRAW_KI : DRAW_KU;
@@ -255,10 +184,10 @@ __global__ __launch_bounds__(HW * 64) void sc_batch_kernel(const float* __restri
         for (int kk = 0; kk < 16; ++kk) sXT[(16 * g + kk) * LDP + wv * 16 + r] = xa[kk];
         __syncthreads();
         float ga[16];
-        load_slab(ga, sG, wv * 16 + r, g);
+        load_slab<LDP>(ga, sG, wv * 16 + r, g);
         f32x4 gx[4];
         zero_acc(gx);
-        tile_product(gx, ga, sWT, r, g);
+        tile_product<LDP>(gx, ga, sWT, r, g);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int bD = b0 + 4 * g + rr;
@@ -272,9 +201,9 @@ __global__ __launch_bounds__(HW * 64) void sc_batch_kernel(const float* __restri
             }
         }
         float slab[16];
-        load_slab(slab, sGT, wv * 16 + r, g);
-        tile_product(dW, slab, sXT, r, g);
-        if (threadIdx.x < D) db += column_sum(sGT, threadIdx.x);
+        load_slab<LDP>(slab, sGT, wv * 16 + r, g);
+        tile_product<LDP>(dW, slab, sXT, r, g);
+        if (threadIdx.x < D) db += column_sum<LDP>(sGT, threadIdx.x);
     }
     float* out = part + static_cast<int64_t>(blockIdx.x) * PRED;
 #pragma unroll
@@ -283,27 +212,6 @@ __global__ __launch_bounds__(HW * 64) void sc_batch_kernel(const float* __restri
         for (int rr = 0; rr < 4; ++rr) out[(wv * 16 + 4 * g + rr) * D + nb * 16 + r] = dW[nb][rr];
     }
     if (threadIdx.x < D) out[D * D + threadIdx.x] = db;
-}
-
-// the predictor's gradient = the workgroups' partial sums in workgroup order
-__global__ __launch_bounds__(256) void sc_pred_reduce_kernel(const float* __restrict__ part, int n_wg, float* __restrict__ out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= PRED) return;
-    float t = 0.0f;
-    for (int w = 0; w < n_wg; ++w) t += part[static_cast<int64_t>(w) * PRED + e];
-    out[e] = t;
-}
-
-__device__ __forceinline__ float block_sum_1024(float v, float* s) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    s[t] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) s[t] += s[t + o];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 // loss[0] = the two cosine terms (SelfCF.py:230-231), loss[1] = reg * reg_loss (:226, :233), loss[2] = their sum
@@ -326,22 +234,6 @@ __global__ __launch_bounds__(1024) void sc_loss_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // the g_x rows into the table G
 // ------------------------------------------------------------------------------------------------
-// order_u [n] / order_i [n]: the positions of the user / item list sorted by (id, position) -- a rank by counting
-__global__ __launch_bounds__(256) void sc_rank_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ items, int n,
-                                                      int32_t* __restrict__ order_u, int32_t* __restrict__ order_i) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= 2 * n) return;
-    const int32_t* ids = k < n ? users : items;
-    const int kk = k < n ? k : k - n;
-    const int id = ids[kk];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-        const int o = ids[j];
-        rank += (o < id || (o == id && j < kk)) ? 1 : 0;
-    }
-    (k < n ? order_u : order_i)[rank] = kk;
-}
-
 // G[id] = the sum of the g_x rows whose list entry is id, in rank order, by the wavefront of the id's first rank: one writer
 // per distinct id (the table was cleared).  Blocks [0, blocks_u) walk the user list, the others the item list.
 __global__ __launch_bounds__(HW * 64) void sc_seg_add_kernel(float* __restrict__ G, const int32_t* __restrict__ users,
@@ -402,20 +294,6 @@ __global__ __launch_bounds__(HW * 64) void sc_queries_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct Marker {                // h_ms: an event after every launch group (the profiling entry); otherwise nothing
-    float* h_ms;
-    hipStream_t st;
-    hipEvent_t ev[SKR_SELFCF_GROUPS + 1];
-    int n_ev;
-    hipError_t mark() {
-        if (h_ms == nullptr) return hipSuccess;
-        if (n_ev > SKR_SELFCF_GROUPS) return hipErrorInvalidValue;
-        hipError_t e = hipEventCreate(&ev[n_ev]);
-        if (e == hipSuccess) e = hipEventRecord(ev[n_ev++], st);
-        return e;
-    }
-};
-
 struct StepLayout {            // float offsets into the step's workspace
     int64_t Gx, lossb, part, ordu, ordi, total;
 };
@@ -464,7 +342,7 @@ int run_step(const skr_selfcf_step_args* a, void* stream, float* h_ms) {
     const int64_t UO = static_cast<int64_t>(U) * D, N = static_cast<int64_t>(U) + I;
     const float* pred = a->params + N * D;
     const float s = 1.0f / static_cast<float>(L + 1);
-    Marker mk = {h_ms, st, {}, 0};
+    StepTimer<SKR_SELFCF_GROUPS + 1> mk(h_ms, st);     // h_ms: an event after every launch group; otherwise nothing
     SKR_HIP(mk.mark());
     // ---- forward (SelfCF.py:151-159): X_k = A-hat' X_(k-1); M = s X_0 + s X_1, then M += s X_k
     if (L == 0) {
@@ -494,14 +372,14 @@ int run_step(const skr_selfcf_step_args* a, void* stream, float* h_ms) {
     hipLaunchKernelGGL(sc_batch_kernel, dim3(n_wg), dim3(HW * 64), 0, st, a->M, pred, a->users, a->items, a->ku, a->ki, n, U, I,
                        1.0f / (1.0f - a->dropout), a->dropout, a->seed, a->step, a->reg, 0.5f / static_cast<float>(n), w + W.Gx, w + W.lossb,
                        w + W.part);
-    hipLaunchKernelGGL(sc_pred_reduce_kernel, dim3((PRED + 255) / 256), dim3(256), 0, st, w + W.part, n_wg, a->grad + N * D);
+    hipLaunchKernelGGL(part_reduce_kernel<PRED>, dim3((PRED + 255) / 256), dim3(256), 0, st, w + W.part, n_wg, a->grad + N * D);
     hipLaunchKernelGGL(sc_loss_kernel, dim3(1), dim3(1024), 0, st, w + W.lossb, n, a->reg, a->loss);
     SKR_LAUNCH_CHECK();
     SKR_HIP(mk.mark());
     // ---- the g_x rows into the cleared table (the gradient itself when there is no propagation)
     float* G = L == 0 ? a->grad : a->G;
     SKR_HIP(hipMemsetAsync(G, 0, static_cast<size_t>(N) * D * sizeof(float), st));
-    hipLaunchKernelGGL(sc_rank_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, st, a->users, a->items, n, ordu, ordi);
+    hipLaunchKernelGGL(rank_lists_kernel<256>, dim3((2 * n + 255) / 256), dim3(256), 0, st, a->users, a->items, n, ordu, ordi);
     const int blocks = (n + HW - 1) / HW;
     hipLaunchKernelGGL(sc_seg_add_kernel, dim3(2 * blocks), dim3(HW * 64), 0, st, G, a->users, a->items, ordu, ordi, n, U, I, blocks, w + W.Gx);
     SKR_LAUNCH_CHECK();
@@ -529,11 +407,7 @@ int run_step(const skr_selfcf_step_args* a, void* stream, float* h_ms) {
         }
     }
     SKR_HIP(mk.mark());
-    if (h_ms != nullptr) {
-        SKR_HIP(hipEventSynchronize(mk.ev[mk.n_ev - 1]));
-        for (int k = 0; k + 1 < mk.n_ev; ++k) SKR_HIP(hipEventElapsedTime(&h_ms[k], mk.ev[k], mk.ev[k + 1]));
-        for (int k = 0; k < mk.n_ev; ++k) SKR_HIP(hipEventDestroy(mk.ev[k]));
-    }
+    SKR_HIP(mk.finish());
     return SKR_OK;
 }
 
