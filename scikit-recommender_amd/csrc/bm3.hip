@@ -612,7 +612,6 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
     const int64_t n4 = round4(n);
     const int64_t UO = static_cast<int64_t>(U) * D, N = static_cast<int64_t>(U) + I;
     const float* pred = a->params + N * D;
-    const float s = 1.0f / static_cast<float>(L + 1);
     float* Y[2] = {a->feat_dim[0] ? w + W.Y : nullptr, a->feat_dim[1] ? w + W.Y + n4 * D : nullptr};
     StepTimer<SKR_BM3_GROUPS + 1> mk(h_ms, st);        // h_ms: an event after every launch group; otherwise nothing
     SKR_HIP(mk.mark());
@@ -621,29 +620,12 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
         hipLaunchKernelGGL(bm_clear_rows_kernel, dim3(a->n_clear, 2), dim3(256), 0, st, cp, a->clear_items, I);
         SKR_LAUNCH_CHECK();
     }
-    // ---- forward (BM3.py:145-151): X_k = A-hat X_(k-1); M = s X_0 + s X_1, then M += s X_k
-    if (L == 0) {
-        SKR_HIP(hipMemcpyAsync(a->M, a->params, static_cast<size_t>(N) * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else {
-        const float* X = a->params;
-        for (int k = 1; k <= L; ++k) {
-            float* Yk = k == L ? nullptr : a->ping[(k - 1) & 1];
-            skr_spmm_epilogue ep = {};
-            ep.mode = SKR_EPI_PLAIN;
-            ep.accum_scale = s;
-            ep.Y = Yk;
-            ep.accum = a->M;
-            ep.accum_base = k == 1 ? a->params : nullptr;
-            int rc = skr_spmm_plan_run_ex(a->plan_a, X + UO, D, &ep, nullptr, nullptr, stream);
-            if (rc != SKR_OK) return rc;
-            ep.Y = Yk ? Yk + UO : nullptr;
-            ep.accum = a->M + UO;
-            ep.accum_base = k == 1 ? a->params + UO : nullptr;
-            rc = skr_spmm_plan_run_ex(a->plan_at, X, D, &ep, nullptr, nullptr, stream);
-            if (rc != SKR_OK) return rc;
-            X = Yk;
-        }
-    }
+    // ---- forward (BM3.py:145-151): the layer means of X_k = A-hat X_(k-1)
+    const auto product = [&](const skr_spmm_plan* plan, const float* X, const skr_spmm_epilogue& ep, bool) {
+        return skr_spmm_plan_run_ex(plan, X, D, &ep, nullptr, nullptr, stream);
+    };
+    int rc = mean_forward(a->plan_a, a->plan_at, a->params, UO, N, L, a->ping, a->M, st, product);
+    if (rc != SKR_OK) return rc;
     SKR_HIP(mk.mark());
     // ---- + h (BM3.py:153) and the Frobenius norms of the whole tables (BM3.py:66-71)
     hipLaunchKernelGGL(bm_addh_sumsq_kernel, dim3(2 * NB), dim3(HW * 64), 0, st, a->M, a->params, U, I, w + W.npart);
@@ -699,25 +681,8 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
     // ---- backward: acc = G; L times acc = A-hat acc + G (A-hat is symmetric); the last product writes acc / (L + 1) into
     // the gradient; then the item rows' + h path
     {
-        const float* X = G;
-        for (int k = 1; k <= L; ++k) {
-            const bool last = k == L;
-            float* Yk = last ? nullptr : a->ping[(k - 1) & 1];
-            skr_spmm_epilogue ep = {};
-            ep.mode = SKR_EPI_PLAIN;
-            ep.accum_scale = s;
-            ep.addend = G;
-            ep.Y = Yk;
-            if (last) { ep.accum = a->grad; ep.accum_init = 1; }
-            int rc = skr_spmm_plan_run_ex(a->plan_a, X + UO, D, &ep, nullptr, nullptr, stream);
-            if (rc != SKR_OK) return rc;
-            ep.addend = G + UO;
-            ep.Y = Yk ? Yk + UO : nullptr;
-            if (last) ep.accum = a->grad + UO;
-            rc = skr_spmm_plan_run_ex(a->plan_at, X, D, &ep, nullptr, nullptr, stream);
-            if (rc != SKR_OK) return rc;
-            X = Yk;
-        }
+        rc = chain_backward(a->plan_a, a->plan_at, G, UO, L, a->ping, a->grad, product);
+        if (rc != SKR_OK) return rc;
         const int64_t ni = static_cast<int64_t>(I) * D;
         const unsigned wgs = static_cast<unsigned>(std::min<int64_t>((ni + 255) / 256, 8192));
         hipLaunchKernelGGL(bm_addh_grad_kernel, dim3(wgs), dim3(256), 0, st, a->grad + UO, G + UO, ni);

@@ -543,15 +543,6 @@ inline StepLayout step_layout(int n, int H) {
     return L;
 }
 
-int run_plan(const skr_spmm_plan* plan, const float* X, const float* addend, float* Y, void* stream) {
-    skr_spmm_epilogue ep = {};
-    ep.mode = SKR_EPI_PLAIN;
-    ep.addend = addend;
-    ep.Y = Y;
-    ep.accum_scale = 1.0f;
-    return skr_spmm_plan_run_ex(plan, X, D, &ep, nullptr, nullptr, stream);
-}
-
 int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
     SKR_REQUIRE(a, "skr_dens_step: NULL argument");
     const int U = a->n_users, I = a->n_items, n = a->n, H = a->n_hops, K = a->n_negs;
@@ -588,9 +579,9 @@ int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
     SKR_HIP(mk.mark());
     // ---- forward (DENS.py:125-134): X_h = A-hat X_(h-1)
     for (int h = 1; h <= H; ++h) {
-        int rc = run_plan(a->plan_a, T.x[h - 1] + UO, nullptr, a->hop[h - 1], stream);
+        int rc = plain_run(a->plan_a, T.x[h - 1] + UO, nullptr, a->hop[h - 1], nullptr, nullptr, stream);
         if (rc != SKR_OK) return rc;
-        rc = run_plan(a->plan_at, T.x[h - 1], nullptr, a->hop[h - 1] + UO, stream);
+        rc = plain_run(a->plan_at, T.x[h - 1], nullptr, a->hop[h - 1] + UO, nullptr, nullptr, stream);
         if (rc != SKR_OK) return rc;
     }
     SKR_HIP(mk.mark());
@@ -626,9 +617,9 @@ int run_step(const skr_dens_step_args* a, void* stream, float* h_ms) {
         const float* X = H > 0 ? a->G[H] : nullptr;
         for (int h = H - 1; h >= 0; --h) {
             float* Y = h == 0 ? a->grad : (X == a->G[H] ? a->ping : a->G[H]);
-            int rc = run_plan(a->plan_a, X + UO, a->G[h], Y, stream);
+            int rc = plain_run(a->plan_a, X + UO, a->G[h], Y, nullptr, nullptr, stream);
             if (rc != SKR_OK) return rc;
-            rc = run_plan(a->plan_at, X, a->G[h] + UO, Y + UO, stream);
+            rc = plain_run(a->plan_at, X, a->G[h] + UO, Y + UO, nullptr, nullptr, stream);
             if (rc != SKR_OK) return rc;
             X = Y;
         }

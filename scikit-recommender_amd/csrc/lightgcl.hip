@@ -622,18 +622,6 @@ inline StepLayout step_layout(int n, int n_users, int n_items) {
     return L;
 }
 
-int run_plan(const skr_spmm_plan* plan, const float* X, const float* addend, float* Y, float* accum, const float* accum_base,
-             void* stream) {
-    skr_spmm_epilogue ep = {};
-    ep.mode = SKR_EPI_PLAIN;
-    ep.addend = addend;
-    ep.Y = Y;
-    ep.accum = accum;
-    ep.accum_base = accum_base;
-    ep.accum_scale = 1.0f;
-    return skr_spmm_plan_run_ex(plan, X, D, &ep, nullptr, nullptr, stream);
-}
-
 int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
     SKR_REQUIRE(a, "skr_lightgcl_step: NULL argument");
     const int U = a->n_users, I = a->n_items, n = a->n, Ly = a->n_layers;
@@ -676,9 +664,9 @@ int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
             float* Y = last ? nullptr : a->ping[(l - 1) & 1];
             float* acc = last ? a->sum : a->below;
             const float* base = last ? below : (l == 1 ? a->E0 : nullptr);
-            int rc = run_plan(a->plan_a, X + UO, nullptr, Y, acc, base, stream);
+            int rc = plain_run(a->plan_a, X + UO, nullptr, Y, acc, base, stream);
             if (rc != SKR_OK) return rc;
-            rc = run_plan(a->plan_at, X, nullptr, Y ? Y + UO : nullptr, acc + UO, base ? base + UO : nullptr, stream);
+            rc = plain_run(a->plan_at, X, nullptr, Y ? Y + UO : nullptr, acc + UO, base ? base + UO : nullptr, stream);
             if (rc != SKR_OK) return rc;
             X = Y;
         }
@@ -737,9 +725,9 @@ int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
         const float* H = a->gsum;
         for (int k = 1; k <= Ly; ++k) {
             float* Y = k == Ly ? a->grad : a->ping[(k - 1) & 1];
-            int rc = run_plan(a->plan_a, H + UO, addend, Y, nullptr, nullptr, stream);
+            int rc = plain_run(a->plan_a, H + UO, addend, Y, nullptr, nullptr, stream);
             if (rc != SKR_OK) return rc;
-            rc = run_plan(a->plan_at, H, addend + UO, Y + UO, nullptr, nullptr, stream);
+            rc = plain_run(a->plan_at, H, addend + UO, Y + UO, nullptr, nullptr, stream);
             if (rc != SKR_OK) return rc;
             H = Y;
         }

@@ -341,32 +341,14 @@ int run_step(const skr_selfcf_step_args* a, void* stream, float* h_ms) {
     int32_t* ordi = reinterpret_cast<int32_t*>(w + W.ordi);
     const int64_t UO = static_cast<int64_t>(U) * D, N = static_cast<int64_t>(U) + I;
     const float* pred = a->params + N * D;
-    const float s = 1.0f / static_cast<float>(L + 1);
     StepTimer<SKR_SELFCF_GROUPS + 1> mk(h_ms, st);     // h_ms: an event after every launch group; otherwise nothing
     SKR_HIP(mk.mark());
-    // ---- forward (SelfCF.py:151-159): X_k = A-hat' X_(k-1); M = s X_0 + s X_1, then M += s X_k
-    if (L == 0) {
-        SKR_HIP(hipMemcpyAsync(a->M, a->params, static_cast<size_t>(N) * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else {
-        const float* X = a->params;
-        for (int k = 1; k <= L; ++k) {
-            float* Y = k == L ? nullptr : a->ping[(k - 1) & 1];
-            skr_spmm_epilogue ep = {};
-            ep.mode = SKR_EPI_PLAIN;
-            ep.accum_scale = s;
-            ep.Y = Y;
-            ep.accum = a->M;
-            ep.accum_base = k == 1 ? a->params : nullptr;
-            int rc = skr_spmm_plan_run_dropped(a->plan_a, X + UO, D, &ep, a->keep_fu, a->edge_scale, stream);
-            if (rc != SKR_OK) return rc;
-            ep.Y = Y ? Y + UO : nullptr;
-            ep.accum = a->M + UO;
-            ep.accum_base = k == 1 ? a->params + UO : nullptr;
-            rc = skr_spmm_plan_run_dropped(a->plan_at, X, D, &ep, a->keep_fi, a->edge_scale, stream);
-            if (rc != SKR_OK) return rc;
-            X = Y;
-        }
-    }
+    // ---- forward (SelfCF.py:151-159): the layer means of X_k = A-hat' X_(k-1), A-hat' the dropped, rescaled matrix
+    int rc = mean_forward(a->plan_a, a->plan_at, a->params, UO, N, L, a->ping, a->M, st,
+                          [&](const skr_spmm_plan* plan, const float* X, const skr_spmm_epilogue& ep, bool item_half) {
+                              return skr_spmm_plan_run_dropped(plan, X, D, &ep, item_half ? a->keep_fi : a->keep_fu, a->edge_scale, stream);
+                          });
+    if (rc != SKR_OK) return rc;
     SKR_HIP(mk.mark());
     const int n_wg = batch_workgroups(n);
     hipLaunchKernelGGL(sc_batch_kernel, dim3(n_wg), dim3(HW * 64), 0, st, a->M, pred, a->users, a->items, a->ku, a->ki, n, U, I,
@@ -385,27 +367,11 @@ int run_step(const skr_selfcf_step_args* a, void* stream, float* h_ms) {
     SKR_LAUNCH_CHECK();
     SKR_HIP(mk.mark());
     // ---- backward: acc = G; L times acc = (A-hat')^T acc + G; the last product writes acc / (L + 1) into the gradient
-    {
-        const float* X = G;
-        for (int k = 1; k <= L; ++k) {
-            const bool last = k == L;
-            float* Y = last ? nullptr : a->ping[(k - 1) & 1];
-            skr_spmm_epilogue ep = {};
-            ep.mode = SKR_EPI_PLAIN;
-            ep.accum_scale = s;
-            ep.addend = G;
-            ep.Y = Y;
-            if (last) { ep.accum = a->grad; ep.accum_init = 1; }
-            int rc = skr_spmm_plan_run_dropped(a->plan_a, X + UO, D, &ep, a->keep_bu, a->edge_scale, stream);
-            if (rc != SKR_OK) return rc;
-            ep.addend = G + UO;
-            ep.Y = Y ? Y + UO : nullptr;
-            if (last) ep.accum = a->grad + UO;
-            rc = skr_spmm_plan_run_dropped(a->plan_at, X, D, &ep, a->keep_bi, a->edge_scale, stream);
-            if (rc != SKR_OK) return rc;
-            X = Y;
-        }
-    }
+    rc = chain_backward(a->plan_a, a->plan_at, G, UO, L, a->ping, a->grad,
+                        [&](const skr_spmm_plan* plan, const float* X, const skr_spmm_epilogue& ep, bool item_half) {
+                            return skr_spmm_plan_run_dropped(plan, X, D, &ep, item_half ? a->keep_bi : a->keep_bu, a->edge_scale, stream);
+                        });
+    if (rc != SKR_OK) return rc;
     SKR_HIP(mk.mark());
     SKR_HIP(mk.finish());
     return SKR_OK;

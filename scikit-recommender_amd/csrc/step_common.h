@@ -1,5 +1,5 @@
 // step_common.h -- what the models' step drivers share: the two small kernels that bm3.hip and selfcf.hip (and, for the
-// reduction, dens.hip) launch alike, and the host-side timer of the profiling entries.
+// reduction, dens.hip) launch alike, the host-side plan runs of the four graph models, and the timer of the profiling entries.
 #pragma once
 #include "skr_common.h"
 
@@ -38,6 +38,80 @@ __global__ __launch_bounds__(256) void part_reduce_kernel(const float* __restric
 }
 
 }  // namespace
+
+// ---- host side: the plan runs of the graph models' steps.  Every table is [n_users + n_items, 64]: the user rows, then the
+// item rows, which start UO = 64 n_users floats in; A-hat maps the item rows to the user rows through plan_a and back through
+// plan_at.
+
+// one product with the plain epilogue: Y = plan X (+ addend); with accum, accum = accum_base + Y or accum += Y
+inline int plain_run(const skr_spmm_plan* plan, const float* X, const float* addend, float* Y, float* accum, const float* accum_base,
+                     void* stream) {
+    skr_spmm_epilogue ep = {};
+    ep.mode = SKR_EPI_PLAIN;
+    ep.addend = addend;
+    ep.Y = Y;
+    ep.accum = accum;
+    ep.accum_base = accum_base;
+    ep.accum_scale = 1.0f;
+    return skr_spmm_plan_run_ex(plan, X, 64, &ep, nullptr, nullptr, stream);
+}
+
+// M = the mean of X_0 .. X_L, X_k = A-hat X_(k-1): M = s X_0 + s X_1, then M += s X_k, s = 1 / (L + 1); X_k for k < L goes
+// to ping[(k - 1) & 1].  run(plan, X, epilogue, item_half) -> int runs one product: the model's A-hat, plain or edge-dropped.
+template <class Run>
+int mean_forward(const skr_spmm_plan* plan_a, const skr_spmm_plan* plan_at, const float* X0, int64_t UO, int64_t N, int L,
+                 float* const* ping, float* M, hipStream_t st, Run run) {
+    if (L == 0) {
+        SKR_HIP(hipMemcpyAsync(M, X0, static_cast<size_t>(N) * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return SKR_OK;
+    }
+    const float* X = X0;
+    for (int k = 1; k <= L; ++k) {
+        float* Y = k == L ? nullptr : ping[(k - 1) & 1];
+        skr_spmm_epilogue ep = {};
+        ep.mode = SKR_EPI_PLAIN;
+        ep.accum_scale = 1.0f / static_cast<float>(L + 1);
+        ep.Y = Y;
+        ep.accum = M;
+        ep.accum_base = k == 1 ? X0 : nullptr;
+        int rc = run(plan_a, X + UO, ep, false);
+        if (rc != SKR_OK) return rc;
+        ep.Y = Y ? Y + UO : nullptr;
+        ep.accum = M + UO;
+        ep.accum_base = k == 1 ? X0 + UO : nullptr;
+        rc = run(plan_at, X, ep, true);
+        if (rc != SKR_OK) return rc;
+        X = Y;
+    }
+    return SKR_OK;
+}
+
+// the backward of mean_forward: acc = G; L times acc = A-hat^T acc + G; the last product writes acc / (L + 1) into grad.
+// ``run`` as above, on the transposed matrix' entries (SelfCF's dropped one is not symmetric).
+template <class Run>
+int chain_backward(const skr_spmm_plan* plan_a, const skr_spmm_plan* plan_at, const float* G, int64_t UO, int L, float* const* ping,
+                   float* grad, Run run) {
+    const float* X = G;
+    for (int k = 1; k <= L; ++k) {
+        const bool last = k == L;
+        float* Y = last ? nullptr : ping[(k - 1) & 1];
+        skr_spmm_epilogue ep = {};
+        ep.mode = SKR_EPI_PLAIN;
+        ep.accum_scale = 1.0f / static_cast<float>(L + 1);
+        ep.addend = G;
+        ep.Y = Y;
+        if (last) { ep.accum = grad; ep.accum_init = 1; }
+        int rc = run(plan_a, X + UO, ep, false);
+        if (rc != SKR_OK) return rc;
+        ep.addend = G + UO;
+        ep.Y = Y ? Y + UO : nullptr;
+        if (last) ep.accum = grad + UO;
+        rc = run(plan_at, X, ep, true);
+        if (rc != SKR_OK) return rc;
+        X = Y;
+    }
+    return SKR_OK;
+}
 
 // The events of a step's profiling entry: one after every launch group, at most MARKS of them.  With h_ms == NULL (the
 // plain entry) nothing here calls the runtime.  The destructor releases the events on every way out of the step.

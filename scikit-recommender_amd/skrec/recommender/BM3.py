@@ -30,18 +30,15 @@ top-K path: the two factor tables come from ``skr_bm3_queries``.
 Limits (NotImplementedError): embed_dim <= 64, n_layers <= 4, batch_size <= 2048, 1 <= F <= 4096 per modality, one GPU.
 """
 import ctypes
-from typing import Dict
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import InteractionIterator
-from ..run_config import RunConfig
-from ..utils.py import EarlyStopping, ModelConfig
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
-from .LightGCL import selfcf_adjacency
+from ..utils.py import ModelConfig
+from ._graph import GraphRecommender, linear_block, propagate_mean, selfcf_adjacency, upload_csr
+from .base import DenseAdam, on_compute_stream
 
 __all__ = ["BM3", "BM3Config"]
 
@@ -133,47 +130,25 @@ def _features(a, num_items, name):
     return a.to(torch.float32)
 
 
-class BM3(AbstractRecommender):
+class BM3(GraphRecommender):
+    """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables
+    or None; ``seed`` (the run's): the key of the device draws"""
     config_class = BM3Config
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: see ``check_limits``"""
-        self.config = BM3Config(**model_config)
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        check_limits(self.config, self.dist.world)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        img, txt = self.dataset.img_features, self.dataset.txt_features
-        check_limits(self.config, self.dist.world, None if img is None else img.shape[1], None if txt is None else txt.shape[1])
-        self.device = _hip.require_gpu()
-        csr = self.dataset.train_data.to_csr_matrix().tocsr()
-        csr.sum_duplicates()
-        csr.sort_indices()
-        self._build(csr.indptr, csr.indices, img, txt, int(getattr(run_config, "seed", 0) or 0))
+    def _check_limits(self, world):
+        check_limits(self.config, world)
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, img=None, txt=None, seed=0):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors); ``img`` / ``txt``: [num_items, F] feature tables or None; ``seed``: the key of the device draws"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
+    def _build_args(self, run_config):
+        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features, "seed": getattr(run_config, "seed", 0) or 0}
+
+    def _check_data(self, img=None, txt=None, seed=0):
         check_limits(self.config, 1, None if img is None else int(img.shape[1]), None if txt is None else int(txt.shape[1]))
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._build(csr[0], csr[1], img, txt, int(seed))
-        return self
 
-    def _build(self, rowptr, items, img, txt, seed):
+    def _build(self, rowptr, items, img=None, txt=None, seed=0):
         cfg, dev = self.config, self.device
         nu, ni, d, L = self.num_users, self.num_items, cfg.embed_dim, cfg.n_layers
         N = nu + ni
-        if torch.is_tensor(rowptr):
-            rp, col = rowptr.to(dev, torch.int64).contiguous(), items.to(dev, torch.int32).contiguous()
-        else:
-            rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-            col = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(dev)
+        rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t, _ = selfcf_adjacency(rp, col, nu, ni)      # BM3.py:116-140 normalises as SelfCF does
         feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
@@ -206,7 +181,7 @@ class BM3(AbstractRecommender):
         self._Qu = torch.zeros((nu, 64), dtype=torch.float32, device=dev)
         self._Qi = torch.zeros((ni, 64), dtype=torch.float32, device=dev)
         self._work = torch.empty(int(_hip.lib().skr_bm3_workspace(min(cfg.batch_size, MAX_BATCH))), dtype=torch.uint8, device=dev)
-        self._seed, self._step = seed, 0
+        self._seed, self._step = int(seed), 0
         self._prev_items = None        # the item ids whose feature-gradient rows the previous step wrote
         self.step_losses = []          # (graph cosines, modal cosines, reg, total) per training step, device tensors [4]
 
@@ -216,9 +191,8 @@ class BM3(AbstractRecommender):
         d, nu, ni = self.config.embed_dim, self.num_users, self.num_items
         N = nu + ni
         rows = flat[:N * 64].view(N, 64)
-        blk = flat[N * 64:N * 64 + PRED_FLOATS]
-        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d],
-               "predictor.weight": blk[:4096].view(64, 64)[:d, :d], "predictor.bias": blk[4096:4096 + d]}
+        W, b = linear_block(flat[N * 64:N * 64 + PRED_FLOATS], d)
+        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d], "predictor.weight": W, "predictor.bias": b}
         for key, prefix, _ in MODALITIES:
             F, ld = self.feat_dim[key], self.feat_ld[key]
             if F:
@@ -246,18 +220,6 @@ class BM3(AbstractRecommender):
             views[k].copy_(t.detach().to(self.device, torch.float32))
 
     # ---- training --------------------------------------------------------------------------------
-    def _ids(self, t):
-        if torch.is_tensor(t):
-            return t.to(self.device, torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
-
-    def _flags(self, t, shape):
-        if not torch.is_tensor(t):
-            t = torch.from_numpy(np.ascontiguousarray(t).astype(np.uint8))
-        t = t.to(self.device, torch.uint8).contiguous()
-        assert tuple(t.shape) == tuple(shape), f"keep flags of shape {tuple(t.shape)}, expected {tuple(shape)}"
-        return t
-
     def target_draws(self, ids, table, step=None):
         """the device draws of one target table at the nodes ``ids`` (``skr_bm3_draws``) -> uint8 [n, 64]; ``table``: one of
         _hip.SKR_BM3_DRAW_*; keyed by (seed, step, table, node id), ``step`` None: the coming step"""
@@ -279,9 +241,7 @@ class BM3(AbstractRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"BM3: a batch holds at most {MAX_BATCH} rows (got {n})")
         assert di.numel() == n
-        need = int(_hip.lib().skr_bm3_workspace(n))
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow_work(int(_hip.lib().skr_bm3_workspace(n)))
         loss = torch.empty(4, dtype=torch.float32, device=self.device)
         a = _hip.BM3StepArgs()
         keeps = None
@@ -333,67 +293,18 @@ class BM3(AbstractRecommender):
         self.step_losses.append(loss)
         return loss
 
-    @on_compute_stream
-    def fit(self):
-        cfg = self.config
-        data_iter = InteractionIterator(self.dataset.train_data, batch_size=cfg.batch_size, shuffle=True, drop_last=False)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=cfg.early_stop)
-        for epoch in range(cfg.epochs):
-            self.step_losses = []
-            for users, items in data_iter:
-                self.train_step(users, items)
-            result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
-            if early_stopping(result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
-
-    # ---- ranking ---------------------------------------------------------------------------------
+    # ---- ranking: the base class's, on the two factor tables (BM3.py:206-210) -----------------------
     def propagate(self):
         """the propagation of the CURRENT parameters, the layer means and the item rows' + h (BM3.py:142-153), then the two
         factor tables W M + b (``skr_bm3_queries``) -> pooled"""
-        nu, ni, L = self.num_users, self.num_items, self.config.n_layers
+        nu, ni = self.num_users, self.num_items
         L_ = _hip.lib()
-        if L == 0:
-            self.pooled.copy_(self.X0)
-        else:
-            s = 1.0 / (L + 1)
-            X = self.X0
-            for k in range(1, L + 1):
-                Y = None if k == L else self._ping[(k - 1) & 1]
-                base = self.X0 if k == 1 else None          # pooled = s X_0 + s X_1, then pooled += s X_k
-                for mat, lo, hi, xs in ((self.adj, 0, nu, X[nu:]), (self.adj_t, nu, None, X[:nu])):
-                    ep = _hip.SpmmEpilogue()
-                    ep.mode = _hip.EPI_PLAIN
-                    ep.Y, ep.accum = _hip.ptr(None if Y is None else Y[lo:hi]), _hip.ptr(self.pooled[lo:hi])
-                    ep.accum_base = _hip.ptr(None if base is None else base[lo:hi])
-                    ep.accum_scale = s
-                    _hip.check(L_.skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(xs), 64, ctypes.byref(ep), None, None, _hip.stream()))
-                X = Y
+        propagate_mean(self.adj, self.adj_t, self.X0, nu, self.config.n_layers, self.pooled, ping=self._ping)
         _hip.check(L_.skr_axpy(1.0, _hip.ptr(self.X0[nu:]), _hip.ptr(self.pooled[nu:]), ni * 64, _hip.stream()))     # + h
         _hip.check(L_.skr_bm3_queries(_hip.ptr(self._pred), _hip.ptr(self.pooled), nu, ni, _hip.ptr(self._Qu), _hip.ptr(self._Qi),
                                       _hip.stream()))
         return self.pooled
 
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        self.propagate()
-        self._pooled_current = True
-        try:
-            return self.evaluator.evaluate(self, test_users)
-        finally:
-            self._pooled_current = False
-
-    def predict_factors(self):
+    def _factors(self):
         """(W M_u + b [U, 64], W M_i + b [I, 64], None) of the current parameters"""
-        if not getattr(self, "_pooled_current", False):
-            self.propagate()
         return self._Qu, self._Qi, None
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores (BM3.py:206-210)"""
-        uf, vf, _ = self.predict_factors()
-        return _hip.score_matrix(uf, list(users), vf, None).cpu().numpy()

@@ -40,6 +40,7 @@ from .. import _hip
 from ..run_config import RunConfig
 from ..utils.py import BatchIterator, EarlyStopping, ModelConfig
 from ..utils.torch import get_initializer
+from ._graph import train_csr
 from .base import AbstractRecommender, DenseAdam, on_compute_stream
 
 __all__ = ["CDAE", "CDAEConfig"]
@@ -161,11 +162,8 @@ class CDAE(AbstractRecommender):
         if self.dist.world > 1:
             raise NotImplementedError("CDAE runs on one GPU: there is no sharded engine for it")
         self.device = _hip.require_gpu()
-        csr = self.dataset.train_data.to_csr_matrix().tocsr()
-        csr.sum_duplicates()
-        csr.sort_indices()
         self.seed = int(getattr(run_config, "seed", 0) or 0)
-        self._build(csr.indptr, csr.indices)
+        self._build(*train_csr(self.dataset))
 
     @classmethod
     def detached(cls, num_users, num_items, model_config, csr, seed=0):

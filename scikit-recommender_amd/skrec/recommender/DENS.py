@@ -17,7 +17,6 @@ Limits (NotImplementedError): ns == "dens", pool == "mean", K == 1, no message o
 context_hops <= 3, n_negs <= 16, batch_size <= 2048, one GPU.  warmup == 0 is a ValueError (the reference divides by zero).
 """
 import ctypes
-from typing import Dict
 
 import numpy as np
 import torch
@@ -25,10 +24,9 @@ import torch.nn as nn
 
 from .. import _hip
 from ..io import PairwiseIterator
-from ..run_config import RunConfig
-from ..utils.py import EarlyStopping, ModelConfig
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
-from .LightGCL import DeviceCSR, normalized_adjacency  # noqa: F401
+from ..utils.py import ModelConfig
+from ._graph import GraphRecommender, linear_block, normalized_adjacency, propagate_mean, upload_csr
+from .base import DenseAdam, on_compute_stream
 
 __all__ = ["DENS", "DENSConfig"]
 
@@ -118,64 +116,27 @@ def init_parameters(num_users, num_items, d):
     return gates, eu, ei
 
 
-def _run_plan(mat, X, Y=None, accum=None, accum_base=None, accum_scale=1.0):
-    ep = _hip.SpmmEpilogue()
-    ep.mode = _hip.EPI_PLAIN
-    ep.Y, ep.accum, ep.accum_base = _hip.ptr(Y), _hip.ptr(accum), _hip.ptr(accum_base)
-    ep.accum_scale = accum_scale
-    _hip.check(_hip.lib().skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(X), 64, ctypes.byref(ep), None, None, _hip.stream()))
-
-
-class DENS(AbstractRecommender):
+class DENS(GraphRecommender):
+    """limits: see ``check_limits``"""
     config_class = DENSConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: see ``check_limits``"""
-        self.config = DENSConfig(**model_config)
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        check_limits(self.config, self.dist.world)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        self.device = _hip.require_gpu()
-        self.sampler_mode = getattr(run_config, "sampler_mode", None)
-        csr = self.dataset.train_data.to_csr_matrix().tocsr()
-        csr.sum_duplicates()
-        csr.sort_indices()
-        self._build(csr.indptr, csr.indices)
-
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        check_limits(self.config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._build(csr[0], csr[1])
-        return self
+    def _check_limits(self, world):
+        check_limits(self.config, world)
 
     def _build(self, rowptr, items):
         cfg, dev = self.config, self.device
         nu, ni, d, H = self.num_users, self.num_items, cfg.dim, cfg.context_hops
         N = nu + ni
-        if torch.is_tensor(rowptr):
-            rp, col = rowptr.to(dev, torch.int64).contiguous(), items.to(dev, torch.int32).contiguous()
-        else:
-            rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-            col = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(dev)
+        rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t = normalized_adjacency(rp, col, nu, ni)
         gates, eu, ei = init_parameters(nu, ni, d)
         flat = torch.zeros(N * 64 + 4 * GATE_FLOATS, dtype=torch.float32)
         rows = flat[:N * 64].view(N, 64)
         rows[:nu, :d], rows[nu:, :d] = eu, ei
-        for k, name in enumerate(GATES):
-            blk = flat[N * 64 + k * GATE_FLOATS:N * 64 + (k + 1) * GATE_FLOATS]
-            blk[:4096].view(64, 64)[:d, :d] = gates[name][0]
-            blk[4096:4096 + d] = gates[name][1]
+        for name in GATES:
+            W, b = self._gate_view(flat, name)
+            W[:], b[:] = gates[name]
         self._flat = flat.to(dev).contiguous()
         self.X0 = self._flat[:N * 64].view(N, 64)
         self.optimizer = DenseAdam(self._flat, lr=cfg.lr)         # Adam(weight_decay=0), DENS.py:432
@@ -190,8 +151,7 @@ class DENS(AbstractRecommender):
 
     def _gate_view(self, flat, name):
         k, N, d = GATES.index(name), self.num_users + self.num_items, self.config.dim
-        blk = flat[N * 64 + k * GATE_FLOATS:N * 64 + (k + 1) * GATE_FLOATS]
-        return blk[:4096].view(64, 64)[:d, :d], blk[4096:4096 + d]
+        return linear_block(flat[N * 64 + k * GATE_FLOATS:N * 64 + (k + 1) * GATE_FLOATS], d)
 
     def parameters(self):
         """{name: tensor} in the reference's shapes (copies): the four gates' weight and bias, user_embed, item_embed"""
@@ -227,11 +187,6 @@ class DENS(AbstractRecommender):
         """1 - min(1, epoch / warmup) (DENS.py:247)"""
         return 1.0 - min(1.0, epoch / self.config.warmup)
 
-    def _ids(self, t):
-        if torch.is_tensor(t):
-            return t.to(self.device, torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
-
     def gradient_step(self, users, pos, cand, epoch, sel_in=None, h_ms=None):
         """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer
         -> (device tensor (mf, emb, total), device int32 [n, H + 1] of the chosen candidate index per row and hop).
@@ -243,9 +198,7 @@ class DENS(AbstractRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"DENS: a batch holds at most {MAX_BATCH} rows (got {n})")
         assert dp.numel() == n and dc.numel() == n * cfg.n_negs
-        need = int(_hip.lib().skr_dens_workspace(n, H))
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow_work(int(_hip.lib().skr_dens_workspace(n, H)))
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
         sel_out = torch.empty((n, H + 1), dtype=torch.int32, device=self.device)
         dsel = None
@@ -279,58 +232,16 @@ class DENS(AbstractRecommender):
         self.step_losses.append(loss)
         return loss
 
-    @on_compute_stream
-    def fit(self):
+    def _make_iterator(self):
         cfg = self.config
-        data_iter = PairwiseIterator(self.dataset.train_data, num_neg=cfg.K * cfg.n_negs, batch_size=cfg.batch_size, shuffle=True,
-                                     drop_last=False, sampler_mode=self.sampler_mode)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=cfg.early_stop)
-        for epoch in range(cfg.epochs):
-            self.step_losses = []
-            for u, i, j in data_iter.iter_device():
-                self.train_step(u, i, j.reshape(-1, cfg.n_negs), epoch)
-            result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
-            if early_stopping(result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+        return PairwiseIterator(self.dataset.train_data, num_neg=cfg.K * cfg.n_negs, batch_size=cfg.batch_size, shuffle=True,
+                                drop_last=False, sampler_mode=self.sampler_mode)
 
-    # ---- ranking ---------------------------------------------------------------------------------
+    def _batches(self, data_iter, epoch):
+        for u, i, j in data_iter.iter_device():
+            yield u, i, j.reshape(-1, self.config.n_negs), epoch
+
+    # ---- ranking: the base class's, on the hop means (DENS.py:469-472) ------------------------------
     def propagate(self):
         """the forward propagation of the CURRENT parameters and the hop means (DENS.py:304-309): pooled = mean_h X_h"""
-        nu, H = self.num_users, self.config.context_hops
-        if H == 0:
-            self.pooled.copy_(self.X0)
-            return self.pooled
-        s = 1.0 / (H + 1)
-        X = self.X0
-        for h in range(1, H + 1):
-            Y = self._hops[h - 1]
-            base = self.X0 if h == 1 else None          # pooled = s X_0 + s X_1, then pooled += s X_h
-            _run_plan(self.adj, X[nu:], Y=Y[:nu], accum=self.pooled[:nu], accum_base=None if base is None else base[:nu], accum_scale=s)
-            _run_plan(self.adj_t, X[:nu], Y=Y[nu:], accum=self.pooled[nu:], accum_base=None if base is None else base[nu:], accum_scale=s)
-            X = Y
-        return self.pooled
-
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        self.propagate()
-        self._pooled_current = True
-        try:
-            return self.evaluator.evaluate(self, test_users)
-        finally:
-            self._pooled_current = False
-
-    def predict_factors(self):
-        """(user table [U, 64], item table [I, 64], None): the hop means of the current parameters"""
-        if not getattr(self, "_pooled_current", False):
-            self.propagate()
-        return self.pooled[:self.num_users], self.pooled[self.num_users:], None
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores (DENS.py:469-472)"""
-        uf, vf, _ = self.predict_factors()
-        return _hip.score_matrix(uf, list(users), vf, None).cpu().numpy()
+        return propagate_mean(self.adj, self.adj_t, self.X0, self.num_users, self.config.context_hops, self.pooled, hops=self._hops)

@@ -21,7 +21,6 @@ its algorithm).
 Limits: dropout == 0, d <= 64, svd_q <= 16, batch_size <= 2048 (NotImplementedError), one GPU.
 """
 import ctypes
-from typing import Dict
 
 import numpy as np
 import torch
@@ -29,10 +28,10 @@ import torch.nn as nn
 
 from .. import _hip
 from ..io import PairwiseIterator
-from ..run_config import RunConfig
-from ..utils.py import EarlyStopping, ModelConfig
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
-from .LightGCN import DeviceCSR
+from ..utils.py import ModelConfig
+from ._graph import GraphRecommender, _device_csr, normalized_adjacency, run_plan, selfcf_adjacency, upload_csr  # noqa: F401
+from .base import DenseAdam, on_compute_stream
+from .LightGCN import DeviceCSR  # noqa: F401
 
 __all__ = ["LightGCL", "LightGCLConfig"]
 
@@ -92,71 +91,13 @@ def init_tables(num_users, num_items, d, q):
     return R, eu, ei
 
 
-def _device_csr(shape, rowptr, col, val):
-    """a DeviceCSR around arrays that are already in HBM"""
-    m = DeviceCSR.__new__(DeviceCSR)
-    m.shape, m.nnz = shape, int(col.numel())
-    m.rowptr, m.col, m.val = rowptr.contiguous(), col.contiguous(), val.contiguous()
-    if m.nnz == 0:
-        m.col = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
-        m.val = torch.zeros(1, dtype=torch.float32, device=rowptr.device)
-    return m
-
-
-def normalized_adjacency(rowptr, col, num_users, num_items):
-    """(A, A^T) as DeviceCSR from the binary train CSR in HBM: values 1 / sqrt(rowdeg * coldeg) (LightGCL.py:185-196),
-    computed on the device -- no loop over the non-zeros, no copy to the host"""
-    dev = rowptr.device
-    rowdeg = (rowptr[1:] - rowptr[:-1])
-    rows = torch.repeat_interleave(torch.arange(num_users, dtype=torch.int64, device=dev), rowdeg)
-    cols = col.to(torch.int64)
-    coldeg = torch.bincount(cols, minlength=num_items)
-    val = 1.0 / (rowdeg[rows].to(torch.float32) * coldeg[cols].to(torch.float32)).sqrt()
-    A = _device_csr((num_users, num_items), rowptr, col, val)
-    order = torch.argsort(cols * num_users + rows)           # the transpose: by column, then by row
-    rp_t = torch.zeros(num_items + 1, dtype=torch.int64, device=dev)
-    rp_t[1:] = torch.cumsum(coldeg, 0)
-    At = _device_csr((num_items, num_users), rp_t, rows[order].to(torch.int32), val[order])
-    return A, At
-
-
-def selfcf_adjacency(rowptr, col, num_users, num_items):
-    """(A, A^T, perm) from the binary train CSR in HBM with SelfCF's normalisation (SelfCF.py:118-123): the float32 of
-    (rowdeg + 1e-7)^-0.5 * (coldeg + 1e-7)^-0.5, powers and product in float64, computed on the device.  ``perm`` (int32
-    [nnz]): the position in A^T's entry order of entry e of A's -- the inverse of the sort that builds the transpose"""
-    dev = rowptr.device
-    rowdeg = (rowptr[1:] - rowptr[:-1])
-    rows = torch.repeat_interleave(torch.arange(num_users, dtype=torch.int64, device=dev), rowdeg)
-    cols = col.to(torch.int64)
-    coldeg = torch.bincount(cols, minlength=num_items)
-    du = (rowdeg.to(torch.float64) + 1e-7).pow(-0.5)
-    di = (coldeg.to(torch.float64) + 1e-7).pow(-0.5)
-    val = (du[rows] * di[cols]).to(torch.float32)
-    A = _device_csr((num_users, num_items), rowptr, col, val)
-    order = torch.argsort(cols * num_users + rows)           # the transpose: by column, then by row
-    rp_t = torch.zeros(num_items + 1, dtype=torch.int64, device=dev)
-    rp_t[1:] = torch.cumsum(coldeg, 0)
-    At = _device_csr((num_items, num_users), rp_t, rows[order].to(torch.int32), val[order])
-    perm = torch.empty(order.numel(), dtype=torch.int32, device=dev)
-    perm[order] = torch.arange(order.numel(), dtype=torch.int32, device=dev)
-    return A, At, perm
-
-
-def _run_plan(mat, X, Y=None, addend=None, accum=None, accum_base=None):
-    ep = _hip.SpmmEpilogue()
-    ep.mode = _hip.EPI_PLAIN
-    ep.addend, ep.Y, ep.accum, ep.accum_base = _hip.ptr(addend), _hip.ptr(Y), _hip.ptr(accum), _hip.ptr(accum_base)
-    ep.accum_scale = 1.0
-    _hip.check(_hip.lib().skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(X), 64, ctypes.byref(ep), None, None, _hip.stream()))
-
-
 def _times(mat, X):
     """mat @ X for a narrow X [n_cols, q <= 64] through the matrix's plan (64-column rows, zero-padded)"""
     q = X.shape[1]
     Xp = torch.zeros((mat.shape[1], 64), dtype=torch.float32, device=X.device)
     Xp[:, :q] = X
     Y = torch.empty((mat.shape[0], 64), dtype=torch.float32, device=X.device)
-    _run_plan(mat, Xp, Y=Y)
+    run_plan(mat, Xp, Y=Y)
     return Y[:, :q].contiguous()
 
 
@@ -177,49 +118,22 @@ def svd_lowrank_device(A, At, R, niter=2):
     return Uf.contiguous(), S, V.contiguous()
 
 
-class LightGCL(AbstractRecommender):
+class LightGCL(GraphRecommender):
+    """limits: dropout == 0, d <= 64, svd_q <= 16, batch_size <= 2048 (NotImplementedError), one GPU.
+    ``svd_factors`` (constructor and ``detached``): (u_mul_s [U, q], v_mul_s [I, q], ut [q, U], vt [q, I]) used instead of
+    the model's own SVD"""
     config_class = LightGCLConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict, svd_factors=None):
-        """limits: dropout == 0, d <= 64, svd_q <= 16, batch_size <= 2048 (NotImplementedError), one GPU.
-        ``svd_factors``: (u_mul_s [U, q], v_mul_s [I, q], ut [q, U], vt [q, I]) used instead of the model's own SVD"""
-        self.config = LightGCLConfig(**model_config)
+    def _check_limits(self, world):
         check_limits(self.config)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        if self.dist.world > 1:
+        if world > 1:
             raise NotImplementedError("LightGCL runs on one GPU: there is no sharded engine for it")
-        self.device = _hip.require_gpu()
-        self.sampler_mode = getattr(run_config, "sampler_mode", None)
-        csr = self.dataset.train_data.to_csr_matrix().tocsr()
-        csr.sum_duplicates()
-        csr.sort_indices()
-        self._build(csr.indptr, csr.indices, svd_factors)
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, svd_factors=None):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        check_limits(self.config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._build(csr[0], csr[1], svd_factors)
-        return self
-
-    def _build(self, rowptr, items, svd_factors):
+    def _build(self, rowptr, items, svd_factors=None):
         cfg, dev = self.config, self.device
         nu, ni, d, q = self.num_users, self.num_items, cfg.d, cfg.svd_q
         N = nu + ni
-        if torch.is_tensor(rowptr):
-            rp, col = rowptr.to(dev, torch.int64).contiguous(), items.to(dev, torch.int32).contiguous()
-        else:
-            rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-            col = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(dev)
+        rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t = normalized_adjacency(rp, col, nu, ni)
         R, eu, ei = init_tables(nu, ni, d, q)
@@ -278,11 +192,6 @@ class LightGCL(AbstractRecommender):
         a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
         return a
 
-    def _ids(self, t):
-        if torch.is_tensor(t):
-            return t.to(self.device, torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
-
     def gradient_step(self, uids, pos, neg, h_ms=None):
         """forward and backward of one batch without the optimiser: the gradient of E_0 is left in the optimiser's gradient
         buffer, the sums in ``self.sums`` -> device tensor (bpr, cl, reg, total).  ``h_ms``: a ctypes float array of
@@ -292,9 +201,7 @@ class LightGCL(AbstractRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"LightGCL: a batch holds at most {MAX_BATCH} pairs (got {n})")
         assert dp.numel() == n and dn.numel() == n
-        need = int(_hip.lib().skr_lightgcl_workspace(n, self.num_users, self.num_items))
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow_work(int(_hip.lib().skr_lightgcl_workspace(n, self.num_users, self.num_items)))
         loss = torch.empty(4, dtype=torch.float32, device=self.device)
         a = self._step_args(du, dp, dn, loss)
         if h_ms is None:
@@ -313,23 +220,12 @@ class LightGCL(AbstractRecommender):
         self.step_losses.append(loss)
         return loss
 
-    @on_compute_stream
-    def fit(self):
-        data_iter = PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True, drop_last=False,
-                                     sampler_mode=self.sampler_mode)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.step_losses = []
-            for u, i, j in data_iter.iter_device():
-                self.train_step(u, i, j)
-            result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
-            if early_stopping(result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+    def _make_iterator(self):
+        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True, drop_last=False,
+                                sampler_mode=self.sampler_mode)
+
+    def _batches(self, data_iter, epoch):
+        return data_iter.iter_device()
 
     # ---- ranking ---------------------------------------------------------------------------------
     def propagate(self):
@@ -341,8 +237,8 @@ class LightGCL(AbstractRecommender):
             Y = None if last else self._ping[(l - 1) & 1]
             acc = self.sums if last else self._below
             base = (self.E0 if L == 1 else self._below) if last else (self.E0 if l == 1 else None)
-            _run_plan(self.adj, X[nu:], Y=None if Y is None else Y[:nu], accum=acc[:nu], accum_base=None if base is None else base[:nu])
-            _run_plan(self.adj_t, X[:nu], Y=None if Y is None else Y[nu:], accum=acc[nu:], accum_base=None if base is None else base[nu:])
+            run_plan(self.adj, X[nu:], Y=None if Y is None else Y[:nu], accum=acc[:nu], accum_base=None if base is None else base[:nu])
+            run_plan(self.adj_t, X[:nu], Y=None if Y is None else Y[nu:], accum=acc[nu:], accum_base=None if base is None else base[nu:])
             X = Y
         self._sums_current = True
         return self.sums
@@ -357,8 +253,3 @@ class LightGCL(AbstractRecommender):
         if not self._sums_current:
             self.propagate()
         return self.sums[:self.num_users], self.sums[self.num_users:], None
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores (LightGCL.py:247-250)"""
-        uf, vf, _ = self.predict_factors()
-        return _hip.score_matrix(uf, list(users), vf, None).cpu().numpy()

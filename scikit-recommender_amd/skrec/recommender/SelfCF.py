@@ -26,18 +26,15 @@ takes recorded values instead and replays a recorded run.
 Limits (NotImplementedError): embed_dim <= 64, n_layers <= 4, batch_size <= 2048, one GPU.
 """
 import ctypes
-from typing import Dict
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import InteractionIterator
-from ..run_config import RunConfig
-from ..utils.py import EarlyStopping, ModelConfig
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
-from .LightGCL import selfcf_adjacency
+from ..utils.py import ModelConfig
+from ._graph import GraphRecommender, linear_block, propagate_mean, selfcf_adjacency, upload_csr
+from .base import DenseAdam, on_compute_stream
 
 __all__ = ["SelfCF", "SelfCFConfig"]
 
@@ -97,53 +94,21 @@ def init_parameters(num_users, num_items, d):
     return eu, ei, lin.weight.detach().clone(), lin.bias.detach().clone()
 
 
-def _epilogue(Y=None, accum=None, accum_base=None, accum_scale=1.0):
-    ep = _hip.SpmmEpilogue()
-    ep.mode = _hip.EPI_PLAIN
-    ep.Y, ep.accum, ep.accum_base = _hip.ptr(Y), _hip.ptr(accum), _hip.ptr(accum_base)
-    ep.accum_scale = accum_scale
-    return ep
-
-
-class SelfCF(AbstractRecommender):
+class SelfCF(GraphRecommender):
+    """limits: see ``check_limits``; ``seed`` (``detached``; the run's seed otherwise): the key of the device draws"""
     config_class = SelfCFConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: see ``check_limits``"""
-        self.config = SelfCFConfig(**model_config)
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        check_limits(self.config, self.dist.world)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        self.device = _hip.require_gpu()
-        csr = self.dataset.train_data.to_csr_matrix().tocsr()
-        csr.sum_duplicates()
-        csr.sort_indices()
-        self._build(csr.indptr, csr.indices, int(getattr(run_config, "seed", 0) or 0))
+    def _check_limits(self, world):
+        check_limits(self.config, world)
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, seed=0):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors); ``seed``: the key of the device draws"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        check_limits(self.config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._build(csr[0], csr[1], int(seed))
-        return self
+    def _build_args(self, run_config):
+        return {"seed": getattr(run_config, "seed", 0) or 0}
 
-    def _build(self, rowptr, items, seed):
+    def _build(self, rowptr, items, seed=0):
         cfg, dev = self.config, self.device
         nu, ni, d, L = self.num_users, self.num_items, cfg.embed_dim, cfg.n_layers
         N = nu + ni
-        if torch.is_tensor(rowptr):
-            rp, col = rowptr.to(dev, torch.int64).contiguous(), items.to(dev, torch.int32).contiguous()
-        else:
-            rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-            col = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(dev)
+        rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t, self.perm = selfcf_adjacency(rp, col, nu, ni)
         self.nnz = int(col.numel())
@@ -151,8 +116,8 @@ class SelfCF(AbstractRecommender):
         flat = torch.zeros(N * 64 + PRED_FLOATS, dtype=torch.float32)
         rows = flat[:N * 64].view(N, 64)
         rows[:nu, :d], rows[nu:, :d] = eu, ei
-        flat[N * 64:N * 64 + 4096].view(64, 64)[:d, :d] = W
-        flat[N * 64 + 4096:N * 64 + 4096 + d] = b
+        Wv, bv = self._pred_view(flat)
+        Wv[:], bv[:] = W, b
         self._flat = flat.to(dev).contiguous()
         self.X0 = self._flat[:N * 64].view(N, 64)
         self._pred = self._flat[N * 64:]
@@ -169,13 +134,11 @@ class SelfCF(AbstractRecommender):
         self._item_bias = torch.zeros(ni, dtype=torch.float32, device=dev)
         self._user_const = torch.zeros(nu, dtype=torch.float32, device=dev)
         self._work = torch.empty(int(_hip.lib().skr_selfcf_workspace(min(cfg.batch_size, MAX_BATCH), L)), dtype=torch.uint8, device=dev)
-        self._seed, self._step = seed, 0
+        self._seed, self._step = int(seed), 0
         self.step_losses = []          # (cosine, reg, total) per training step, device tensors [3]
 
     def _pred_view(self, flat):
-        N, d = self.num_users + self.num_items, self.config.embed_dim
-        blk = flat[N * 64:]
-        return blk[:4096].view(64, 64)[:d, :d], blk[4096:4096 + d]
+        return linear_block(flat[(self.num_users + self.num_items) * 64:], self.config.embed_dim)
 
     def parameters(self):
         """{name: tensor} in the reference's shapes (copies): user_emb, item_emb, predictor.weight, predictor.bias"""
@@ -203,18 +166,6 @@ class SelfCF(AbstractRecommender):
         b.copy_(t(named["predictor.bias"]))
 
     # ---- training --------------------------------------------------------------------------------
-    def _ids(self, t):
-        if torch.is_tensor(t):
-            return t.to(self.device, torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
-
-    def _flags(self, t, shape):
-        if not torch.is_tensor(t):
-            t = torch.from_numpy(np.ascontiguousarray(t).astype(np.uint8))
-        t = t.to(self.device, torch.uint8).contiguous()
-        assert tuple(t.shape) == tuple(shape), f"keep flags of shape {tuple(t.shape)}, expected {tuple(shape)}"
-        return t
-
     def edge_keeps(self, rate, edge_keep=None, step=None):
         """the four keep arrays of one step (``skr_selfcf_keeps``) -> uint8 [4, nnz]: forward user rows, forward item rows,
         backward user rows, backward item rows.  ``edge_keep`` = (k1, k2): the user-row half in the train CSR's order and the
@@ -244,9 +195,7 @@ class SelfCF(AbstractRecommender):
             rate = np.random.random()
         rate = float(rate)
         assert 0.0 <= rate < 1.0
-        need = int(_hip.lib().skr_selfcf_workspace(n, L))
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow_work(int(_hip.lib().skr_selfcf_workspace(n, L)))
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
         ku = ki = None
         if target_keep is not None:
@@ -280,60 +229,18 @@ class SelfCF(AbstractRecommender):
         self.step_losses.append(loss)
         return loss
 
-    @on_compute_stream
-    def fit(self):
-        cfg = self.config
-        data_iter = InteractionIterator(self.dataset.train_data, batch_size=cfg.batch_size, shuffle=True, drop_last=False)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=cfg.early_stop)
-        for epoch in range(cfg.epochs):
-            self.step_losses = []
-            for users, items in data_iter:
-                self.train_step(users, items)
-            result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
-            if early_stopping(result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
-
     # ---- ranking ---------------------------------------------------------------------------------
     def propagate(self):
         """the plain, un-dropped propagation of the CURRENT parameters and the layer means (SelfCF.py:170-187), then the
         query rows, the item bias and the per-user constant of the folded score (``skr_selfcf_queries``) -> pooled"""
-        nu, L = self.num_users, self.config.n_layers
-        L_ = _hip.lib()
-        if L == 0:
-            self.pooled.copy_(self.X0)
-        else:
-            s = 1.0 / (L + 1)
-            X = self.X0
-            for k in range(1, L + 1):
-                Y = None if k == L else self._ping[(k - 1) & 1]
-                base = self.X0 if k == 1 else None          # pooled = s X_0 + s X_1, then pooled += s X_k
-                for mat, lo, hi, xs in ((self.adj, 0, nu, X[nu:]), (self.adj_t, nu, None, X[:nu])):
-                    ep = _epilogue(Y=None if Y is None else Y[lo:hi], accum=self.pooled[lo:hi],
-                                   accum_base=None if base is None else base[lo:hi], accum_scale=s)
-                    _hip.check(L_.skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(xs), 64, ctypes.byref(ep), None, None, _hip.stream()))
-                X = Y
-        _hip.check(L_.skr_selfcf_queries(_hip.ptr(self._pred), _hip.ptr(self.pooled), nu, self.num_items, _hip.ptr(self._Q),
-                                         _hip.ptr(self._item_bias), _hip.ptr(self._user_const), _hip.stream()))
+        nu = self.num_users
+        propagate_mean(self.adj, self.adj_t, self.X0, nu, self.config.n_layers, self.pooled, ping=self._ping)
+        _hip.check(_hip.lib().skr_selfcf_queries(_hip.ptr(self._pred), _hip.ptr(self.pooled), nu, self.num_items, _hip.ptr(self._Q),
+                                                 _hip.ptr(self._item_bias), _hip.ptr(self._user_const), _hip.stream()))
         return self.pooled
 
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        self.propagate()
-        self._pooled_current = True
-        try:
-            return self.evaluator.evaluate(self, test_users)
-        finally:
-            self._pooled_current = False
-
-    def predict_factors(self):
+    def _factors(self):
         """(query rows (W + W^T) M_u [U, 64], item table M_i [I, 64], item bias <b, M_i> [I]) of the current parameters"""
-        if not getattr(self, "_pooled_current", False):
-            self.propagate()
         return self._Q, self.pooled[self.num_users:], self._item_bias
 
     def predict(self, users) -> np.ndarray:

@@ -26,6 +26,18 @@ def random_csr(rng, n_users, n_items, lo, hi, empty_frac=0.1):
     return rowptr, np.ascontiguousarray(items, np.int32)
 
 
+def graph_70x45():
+    """(rowptr, items) of a 70 x 45 binary train matrix of about 300 entries; user 17 has no item, item 44 no user"""
+    U, I = 70, 45
+    rng = np.random.default_rng(7045)
+    lens = rng.integers(1, 9, U)
+    lens[17] = 0
+    rowptr = np.zeros(U + 1, np.int64)
+    rowptr[1:] = np.cumsum(lens)
+    items = np.concatenate([np.sort(rng.choice(I - 1, int(l), replace=False)) for l in lens]).astype(np.int32)
+    return rowptr, items
+
+
 def tiny_arrays(golden):
     d = golden("tiny_dataset")
     tr = d["train"]
