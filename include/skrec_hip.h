@@ -314,7 +314,11 @@ int skr_csr_spmm_strided(int n_rows, const int64_t* d_rowptr, const int32_t* d_c
  *                         (SKR_SPMM_HOT=0: off)
  *                         SKR_SPMM_WINDOWS=n (default 1) makes the short-row kernel gather from X in n column windows, one
  *                         launch each (an experiment switch: no gain measured at X = 256 MB)
- * A plan may be run any number of times, by one stream at a time (the scratch buffer is shared between runs). */
+ *                         SKR_SPMM_HOT_DENSITY, SKR_SPMM_HOT_WGS, SKR_SPMM_CBLK and SKR_SPMM_WINDOWS are read when a plan is
+ *                         created; the switches of a run (SKR_SPMM_HOT, _HOT_PF, _ROWS_WGS, _TASK_WGS, _TASK_SPAN) once per process
+ * A plan may be run any number of times, by one stream at a time (the scratch buffer is shared between runs).
+ * X must be finite in a run without d_col_mask and d_keep: short lists are padded with column 0 of the row or of the block
+ * of X times 0, so a NaN or Inf there would reach rows that do not name that column. */
 typedef struct skr_spmm_plan skr_spmm_plan;
 int skr_spmm_plan_create(int n_rows, int n_cols, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val,
                          int64_t nnz, int long_rows_from, skr_spmm_plan** out, void* stream);
@@ -323,8 +327,9 @@ int skr_spmm_plan_run(const skr_spmm_plan* plan, const float* d_X, int dim, cons
 /* The same product where parts of it are known not to be needed (LightGCN's step: only the batch's rows of the LAST
  * forward layer are read, and the gradient that enters the FIRST backward hop is zero outside the batch's rows):
  *   d_row_mask  uint8[n_rows] or NULL: rows with a 0 byte are skipped entirely (their Y / accum rows are left as they are)
- *   d_col_mask  uint8[n_cols] or NULL: entries whose column has a 0 byte are skipped -- the caller guarantees that those
- *               rows of X are zero, so the result is the full product's (up to the sign of a zero)
+ *   d_col_mask  uint8[n_cols] or NULL: entries whose column has a 0 byte are skipped, and the rows of X of those columns are
+ *               not read (they may hold anything, NaN included): the result is the product of the marked entries -- the
+ *               full product's, up to the sign of a zero, where those rows of X are zero
  * skr_mark_ids sets d_mask[offset + ids[k]] = 1 (negative ids skipped); clear the mask first. */
 int skr_spmm_plan_run_masked(const skr_spmm_plan* plan, const float* d_X, int dim, const float* d_addend, float* d_Y,
                              float* d_accum, float accum_scale, const uint8_t* d_row_mask, const uint8_t* d_col_mask,
@@ -379,10 +384,11 @@ int skr_spmm_plan_run_ex(const skr_spmm_plan* plan, const float* d_X, int dim, c
 /* The product with per-ENTRY dropout (edge dropout drawn anew for every step, no new plan):
  *   A'[e] = d_keep[e] ? val[e] * scale : 0     (one fp32 multiply; the reference's v[mask] * (1. / (1 - rate)),
  *                                                recommender/SelfCF.py:133-144, with scale = float32(1 / (1 - rate)))
- * d_keep: uint8 [nnz] in the plan's CSR entry order.  A dropped entry is SKIPPED: its row of X is not gathered.  Same row /
- * task / reduce structure and the same fixed order of additions as skr_spmm_plan_run_ex; the plan's densest rows go through
- * the task path (their block-major copies hold no flags).  No float atomic: repeated runs are bit-identical.  SKR_EPI_PLAIN
- * only (any other mode: SKR_EINVAL); a row whose entries are all dropped still gets its epilogue (y = addend_r or 0). */
+ * d_keep: uint8 [nnz] in the plan's CSR entry order.  A dropped entry is SKIPPED: its row of X is not read (where every entry
+ * of a column is dropped, that row of X may hold anything, NaN included).  Same row / task / reduce structure and the same
+ * fixed order of additions as skr_spmm_plan_run_ex; the plan's densest rows go through the task path (their block-major
+ * copies hold no flags).  No float atomic: repeated runs are bit-identical.  SKR_EPI_PLAIN only (any other mode: SKR_EINVAL);
+ * a row whose entries are all dropped still gets its epilogue (y = addend_r or 0). */
 int skr_spmm_plan_run_dropped(const skr_spmm_plan* plan, const float* d_X, int dim, const skr_spmm_epilogue* epi,
                               const uint8_t* d_keep, float scale, void* stream);
 int skr_spmm_plan_info(const skr_spmm_plan* plan, int64_t* h_info4);

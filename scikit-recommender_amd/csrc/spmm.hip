@@ -97,20 +97,27 @@ __device__ __forceinline__ void sum_groups(float4& acc) {
     acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
 }
 
-// keep only the entries whose column is marked in `col_mask` (the others would multiply rows of X that are known to be
-// zero): kept entries move to the front of the block in their order, the others behind them with value 0; returns how
-// many were kept.  Every lane takes part in the two permutes.
-// (tried in round 3: the mask as bits in LDS instead of a byte per entry out of L2 -- LightGCN 10.92-10.94 vs 10.96 ms per step:
-//  the mask look-ups are not what the column-masked products wait for)
-__device__ __forceinline__ int keep_marked(const uint8_t* __restrict__ col_mask, int lane, int m, int& cl, float& vl) {
-    const bool keep = lane < m && col_mask[cl] != 0;
+// the kept entries of a block of 64 (one per lane in cl / vl) move to the front in their order; returns how many were kept.
+// The lanes that are not kept -- skipped entries and lanes behind the block's end -- go behind them with value 0 and the
+// column of the FIRST KEPT entry: gather_block's tail loop gathers up to three of those columns, and the X row of a skipped
+// entry must not be read (it may hold anything, a NaN included).  With nothing kept nothing is gathered.  Every lane takes
+// part in the two permutes.
+__device__ __forceinline__ int compact_kept(bool keep, int lane, int& cl, float& vl) {
     const unsigned long long b = __ballot(keep);
     const int kept = __popcll(b);
     const int below = __popcll(b & ((1ull << lane) - 1ull));
     const int dst = keep ? below : kept + (lane - below);
-    cl = __builtin_amdgcn_ds_permute(dst << 2, cl);
+    const int first = __builtin_amdgcn_readlane(cl, b ? __ffsll(static_cast<long long>(b)) - 1 : 0);
+    cl = __builtin_amdgcn_ds_permute(dst << 2, keep ? cl : first);
     vl = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(keep ? vl : 0.0f)));
     return kept;
+}
+
+// keep only the entries whose column is marked in `col_mask`: the rows of X of the other columns are not read
+// (tried in round 3: the mask as bits in LDS instead of a byte per entry out of L2 -- LightGCN 10.92-10.94 vs 10.96 ms per step:
+//  the mask look-ups are not what the column-masked products wait for)
+__device__ __forceinline__ int keep_marked(const uint8_t* __restrict__ col_mask, int lane, int m, int& cl, float& vl) {
+    return compact_kept(lane < m && col_mask[cl] != 0, lane, cl, vl);
 }
 
 // ---- what happens to a finished row (skr_spmm_epilogue, include/skrec_hip.h) ---------------------------------------------
@@ -373,17 +380,8 @@ __global__ __launch_bounds__(256) void spmm_reduce_kernel(const int32_t* __restr
 // ---- dropped runs (skr_spmm_plan_run_dropped): per-ENTRY keep flags, drawn anew by the caller for every step ---------------
 // Siblings of spmm_rows_kernel / spmm_tasks_kernel, same row / task / reduce structure and the same order of additions: an
 // entry e counts as val[e] * scale when keep[e] != 0 and is SKIPPED otherwise -- its row of X is not gathered.  The kept
-// entries of a block of 64 move to the front in their order (as keep_marked does for marked columns), so a run whose flags
+// entries of a block of 64 move to the front in their order (compact_kept, as for marked columns), so a run whose flags
 // are all set adds the same terms in the same order as the plain run.
-__device__ __forceinline__ int compact_kept(bool keep, int lane, int& cl, float& vl) {
-    const unsigned long long b = __ballot(keep);
-    const int kept = __popcll(b);
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    const int dst = keep ? below : kept + (lane - below);
-    cl = __builtin_amdgcn_ds_permute(dst << 2, cl);
-    vl = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(keep ? vl : 0.0f)));
-    return kept;
-}
 
 __global__ __launch_bounds__(ROW_WAVES * 64) void spmm_rows_dropped_kernel(int n_rows, int long_thr, const int64_t* __restrict__ rowptr,
                                                                            const int32_t* __restrict__ col, const float* __restrict__ val,
@@ -399,7 +397,7 @@ __global__ __launch_bounds__(ROW_WAVES * 64) void spmm_rows_dropped_kernel(int n
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t e = rb; e < re; e += 64) {
             int m = static_cast<int>(re - e < 64 ? re - e : 64);
-            int cl = col[rb];              // dropped and padding lanes: a valid column, value 0, behind the kept ones
+            int cl = 0;                    // dropped and padding lanes: compact_kept gives them a kept entry's column, value 0
             float vl = 0.0f;
             const bool k = lane < m && keep[e + lane] != 0;
             if (k) { cl = col[e + lane]; vl = val[e + lane] * scale; }
@@ -430,7 +428,7 @@ __global__ __launch_bounds__(ROW_WAVES * 64) void spmm_tasks_dropped_kernel(cons
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int e0 = 0; e0 < len; e0 += 64) {
             int m = len - e0 < 64 ? len - e0 : 64;
-            int cl = col[tk.beg];          // dropped and padding lanes: the task's first column, an address inside the block
+            int cl = 0;                    // dropped and padding lanes: compact_kept gives them a kept entry's column, value 0
             float vl = 0.0f;
             const bool k = lane < m && keep[tk.beg + e0 + lane] != 0;
             if (k) { cl = col[tk.beg + e0 + lane]; vl = val[tk.beg + e0 + lane] * scale; }
@@ -904,7 +902,9 @@ int skr_spmm_plan_create(int n_rows, int n_cols, const int64_t* d_rowptr, const 
         // 3. the densest rows: at least `dens` entries per HOT_UB columns on average (SKR_SPMM_HOT_DENSITY, default 4; 0: none).
         //    Chosen on the host from the long rows' lengths (a few thousand numbers): the densest first, a row far heavier than a
         //    wavefront's fair share cut into pieces, pieces dealt to the 8 wavefronts' 16 slots by load (largest first).
-        static const double dens = [] { const char* e = getenv("SKR_SPMM_HOT_DENSITY"); return e ? atof(e) : 4.0; }();
+        //    Read per plan, like SKR_SPMM_CBLK above: creating a plan synchronises the stream anyway.
+        const char* dens_env = getenv("SKR_SPMM_HOT_DENSITY");
+        const double dens = dens_env ? atof(dens_env) : 4.0;
         if (dens > 0.0 && n_cols >= HOT_UB) {
             int64_t* d_deg = nullptr;
             PLAN_HIP(hipMalloc(&d_deg, sizeof(int64_t) * n_long));
@@ -966,7 +966,9 @@ int skr_spmm_plan_create(int n_rows, int n_cols, const int64_t* d_rowptr, const 
                 p->n_hot = static_cast<int>(kept.size());
                 p->n_virt = static_cast<int>(virt.size());
                 p->n_ub = (n_cols + HOT_UB - 1) / HOT_UB;
-                static const int wgs_max = [] { const char* e = getenv("SKR_SPMM_HOT_WGS"); const int v = e ? atoi(e) : HOT_WGS; return v < 1 ? 1 : (v > 2048 ? 2048 : v); }();
+                const char* wgs_env = getenv("SKR_SPMM_HOT_WGS");      // workgroups of the LDS-streamed kernel at most (per plan)
+                const int wgs_cfg = wgs_env ? atoi(wgs_env) : HOT_WGS;
+                const int wgs_max = wgs_cfg < 1 ? 1 : (wgs_cfg > 2048 ? 2048 : wgs_cfg);
                 p->hot_wgs = p->n_ub < wgs_max ? p->n_ub : wgs_max;
                 std::vector<int32_t> h_rows(p->n_hot), h_vptr(p->n_hot + 1, 0), h_vidx;
                 std::vector<uint8_t> h_flag(n_long, 0);

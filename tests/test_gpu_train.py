@@ -150,6 +150,7 @@ def test_csr_spmm_vs_scipy(n_rows, density, heavy, plan, monkeypatch):
     if plan == "1":
         info = csr.plan_info()
         assert info["long_rows"] == heavy and (info["tasks"] > 0) == (heavy > 0), info
+        assert info["hot_rows"] == heavy, info       # the heavy rows name >= 4 of 128 columns on average: through LDS, not tasks
 
 
 @pytest.mark.parametrize("windows", [None, "3"])
@@ -309,6 +310,9 @@ def test_spmm_row_epilogues_equal_the_separate_passes(plan, monkeypatch):
     A[n // 3, :] = 0
     A.eliminate_zeros()
     csr = DeviceCSR(A, dev())
+    if plan == "1":
+        info = csr.plan_info()
+        assert info["long_rows"] == 3 and info["hot_rows"] == 3, info      # the long rows' epilogues run in spmm_hot_reduce_kernel
     X, E, add, acc0, dE0 = (to_dev(rng.standard_normal((n, 64)).astype(np.float32)) for _ in range(5))
     mask_np = (rng.random(n) < 0.3).astype(np.uint8)
     mask_np[[1, 12, 23]] = [1, 0, 1]
