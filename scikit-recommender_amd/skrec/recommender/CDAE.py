@@ -30,18 +30,16 @@ item), equal to the reference's torch draws in law only.
 Limits: hidden_dim <= 64 (NotImplementedError), batch_size <= 1024, loss_func sigmoid_cross_entropy, one GPU.
 """
 import os
-from typing import Dict
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..run_config import RunConfig
-from ..utils.py import BatchIterator, EarlyStopping, ModelConfig
+from ..utils.py import BatchIterator, ModelConfig
 from ..utils.torch import get_initializer
-from ._graph import train_csr
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from ._graph import train_csr, upload_csr
+from .base import DenseAdam, DeviceRecommender, on_compute_stream
 
 __all__ = ["CDAE", "CDAEConfig"]
 
@@ -147,52 +145,31 @@ class _Block(object):
                  "ids", "per")
 
 
-class CDAE(AbstractRecommender):
+class CDAE(DeviceRecommender):
+    """limits: hidden_dim <= 64 (NotImplementedError), batch_size <= 1024 and the reference's own refusals (ValueError),
+    one GPU.  ``seed`` (``detached``; the run's seed otherwise): the key of the device's keep flags"""
     config_class = CDAEConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: hidden_dim <= 64 (NotImplementedError), batch_size <= 1024 and the reference's own refusals
-        (ValueError), one GPU"""
-        self.config = CDAEConfig(**model_config)
+    def _check_limits(self, world):
         check_limits(self.config)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        if self.dist.world > 1:
+        if world > 1:
             raise NotImplementedError("CDAE runs on one GPU: there is no sharded engine for it")
-        self.device = _hip.require_gpu()
-        self.seed = int(getattr(run_config, "seed", 0) or 0)
-        self._build(*train_csr(self.dataset))
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, seed=0):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        check_limits(self.config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self.seed = int(seed)
-        self._build(csr[0], csr[1])
-        return self
+    def _train_inputs(self):
+        return train_csr(self.dataset)
 
-    def _build(self, rowptr, items):
+    def _build_args(self, run_config):
+        return {"seed": getattr(run_config, "seed", 0) or 0}
+
+    def _build(self, rowptr, items, seed=0):
         cfg = self.config
         d, nu, ni = check_limits(cfg), self.num_users, self.num_items
         self.d = d
+        self.seed = int(seed)
         self.keep_prob = 1 - cfg.dropout
         self.act = _hip.SKR_CDAE_SIGMOID if cfg.hidden_act == "sigmoid" else _hip.SKR_CDAE_IDENTITY
-        if torch.is_tensor(rowptr):                                    # device arrays as they are (timing tools)
-            self._rowptr = rowptr.to(self.device, torch.int64).contiguous()
-            self._items = items.to(self.device, torch.int32).contiguous()
-            self._rowptr_host = self._rowptr.cpu().numpy()
-        else:
-            self._rowptr_host = np.ascontiguousarray(rowptr, dtype=np.int64)
-            self._rowptr = torch.from_numpy(self._rowptr_host).to(self.device)
-            self._items = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(self.device)
+        self._rowptr, self._items = upload_csr(rowptr, items, self.device)
+        self._rowptr_host = self._rowptr.cpu().numpy() if torch.is_tensor(rowptr) else np.ascontiguousarray(rowptr, dtype=np.int64)
         assert self._rowptr_host.shape[0] == nu + 1
         en, off, de, bias, user = _init_tables(nu, ni, d)
         pad = lambda t: nn.functional.pad(t, (0, 64 - d))              # noqa: E731
@@ -387,27 +364,14 @@ class CDAE(AbstractRecommender):
         self.step_losses = losses
         return losses
 
-    @on_compute_stream
-    def fit(self):
+    def _make_iterator(self):
         train_users = [u for u in range(self.num_users) if self._rowptr_host[u + 1] > self._rowptr_host[u]]
-        user_iter = BatchIterator(train_users, batch_size=self.config.batch_size, shuffle=True, drop_last=False)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.train_epoch([np.asarray(b, dtype=np.int32) for b in user_iter])
-            cur_result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
-            if early_stopping(cur_result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+        return BatchIterator(train_users, batch_size=self.config.batch_size, shuffle=True, drop_last=False)
+
+    def _run_epoch(self, data_iter, epoch):
+        self.train_epoch([np.asarray(b, dtype=np.int32) for b in data_iter])      # one pass of the iterator: one shuffle
 
     # ---- ranking ---------------------------------------------------------------------------------
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        return self.evaluator.evaluate(self, test_users)
-
     @on_compute_stream
     def predict_factors(self):
         """(Q [num_users, 64], E_de [num_items, 64], bias [num_items]): score = <Q[u], E_de[i]> + bias[i].  Q is computed by
@@ -420,8 +384,3 @@ class CDAE(AbstractRecommender):
                                                    _hip.stream()))
             self._q_current = True
         return self._Q, self._de, self._bias
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores (CDAE.py:220-224)"""
-        Q, E_de, bias = self.predict_factors()
-        return _hip.score_matrix(Q, list(users), E_de, bias).cpu().numpy()

@@ -7,13 +7,10 @@ reference's order, so a given ``--seed`` yields the reference's initial tables),
 One training step is ``skr_fpmc_step`` (gathers + both scores + loss + gradient scatter fused) and the Adam update of
 the flat [UI | IU | IL | LI] buffer (skrec/recommender/_seq.py).
 """
-from typing import Dict
-
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..run_config import RunConfig
 from ..utils.py import ModelConfig
 from ..utils.torch import get_initializer
 from ._seq import SeqPairwiseRecommender
@@ -53,11 +50,8 @@ def _init_tables(num_users, num_items, dim):
 class FPMC(SeqPairwiseRecommender):
     config_class = FPMCConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        self.config = FPMCConfig(**model_config)
-        super().__init__(run_config, self.config)
-
-    def _build(self):
+    def _build(self, last_items=None):
+        super()._build(last_items)
         from .LightGCN import pad_columns, padded_width
         nu, ni, e = self.num_users, self.num_items, self.config.embed_size
         self.dp = d = padded_width(e)

@@ -22,19 +22,16 @@ Where the reference's own code fails -- a last batch of exactly one instance, or
 change rank (HGN.py:111,128-138) -- the kernel computes the mathematically intended result; there is no parity claim
 for those shapes.
 """
-from typing import Dict
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
 from ..io import SequentialPairwiseIterator
-from ..run_config import RunConfig
 from ..utils.py import ModelConfig
 from ..utils.torch import get_initializer
 from ._seq import SeqPairwiseRecommender
-from .base import on_compute_stream
+from .base import DeviceRecommender, on_compute_stream
 
 __all__ = ["HGN", "HGNConfig"]
 
@@ -91,28 +88,31 @@ def _init_tables(num_users, num_rows, dim, seq_L, pad_idx):
 
 
 class HGN(SeqPairwiseRecommender):
+    """limits: embed_size <= 64 (NotImplementedError beyond), 1 <= seq_L <= 32 and 1 <= seq_T <= 16 (ValueError:
+    ``skr_hgn_step`` holds an instance's window, instance gates and targets one per lane), one GPU.
+    ``detached``: ``num_items`` without the padding item"""
     config_class = HGNConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: embed_size <= 64 (NotImplementedError beyond), 1 <= seq_L <= 32 and 1 <= seq_T <= 16 (ValueError:
-        ``skr_hgn_step`` holds an instance's window, instance gates and targets one per lane), one GPU"""
-        self.config = HGNConfig(**model_config)
-        super().__init__(run_config, self.config)
+    def _check_limits(self, world):
+        e, Lw, T = self.config.embed_size, self.config.seq_L, self.config.seq_T
+        if e > 64:
+            raise NotImplementedError(f"HGN: embed_size <= 64 (got {e}): rows are 64 floats, the gate matrices live in LDS "
+                                      f"and the fused evaluator ranks 64 columns")
+        if not (1 <= Lw <= _hip.SKR_HGN_MAX_L and 1 <= T <= _hip.SKR_HGN_MAX_T):
+            raise ValueError(f"HGN: 1 <= seq_L <= {_hip.SKR_HGN_MAX_L} and 1 <= seq_T <= {_hip.SKR_HGN_MAX_T} "
+                             f"(got {Lw}, {T}): skr_hgn_step holds an instance's window and targets one per lane")
+        super()._check_limits(world)
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, windows=None):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (timing tools);
-        ``num_items`` without the padding item; ``windows``: int32 [num_users, seq_L], every user's last seq_L training
-        items, left-padded with ``num_items`` (default: item 0 in every position)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._set_last_items(np.zeros(self.num_users, np.int32))
-        self.step_losses = None
-        self._detached_windows = windows
-        self._build()
-        return self
+    def _build_args(self, run_config):
+        kw = super()._build_args(run_config)
+        # every user's window of the last seq_L training items; a user without history gets -1 (predict raises first)
+        Lw, pad = self.config.seq_L, self.num_items                    # the padding item: HGN.py:173-174
+        self.user_truncated_seq = self.dataset.train_data.to_truncated_seq_dict(Lw, pad_value=pad, padding="pre",
+                                                                                truncating="pre")
+        win = np.full((self.num_users, Lw), -1, np.int32)
+        for u, row in self.user_truncated_seq.items():
+            win[int(u)] = row
+        return dict(kw, windows=win)
 
     @property
     def _weight_decay(self):
@@ -123,31 +123,20 @@ class HGN(SeqPairwiseRecommender):
         return SequentialPairwiseIterator(self.dataset.train_data, num_previous=cfg.seq_L, num_next=cfg.seq_T,
                                           pad=self.pad_idx, batch_size=cfg.batch_size, shuffle=True, drop_last=False)
 
-    def _build(self):
+    def _build(self, windows=None, last_items=None):
+        """``windows``: int32 [num_users, seq_L], every user's last seq_L training items, left-padded with the padding item
+        (``detached``'s default: item 0 in every position)"""
         from .LightGCN import pad_columns
+        super()._build(last_items)
         cfg = self.config
         e, Lw, T = cfg.embed_size, cfg.seq_L, cfg.seq_T
-        if e > 64:
-            raise NotImplementedError(f"HGN: embed_size <= 64 (got {e}): rows are 64 floats, the gate matrices live in LDS "
-                                      f"and the fused evaluator ranks 64 columns")
-        if not (1 <= Lw <= _hip.SKR_HGN_MAX_L and 1 <= T <= _hip.SKR_HGN_MAX_T):
-            raise ValueError(f"HGN: 1 <= seq_L <= {_hip.SKR_HGN_MAX_L} and 1 <= seq_T <= {_hip.SKR_HGN_MAX_T} "
-                             f"(got {Lw}, {T}): skr_hgn_step holds an instance's window and targets one per lane")
         self.pad_idx = self.num_items                 # HGN.py:173-174
         self.num_items += 1
         nu, ni, d = self.num_users, self.num_items, 64
         self.dp = d
-        # every user's window of the last seq_L training items; a user without history gets -1 (predict raises first)
-        win = np.full((nu, Lw), -1, np.int32)
-        if getattr(self, "dataset", None) is not None:
-            self.user_truncated_seq = self.dataset.train_data.to_truncated_seq_dict(Lw, pad_value=self.pad_idx,
-                                                                                    padding="pre", truncating="pre")
-            for u, row in self.user_truncated_seq.items():
-                win[int(u)] = row
-        elif self._detached_windows is not None:
-            win[:] = np.asarray(self._detached_windows, dtype=np.int32).reshape(nu, Lw)
-        else:
-            win[:] = 0
+        win = np.zeros((nu, Lw), np.int32)
+        if windows is not None:
+            win[:] = np.asarray(windows, dtype=np.int32).reshape(nu, Lw)
         self._windows = torch.from_numpy(win).to(self.device)
         ue, ie, giw, gib, guw, gub, igi, igu, w2, b2 = _init_tables(nu, ni, e, Lw, self.pad_idx)
         nb = 64 * ((ni + 63) // 64)                   # b2, zero-padded to whole 64-float blocks
@@ -230,5 +219,4 @@ class HGN(SeqPairwiseRecommender):
         """dense [len(users), num_items] scores, the padding item's column included (HGN.py:147-163,222-227)"""
         users = list(users)
         self._require_history(users)
-        Q, W2, b2 = self.predict_factors()
-        return _hip.score_matrix(Q, users, W2, b2).cpu().numpy()
+        return DeviceRecommender.predict(self, users)

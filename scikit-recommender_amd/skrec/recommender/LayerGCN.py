@@ -31,8 +31,8 @@ import torch.nn as nn
 from .. import _hip
 from ..io import PairwiseIterator
 from ..run_config import RunConfig
-from ..utils.py import EarlyStopping, ModelConfig
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from ..utils.py import ModelConfig
+from .base import AbstractRecommender, DenseAdam, DeviceRecommender, on_compute_stream
 from .LightGCN import DEVICE_ADJ_MIN_PAIRS, DeviceCSR, pad_columns, padded_width
 
 __all__ = ["LayerGCN", "LayerGCNConfig"]
@@ -72,10 +72,10 @@ def build_layergcn_adjacency(inter_coo, n_users, n_items):
     return (d * A * d).astype(np.float32)
 
 
-class LayerGCN(AbstractRecommender):
+class LayerGCN(DeviceRecommender):
     def __init__(self, run_config: RunConfig, model_config: Dict):
         self.config = LayerGCNConfig(**model_config)
-        super().__init__(run_config, self.config)
+        AbstractRecommender.__init__(self, run_config, self.config)
         cfg = self.config
         self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
         self.dp = padded_width(cfg.embed_dim)        # row width of the tables in HBM (zero-padded to a multiple of 64)
@@ -290,23 +290,13 @@ class LayerGCN(AbstractRecommender):
             else:
                 self.train_step(u.contiguous(), i.contiguous(), j.contiguous(), self.step_losses[k])
 
-    @on_compute_stream
-    def fit(self):
-        data_iter = PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True,
-                                     drop_last=False, sampler_mode=self.sampler_mode)
-        log = self.logger.info if self.dist.rank == 0 else (lambda *_: None)
-        log("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.pre_epoch_processing()
-            self.train_epoch(data_iter)
-            cur_result = self.evaluate()
-            log(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
-            if early_stopping(cur_result):
-                log("early stop")
-                break
-        log("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+    def _make_iterator(self):
+        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True,
+                                drop_last=False, sampler_mode=self.sampler_mode)
+
+    def _run_epoch(self, data_iter, epoch):
+        self.pre_epoch_processing()
+        self.train_epoch(data_iter)
 
     def _refresh_outputs(self):
         """one full-graph propagation per evaluation (the reference repeats it per batch, :255-262)"""

@@ -21,9 +21,9 @@ from .. import _hip
 from ..io import PairwiseIterator
 from ..run_config import RunConfig
 from ..utils.common import make_sure_dirs, normalize_adj_matrix
-from ..utils.py import EarlyStopping, ModelConfig
+from ..utils.py import ModelConfig
 from ..utils.torch import get_initializer
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from .base import AbstractRecommender, DenseAdam, DeviceRecommender, on_compute_stream
 
 __all__ = ["LightGCN", "LightGCNConfig", "DeviceCSR"]
 
@@ -317,10 +317,10 @@ def build_adjacency_device(users, items, num_users, num_items, adj_type, dev):
 DEVICE_ADJ_MIN_PAIRS = 1 << 21
 
 
-class LightGCN(AbstractRecommender):
+class LightGCN(DeviceRecommender):
     def __init__(self, run_config: RunConfig, model_config: Dict):
         self.config = LightGCNConfig(**model_config)
-        super().__init__(run_config, self.config)
+        AbstractRecommender.__init__(self, run_config, self.config)
         cfg = self.config
         self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
         self.dp = padded_width(cfg.embed_size)       # row width of the tables in HBM (zero-padded to a multiple of 64)
@@ -479,22 +479,9 @@ class LightGCN(AbstractRecommender):
             else:
                 self.train_step(u.contiguous(), i.contiguous(), j.contiguous(), self.step_losses[k])
 
-    @on_compute_stream
-    def fit(self):
-        data_iter = PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True,
-                                     drop_last=False, sampler_mode=self.sampler_mode)
-        log = self.logger.info if self.dist.rank == 0 else (lambda *_: None)
-        log("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.train_epoch(data_iter)
-            cur_result = self.evaluate()
-            log(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
-            if early_stopping(cur_result):
-                log("early stop")
-                break
-        log("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+    def _make_iterator(self):
+        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True,
+                                drop_last=False, sampler_mode=self.sampler_mode)
 
     def eval(self):
         """recompute and cache the final embeddings (_LightGCN.eval, LightGCN.py:109-111)"""

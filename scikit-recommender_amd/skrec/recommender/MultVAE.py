@@ -25,18 +25,17 @@ of the batch.  Device draws equal the reference's torch draws in law only.
 
 Limits: p_dims == [d] with d <= 64, q_dims None or [d], batch_size <= 1024, one GPU.
 """
-from typing import Dict, List
+from typing import List
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..run_config import RunConfig
-from ..utils.py import BatchIterator, EarlyStopping, ModelConfig
+from ..utils.py import BatchIterator, ModelConfig
 from ..utils.torch import get_initializer
-from ._graph import train_csr
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from ._graph import train_csr, upload_csr
+from .base import DenseAdam, DeviceRecommender, on_compute_stream
 
 __all__ = ["MultVAE", "MultVAEConfig"]
 
@@ -101,50 +100,29 @@ def _init_tables(num_items, d):
     return tuple(t.detach() for t in (lq.weight, lq.bias, lp.weight, lp.bias))
 
 
-class MultVAE(AbstractRecommender):
+class MultVAE(DeviceRecommender):
+    """limits: p_dims == [d] with d <= 64 and q_dims in (None, [d]) (NotImplementedError), batch_size <= 1024 (ValueError),
+    one GPU.  ``seed`` (``detached``; the run's seed otherwise): the key of the device draws"""
     config_class = MultVAEConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        """limits: p_dims == [d] with d <= 64 and q_dims in (None, [d]) (NotImplementedError), batch_size <= 1024
-        (ValueError), one GPU"""
-        self.config = MultVAEConfig(**model_config)
+    def _check_limits(self, world):
         check_limits(self.config)
-        super().__init__(run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        if self.dist.world > 1:
+        if world > 1:
             raise NotImplementedError("MultVAE runs on one GPU: there is no sharded engine for it")
-        self.device = _hip.require_gpu()
-        self.seed = int(getattr(run_config, "seed", 0) or 0)
-        self._build(*train_csr(self.dataset))
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, seed=0):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        check_limits(self.config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self.seed = int(seed)
-        self._build(csr[0], csr[1])
-        return self
+    def _train_inputs(self):
+        return train_csr(self.dataset)
 
-    def _build(self, rowptr, items):
+    def _build_args(self, run_config):
+        return {"seed": getattr(run_config, "seed", 0) or 0}
+
+    def _build(self, rowptr, items, seed=0):
         cfg = self.config
         d, nu, ni = check_limits(cfg), self.num_users, self.num_items
         self.d = d
-        if torch.is_tensor(rowptr):                                    # device arrays as they are (timing tools)
-            self._rowptr = rowptr.to(self.device, torch.int64).contiguous()
-            self._items = items.to(self.device, torch.int32).contiguous()
-            self._rowptr_host = self._rowptr.cpu().numpy()
-        else:
-            self._rowptr_host = np.ascontiguousarray(rowptr, dtype=np.int64)
-            self._rowptr = torch.from_numpy(self._rowptr_host).to(self.device)
-            self._items = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(self.device)
+        self.seed = int(seed)
+        self._rowptr, self._items = upload_csr(rowptr, items, self.device)
+        self._rowptr_host = self._rowptr.cpu().numpy() if torch.is_tensor(rowptr) else np.ascontiguousarray(rowptr, dtype=np.int64)
         assert self._rowptr_host.shape[0] == nu + 1
         Wq, bq, Wp, bp = _init_tables(ni, d)
         pad = lambda t: nn.functional.pad(t, (0, 64 - d))              # noqa: E731
@@ -229,30 +207,17 @@ class MultVAE(AbstractRecommender):
         self.step_losses.append(loss)
         return loss
 
-    @on_compute_stream
-    def fit(self):
+    def _make_iterator(self):
+        self.update_count = 0          # every fit() starts the annealing over (MultVAE.py:175)
         train_users = [u for u in range(self.num_users) if self._rowptr_host[u + 1] > self._rowptr_host[u]]
-        user_iter = BatchIterator(train_users, batch_size=self.config.batch_size, shuffle=True, drop_last=False)
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        self.update_count = 0
-        for epoch in range(self.config.epochs):
-            self.step_losses = []
-            for bat_users in user_iter:
-                self.train_step(bat_users)
-            cur_result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
-            if early_stopping(cur_result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+        return BatchIterator(train_users, batch_size=self.config.batch_size, shuffle=True, drop_last=False)
+
+    def _run_epoch(self, data_iter, epoch):
+        self.step_losses = []
+        for bat_users in data_iter:
+            self.train_step(bat_users)
 
     # ---- ranking ---------------------------------------------------------------------------------
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        return self.evaluator.evaluate(self, test_users)
-
     @on_compute_stream
     def predict_factors(self):
         """(Q [num_users, 64], Wp [num_items, 64], bp [num_items]): score = <Q[u], Wp[i]> + bp[i].  Q is computed by one
@@ -264,8 +229,3 @@ class MultVAE(AbstractRecommender):
                                                       self.num_items, _hip.ptr(self._Q), _hip.stream()))
             self._q_current = True
         return self._Q, self._wp, self._bp
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores (MultVAE.py:216-220)"""
-        Q, Wp, bp = self.predict_factors()
-        return _hip.score_matrix(Q, list(users), Wp, bp).cpu().numpy()

@@ -8,13 +8,10 @@ of squares of U[u], T, V[l], V[p], V[n], b[p], b[n], T once per batch, TransRec.
 training step is ``skr_transrec_step`` (two launches: the fused triple step, then T's gradient summed over the batch in
 a fixed order) and the Adam update of the flat [U | V | b | T] buffer (skrec/recommender/_seq.py).
 """
-from typing import Dict
-
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..run_config import RunConfig
 from ..utils.py import ModelConfig
 from ..utils.torch import get_initializer
 from ._seq import SeqPairwiseRecommender
@@ -56,11 +53,8 @@ def _init_tables(num_users, num_items, dim):
 class TransRec(SeqPairwiseRecommender):
     config_class = TransRecConfig
 
-    def __init__(self, run_config: RunConfig, model_config: Dict):
-        self.config = TransRecConfig(**model_config)
-        super().__init__(run_config, self.config)
-
-    def _build(self):
+    def _build(self, last_items=None):
+        super()._build(last_items)
         from .LightGCN import pad_columns, padded_width
         nu, ni, e = self.num_users, self.num_items, self.config.embed_size
         self.dp = d = padded_width(e)

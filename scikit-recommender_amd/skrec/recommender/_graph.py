@@ -1,8 +1,8 @@
 """Shared half of the graph recommenders on the bipartite train matrix (LightGCL, DENS, SelfCF, BM3): the normalised
 adjacency pair (A, A^T) built in HBM, the plain run of a SpMM plan, the layer-mean propagation, the ``W | b`` view of a
-linear block of the flat parameter buffer, and ``GraphRecommender`` -- the constructor and ``detached`` scaffold, the fit
-loop and the ranking half.  A model keeps its config, its limits, its draws, ``_build``, ``gradient_step``, ``train_step``
-and what is its own in ``propagate``.
+linear block of the flat parameter buffer, and ``GraphRecommender`` -- the epoch of steps and the propagate-then-rank
+half on ``DeviceRecommender`` (base.py).  A model keeps its config, its limits, its draws, ``_build``, ``gradient_step``,
+``train_step`` and what is its own in ``propagate``.
 """
 import ctypes
 
@@ -11,8 +11,7 @@ import torch
 
 from .. import _hip
 from ..io import InteractionIterator
-from ..utils.py import EarlyStopping
-from .base import AbstractRecommender, on_compute_stream
+from .base import DeviceRecommender, on_compute_stream
 from .LightGCN import DeviceCSR
 
 __all__ = ["GraphRecommender", "normalized_adjacency", "selfcf_adjacency", "train_csr", "upload_csr", "run_plan",
@@ -123,52 +122,13 @@ def linear_block(block, d):
 
 
 # ---- the recommender ---------------------------------------------------------------------------------
-class GraphRecommender(AbstractRecommender):
-    """Subclasses name their ``config_class`` and provide ``_check_limits(world)`` (raises for a config that does not run),
-    ``_build(rowptr, items, **build_kw)`` (whose keywords and defaults are ``detached``'s), ``gradient_step``,
-    ``train_step`` and ``propagate``.  Optional: ``_build_args(run_config)`` (the keywords a data set supplies),
-    ``_check_data(**build_kw)`` (limits that need them), ``_make_iterator`` / ``_batches`` (the fit loop's batches) and
-    ``_factors`` (what ``propagate`` left for the ranking)."""
+class GraphRecommender(DeviceRecommender):
+    """``DeviceRecommender`` on the train CSR: ``_build(rowptr, items, **build_kw)``; subclasses also provide
+    ``gradient_step``, ``train_step`` and ``propagate``.  Optional: ``_make_iterator`` / ``_batches`` (the fit loop's
+    batches) and ``_factors`` (what ``propagate`` left for the ranking)."""
 
-    def __init__(self, run_config, model_config, **build_kw):
-        """limits: see the model's ``check_limits``; raises before it touches the data set or the GPU"""
-        self.config = self.config_class(**model_config)
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        self._check_limits(self.dist.world)
-        AbstractRecommender.__init__(self, run_config, self.config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        build_kw = dict(self._build_args(run_config), **build_kw)
-        self._check_data(**build_kw)
-        self.device = _hip.require_gpu()
-        self.sampler_mode = getattr(run_config, "sampler_mode", None)
-        rowptr, items = train_csr(self.dataset)
-        self._build(rowptr, items, **build_kw)
-
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, csr, **build_kw):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
-        ``csr``: (rowptr [num_users + 1], items) of the binary train matrix, items ascending inside a row (numpy arrays or
-        device tensors); ``build_kw``: the keywords of the model's ``_build``"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        self._check_limits(1)
-        self._check_data(**build_kw)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._build(csr[0], csr[1], **build_kw)
-        return self
-
-    def _build_args(self, run_config):
-        return {}
-
-    def _check_data(self, **build_kw):
-        pass
-
-    def _ids(self, t):
-        if torch.is_tensor(t):
-            return t.to(self.device, torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
+    def _train_inputs(self):
+        return train_csr(self.dataset)
 
     def _flags(self, t, shape):
         if not torch.is_tensor(t):
@@ -176,10 +136,6 @@ class GraphRecommender(AbstractRecommender):
         t = t.to(self.device, torch.uint8).contiguous()
         assert tuple(t.shape) == tuple(shape), f"keep flags of shape {tuple(t.shape)}, expected {tuple(shape)}"
         return t
-
-    def _grow_work(self, need):
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
 
     # ---- training --------------------------------------------------------------------------------
     def _make_iterator(self):
@@ -189,22 +145,10 @@ class GraphRecommender(AbstractRecommender):
         """the argument tuples of ``train_step`` for one epoch"""
         return data_iter
 
-    @on_compute_stream
-    def fit(self):
-        data_iter = self._make_iterator()
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.step_losses = []
-            for batch in self._batches(data_iter, epoch):
-                self.train_step(*batch)
-            result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
-            if early_stopping(result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
+    def _run_epoch(self, data_iter, epoch):
+        self.step_losses = []
+        for batch in self._batches(data_iter, epoch):
+            self.train_step(*batch)
 
     # ---- ranking ---------------------------------------------------------------------------------
     def _factors(self):
@@ -225,8 +169,3 @@ class GraphRecommender(AbstractRecommender):
         if not getattr(self, "_pooled_current", False):
             self.propagate()
         return self._factors()
-
-    def predict(self, users) -> np.ndarray:
-        """dense [len(users), num_items] scores"""
-        uf, vf, bias = self.predict_factors()
-        return _hip.score_matrix(uf, list(users), vf, bias).cpu().numpy()

@@ -16,53 +16,39 @@ import torch
 
 from .. import _hip
 from ..io import SequentialPairwiseIterator
-from ..utils.py import EarlyStopping
-from .base import AbstractRecommender, DenseAdam, on_compute_stream
+from .base import DenseAdam, DeviceRecommender, on_compute_stream
 
 __all__ = ["SeqPairwiseRecommender"]
 
 
-class SeqPairwiseRecommender(AbstractRecommender):
-    """Subclasses name their ``config_class`` and provide ``_build`` (sets ``self.dp``, hands the flat parameter buffer
-    to ``_setup`` and sets ``_step_launch``, one batch of the step kernel on cached addresses), ``_block_id_parts`` (the
-    64-float blocks of the flat buffer a batch touches: int32 tensors [n] or [n, w], negative entries are skipped) and
-    ``_score_launch`` (skr_seq_scores).  ``_make_iterator`` names the iterator's shape, ``_weight_decay`` the optimiser's."""
+class SeqPairwiseRecommender(DeviceRecommender):
+    """Subclasses name their ``config_class`` and provide ``_build`` (calls this class's first, sets ``self.dp``, hands the
+    flat parameter buffer to ``_setup`` and sets ``_step_launch``, one batch of the step kernel on cached addresses),
+    ``_block_id_parts`` (the 64-float blocks of the flat buffer a batch touches: int32 tensors [n] or [n, w], negative
+    entries are skipped) and ``_score_launch`` (skr_seq_scores).  ``_make_iterator`` names the iterator's shape,
+    ``_weight_decay`` the optimiser's."""
 
     _weight_decay = 0.0
 
-    def __init__(self, run_config, config):
-        super().__init__(run_config, config)
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        from ..parallel import init_from_env
-        self.dist = init_from_env()
-        if self.dist.world > 1:
+    def _check_limits(self, world):
+        if world > 1:
             raise NotImplementedError(f"{type(self).__name__} runs on one GPU: there is no sharded engine for it")
-        self.device = _hip.require_gpu()
+
+    def _build_args(self, run_config):
         self.user_pos_dict = self.dataset.train_data.to_user_dict_by_time()
         last = np.full(self.num_users, -1, np.int32)
         for u, items in self.user_pos_dict.items():
             if len(items):
                 last[int(u)] = int(items[-1])
-        self._set_last_items(last)
-        self.step_losses = None  # device [n_steps, 2]: (bpr sum, l2) per step of the last epoch
-        self._build()
+        return {"last_items": last}
 
-    @classmethod
-    def detached(cls, num_users, num_items, model_config, last_items=None):
-        """the model's parameters, training step and scoring without a data set, logger or evaluator (timing tools);
-        ``last_items``: int32 [num_users], every user's last training item (default: item 0)"""
-        self = cls.__new__(cls)
-        self.config = cls.config_class(**model_config)
-        self.num_users, self.num_items = int(num_users), int(num_items)
-        self.device = _hip.require_gpu()
-        self._set_last_items(np.zeros(self.num_users, np.int32) if last_items is None else last_items)
-        self.step_losses = None
-        self._build()
-        return self
-
-    def _set_last_items(self, last):
+    def _build(self, last_items=None):
+        """``last_items``: int32 [num_users], every user's last training item, -1 without one (``detached``'s default:
+        item 0)"""
+        last = np.zeros(self.num_users, np.int32) if last_items is None else last_items
         self._last_host = np.ascontiguousarray(last, dtype=np.int32)
         self._last = torch.from_numpy(self._last_host).to(self.device)
+        self.step_losses = None  # device [n_steps, 2]: (bpr sum, l2) per step of the last epoch
 
     def _setup(self, flat):
         """``flat``: the model's parameters, one contiguous device buffer"""
@@ -137,21 +123,6 @@ class SeqPairwiseRecommender(AbstractRecommender):
     def _make_iterator(self):
         return SequentialPairwiseIterator(self.dataset.train_data, num_previous=1, num_next=1,
                                           batch_size=self.config.batch_size, shuffle=True, drop_last=False)
-
-    @on_compute_stream
-    def fit(self):
-        data_iter = self._make_iterator()
-        self.logger.info("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
-        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
-        for epoch in range(self.config.epochs):
-            self.train_epoch(data_iter)
-            cur_result = self.evaluate()
-            self.logger.info(f"epoch {epoch}:".ljust(12) + f"\t{cur_result.values_str}")
-            if early_stopping(cur_result):
-                self.logger.info("early stop")
-                break
-        self.logger.info("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
-        return early_stopping.best_result
 
     # ---- ranking ---------------------------------------------------------------------------------
     def _require_history(self, users):

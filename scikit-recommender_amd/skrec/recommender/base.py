@@ -1,5 +1,7 @@
 """``AbstractRecommender`` (reference: skrec/recommender/base.py:20-74): dataset, logger, evaluator and
-the activity groups are built here; subclasses provide ``fit`` / ``evaluate`` / ``predict``."""
+the activity groups are built here; subclasses provide ``fit`` / ``evaluate`` / ``predict``.  ``DeviceRecommender``: what
+the models on the GPU share beyond that -- the order of the constructor's checks, ``detached``, the fit loop and the
+ranking half on ``predict_factors``."""
 import os
 import platform
 import time
@@ -9,10 +11,10 @@ import numpy as np
 
 from ..io import Logger, RSDataset, group_users_by_interactions
 from ..run_config import RunConfig
-from ..utils.py import Config, MetricReport, RankingEvaluator, slugify
+from ..utils.py import Config, EarlyStopping, MetricReport, RankingEvaluator, slugify
 from ..version import __version__
 
-__all__ = ["AbstractRecommender", "DenseAdam", "on_compute_stream"]
+__all__ = ["AbstractRecommender", "DeviceRecommender", "DenseAdam", "on_compute_stream"]
 
 
 def on_compute_stream(fit):
@@ -83,6 +85,99 @@ class AbstractRecommender(object):
 
     def predict(self, users: Union[List[int], np.ndarray]) -> np.ndarray:
         raise NotImplementedError
+
+
+class DeviceRecommender(AbstractRecommender):
+    """Subclasses name their ``config_class`` and provide ``_check_limits(world)`` (raises for a config that does not run),
+    ``_build(*inputs, **build_kw)`` (whose keywords and defaults are ``detached``'s), ``train_step`` or ``train_epoch``,
+    ``_make_iterator`` and ``predict_factors``.  Optional: ``_train_inputs()`` (what a data set supplies positionally to
+    ``_build``), ``_build_args(run_config)`` (the keywords it supplies), ``_check_data(**build_kw)`` (limits that need
+    them) and ``_run_epoch`` (one epoch of the fit loop).  LightGCN and LayerGCN, whose constructors choose between one GPU
+    and a sharded engine, keep those and take the fit loop only."""
+
+    def __init__(self, run_config, model_config, **build_kw):
+        """limits: see the model's ``_check_limits``; raises before it touches the data set or the GPU"""
+        from .. import _hip
+        from ..parallel import init_from_env
+        self.config = self.config_class(**model_config)
+        self.dist = init_from_env()
+        self._check_limits(self.dist.world)
+        AbstractRecommender.__init__(self, run_config, self.config)
+        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
+        build_kw = dict(self._build_args(run_config), **build_kw)
+        self._check_data(**build_kw)
+        self.device = _hip.require_gpu()
+        self.sampler_mode = getattr(run_config, "sampler_mode", None)
+        self._build(*self._train_inputs(), **build_kw)
+
+    @classmethod
+    def detached(cls, num_users, num_items, model_config, *inputs, **build_kw):
+        """the model's parameters, training step and scoring without a data set, logger or evaluator (tests, timing tools);
+        ``inputs``: the positional arguments of the model's ``_build``, or one tuple of them -- the binary train matrix is
+        handed over as ``(rowptr [num_users + 1], items)``, items ascending inside a row (numpy arrays or device tensors);
+        ``build_kw``: the keywords of ``_build``"""
+        from .. import _hip
+        self = cls.__new__(cls)
+        self.config = cls.config_class(**model_config)
+        self._check_limits(1)
+        self._check_data(**build_kw)
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.device = _hip.require_gpu()
+        if len(inputs) == 1 and isinstance(inputs[0], tuple):
+            inputs = inputs[0]
+        self._build(*inputs, **build_kw)
+        return self
+
+    def _train_inputs(self):
+        return ()
+
+    def _build_args(self, run_config):
+        return {}
+
+    def _check_data(self, **build_kw):
+        pass
+
+    def _ids(self, t):
+        import torch
+        if torch.is_tensor(t):
+            return t.to(self.device, torch.int32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
+
+    def _grow_work(self, need):
+        import torch
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    # ---- training --------------------------------------------------------------------------------
+    def _run_epoch(self, data_iter, epoch):
+        self.train_epoch(data_iter)
+
+    @on_compute_stream
+    def fit(self):
+        data_iter = self._make_iterator()
+        log = self.logger.info if self.dist.rank == 0 else (lambda *_: None)
+        log("metrics:".ljust(12) + f"\t{self.evaluator.metrics_str}")
+        early_stopping = EarlyStopping(metric="NDCG@10", patience=self.config.early_stop)
+        for epoch in range(self.config.epochs):
+            self._run_epoch(data_iter, epoch)
+            result = self.evaluate()
+            log(f"epoch {epoch}:".ljust(12) + f"\t{result.values_str}")
+            if early_stopping(result):
+                log("early stop")
+                break
+        log("best:".ljust(12) + f"\t{early_stopping.best_result.values_str}")
+        return early_stopping.best_result
+
+    # ---- ranking ---------------------------------------------------------------------------------
+    @on_compute_stream
+    def evaluate(self, test_users=None):
+        return self.evaluator.evaluate(self, test_users)
+
+    def predict(self, users) -> np.ndarray:
+        """dense [len(users), num_items] scores"""
+        from .. import _hip
+        uf, vf, bias = self.predict_factors()
+        return _hip.score_matrix(uf, list(users), vf, bias).cpu().numpy()
 
 
 class DenseAdam(object):
