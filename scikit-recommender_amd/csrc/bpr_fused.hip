@@ -66,8 +66,12 @@ struct FusedWork {
 // and the barrier and the second id load come on top.
 //
 // The load phase.  A wavefront's time is a chain of memory round trips, and the launch lasts as long as its slowest
-// wavefront, so the phase is written to make exactly three of them, whatever the rows' sources:
-//   1. the arguments the first loads need (the id and word columns, n);
+// wavefront, so the phase is written to make exactly two of them, whatever the rows' sources (three on a stack that does not
+// preload kernel arguments):
+//   1. the arguments the first loads need (the id and word columns, n) cost no trip: they are the first 14 dwords of the
+//      parameter list, which the Makefile has this file's kernels receive in SGPRs at wavefront launch
+//      (-amdgpu-kernarg-preload-count; firmware that does not preload runs the compiler's prologue, which loads the
+//      same registers: the round trip of before).  Keep them first when the list changes;
 //   2. the first interaction's ids and words (two loads: one row per group of four lanes) and the per-step tables, with
 //      every other argument fetched beside them in one round of scalar loads;
 //   3. all twenty row loads (p, m, v and the gradient word of the five rows), issued back to back with no wait between
@@ -81,10 +85,10 @@ struct FusedWork {
 // trips for the rows, and four for the arguments and tables in front of them.  The values that reach chain_advance are
 // the same: the kernel stays bit-identical.
 __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
-    const float* __restrict__ P, const float* __restrict__ M, const float* __restrict__ V, int64_t n_par, FusedWork w,
     const int32_t* __restrict__ u_ids, const int32_t* __restrict__ i_ids, const int32_t* __restrict__ j_ids,
-    const int32_t* __restrict__ meta, int n, int64_t ublk0, int64_t iblk0, int64_t bblk0, int s_now, AdamBlockArgs a,
-    float reg, float* __restrict__ loss, int loss_slots, int dbg, const float* __restrict__ pre) {
+    const int32_t* __restrict__ meta, int n, int s_now, int dbg, int loss_slots, const float* __restrict__ P,
+    const float* __restrict__ M, const float* __restrict__ V, int64_t n_par, FusedWork w, int64_t ublk0, int64_t iblk0,
+    int64_t bblk0, AdamBlockArgs a, float reg, float* __restrict__ loss, const float* __restrict__ pre) {
     __shared__ float s_loss[BPR_WAVES], s_l2[BPR_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // round 1: the ids and the words in two loads -- lane L works for row L >> 2 (lanes 20 .. 63: row 4 again) and fetches
@@ -193,10 +197,13 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
                     const int64_t slot = mt[r] & ((1 << FUSED_SLOT_BITS) - 1);
                     const int n0 = (mt[r] >> FUSED_SLOT_BITS) & 7;
                     const int64_t e = (((n0 + 1) & 1) * w.cap + slot) * 64 + lane;
-                    w.wp[e] = row[r].p;
-                    w.wm[e] = row[r].m;
-                    w.wv[e] = row[r].v;
-                    w.g[(((n0 + 1) % 3) * w.cap + slot) * 64 + lane] = 0.0f;
+                    // write-through (relaxed stores of agent scope: the plain vector store with sc1): nothing in this launch
+                    // reads them, and the lines drain while the wavefront works, not at the kernel's end
+                    __hip_atomic_store(&w.wp[e], row[r].p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&w.wm[e], row[r].m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&w.wv[e], row[r].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&w.g[(((n0 + 1) % 3) * w.cap + slot) * 64 + lane], 0.0f, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
         }
@@ -232,6 +239,9 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
         acc_loss += l;
         acc_l2 += 0.5f * sq;
     }
+    // the loss words: one pair of adds per WORKGROUP.  The SKR_LOSS_SLOTS pairs of a step lie in four 128-byte lines, and what
+    // the adds cost follows their number per line: 1.5 us of the launch for these 512 (SKR_FUSED_DBG=8 takes them out), 9 us
+    // for one pair per wavefront issued ahead of the gradient traffic -- built, measured, removed
     if (lane == 0) {
         s_loss[wv] = acc_loss;
         s_l2[wv] = acc_l2;
@@ -254,13 +264,13 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
 // first naming, into the pre buffer ([3][cap][64]: p, m, v).  These zero-gradient updates depend on nothing the block
 // itself does; the step launch that first names such a row then finds it current and spends nothing on catching up
 // (16 updates on average at k = 32, on the critical path of the step before).  The same fused_advance call the step
-// would have made: the same bits.
-__global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const float* __restrict__ P, const float* __restrict__ M,
-                                                            const float* __restrict__ V, int64_t n_par, float* __restrict__ pre,
-                                                            int64_t cap, const int32_t* __restrict__ slot_blk,
-                                                            const int32_t* __restrict__ slot_fin, const int32_t* __restrict__ n_slots,
-                                                            AdamBlockArgs a, const int32_t* __restrict__ tag_prev,
-                                                            int32_t tag_prev_value) {
+// would have made: the same bits.  (Parameter order, here and in bpr_fused_end_kernel: what the first loads need -- the slot
+// count, the slot tables, the tags -- inside the first 14 dwords, which arrive in SGPRs at wavefront launch.)
+__global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const int32_t* __restrict__ n_slots, const int32_t* __restrict__ slot_blk,
+                                                            const int32_t* __restrict__ slot_fin, const int32_t* __restrict__ tag_prev,
+                                                            int32_t tag_prev_value, int64_t n_par, int64_t cap,
+                                                            const float* __restrict__ P, const float* __restrict__ M,
+                                                            const float* __restrict__ V, float* __restrict__ pre, AdamBlockArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t slot = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (slot >= *n_slots) return;
@@ -283,11 +293,10 @@ __global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const float* __restr
 // updates up to the later of the two rows' last namings; from there to the block's end two rows that both passed the
 // ordinary test advance together on the packed pair form (adam_pair_ordinary: the cold pass's, the same operations per
 // component).  A pair with a row that failed the test or that the `which` filter drops, and a lone last slot, run one by one.
-__global__ __launch_bounds__(256) void bpr_fused_end_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
-                                                            int64_t n_par, FusedWork w, const int32_t* __restrict__ slot_blk,
-                                                            const int32_t* __restrict__ slot_fin,
-                                                            const int32_t* __restrict__ n_slots, AdamBlockArgs a,
-                                                            const int32_t* __restrict__ tag_next, int32_t tag_next_value, int which) {
+__global__ __launch_bounds__(256) void bpr_fused_end_kernel(const int32_t* __restrict__ n_slots, const int32_t* __restrict__ slot_blk,
+                                                            const int32_t* __restrict__ slot_fin, const int32_t* __restrict__ tag_next,
+                                                            int32_t tag_next_value, int which, int64_t n_par, float* __restrict__ P,
+                                                            float* __restrict__ M, float* __restrict__ V, FusedWork w, AdamBlockArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t slot0 = 2 * (static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
     const int64_t n = *n_slots;
@@ -492,9 +501,9 @@ int skr_bpr_fused_step2(const float* d_p, const float* d_m, const float* d_v, in
     static const int dbg = [] { const char* e = getenv("SKR_FUSED_DBG"); return e ? atoi(e) : 0; }();
     int blocks = (n_batch + BPR_WAVES - 1) / BPR_WAVES;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(bpr_fused_step_kernel, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_p, d_m, d_v, n,
-                       fused_work(d_work, cap), d_u, d_i, d_j, d_meta, n_batch, user_block0, item_block0, bias_block0, s, a, reg,
-                       d_loss64, SKR_LOSS_SLOTS, dbg, d_pre);
+    hipLaunchKernelGGL(bpr_fused_step_kernel, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_u, d_i, d_j, d_meta,
+                       n_batch, s, dbg, SKR_LOSS_SLOTS, d_p, d_m, d_v, n, fused_work(d_work, cap), user_block0, item_block0,
+                       bias_block0, a, reg, d_loss64, d_pre);
     SKR_LAUNCH_CHECK();
     return SKR_OK;
 }
@@ -549,8 +558,8 @@ int skr_bpr_fused_pre(const float* d_p, const float* d_m, const float* d_v, int6
     adam_block_scalars(a, lr, beta1, beta2, step_t0, k, false);
     adam_block_thresholds(a, lr, beta1, beta2, eps, k);
     a.stats = fused_stats_buffer();
-    hipLaunchKernelGGL(bpr_fused_pre_kernel, dim3(static_cast<unsigned>((cap + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_p, d_m,
-                       d_v, n, d_pre, cap, d_slot_block, d_slot_fin, d_n_slots, a, d_tag_prev, tag_prev_value);
+    hipLaunchKernelGGL(bpr_fused_pre_kernel, dim3(static_cast<unsigned>((cap + 3) / 4)), dim3(256), 0, skr::as_stream(stream), d_n_slots,
+                       d_slot_block, d_slot_fin, d_tag_prev, tag_prev_value, n, cap, d_p, d_m, d_v, d_pre, a);
     SKR_LAUNCH_CHECK();
     return SKR_OK;
 }
@@ -563,8 +572,8 @@ int skr_bpr_fused_end(float* d_p, float* d_m, float* d_v, int64_t n, float* d_wo
     SKR_REQUIRE(step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "skr_bpr_fused_end: need 1 <= k <= %d", AB_KMAX);
     SKR_REQUIRE(which >= 0 && which <= 2 && (which == 0 || d_tag_next), "skr_bpr_fused_end: which must be 0, or 1 / 2 with the next block's tags");
     const AdamBlockArgs& a = fused_block_args(lr, beta1, beta2, eps, step_t0, k);
-    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>((cap + 7) / 8)), dim3(256), 0, skr::as_stream(stream), d_p,
-                       d_m, d_v, n, fused_work(d_work, cap), d_slot_block, d_slot_fin, d_n_slots, a, d_tag_next, tag_next_value, which);
+    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>((cap + 7) / 8)), dim3(256), 0, skr::as_stream(stream), d_n_slots,
+                       d_slot_block, d_slot_fin, d_tag_next, tag_next_value, which, n, d_p, d_m, d_v, fused_work(d_work, cap), a);
     SKR_LAUNCH_CHECK();
     return SKR_OK;
 }
