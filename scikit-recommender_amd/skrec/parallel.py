@@ -26,7 +26,7 @@ import torch
 
 from . import _hip
 from .recommender.base import DenseAdam
-from .recommender.LightGCN import DeviceCSR
+from .recommender._sparse import DeviceCSR
 
 __all__ = ["DistContext", "ShardedBPRMF", "ShardedLightGCN", "ShardedLayerGCN", "init_from_env", "sharded_evaluate",
            "unique_padded_rows"]
@@ -114,25 +114,123 @@ def unique_padded_rows(ids):
     return torch.where(srt == big, torch.full_like(srt, -1), srt).int().contiguous()
 
 
-def _csr_from_device_coo(rows, cols, vals, n_rows, n_cols):
-    """rectangular CSR in HBM from unique (row, col) pairs"""
-    order = torch.argsort(rows * n_cols + cols)
-    csr = DeviceCSR.__new__(DeviceCSR)
-    csr.shape = (int(n_rows), int(n_cols))
-    csr.nnz = int(rows.numel())
-    csr.rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
-    csr.rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
-    csr.col = cols[order].int().contiguous()
-    csr.val = vals[order].float().contiguous()
-    return csr
+class ShardedGraphEngine(object):
+    """What the two full-graph engines share: rows laid out [this rank's users ; all items] in 64-float rows, the
+    parameters with their dense Adam, the marks of a global batch's rows, the compact exchange of a batch's item rows, the
+    gathers of a full user table.  A subclass names its output table in ``output`` and provides ``propagate`` and
+    ``train_step``."""
+
+    output = None      # "final" / "out": the propagation's result; whole only after a propagate() without last_rows
+
+    def _alloc_parameters(self, user_rows, item_rows, lr):
+        """ego = [this rank's user rows ; item rows] in HBM, its dense Adam, the gradient view and the (bpr, l2) pair"""
+        self.ego = torch.cat([user_rows, item_rows], dim=0).to(self.device).contiguous()   # [U_loc + I, 64]
+        n = self.n_local + self.num_items
+        assert self.ego.shape == (n, 64)
+        self.optimizer = DenseAdam(self.ego.view(-1), lr=lr)
+        self._g_ego = self.optimizer.grad.view(n, 64)
+        self.loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    # ---- helpers ---------------------------------------------------------------------------------
+    def _axpy(self, a, x, y):
+        _hip.check(_hip.lib().skr_axpy(float(a), _hip.ptr(x), _hip.ptr(y), x.numel(), _hip.stream()))
+
+    @property
+    def user_rows(self):
+        return self.ego[:self.n_local]
+
+    @property
+    def item_rows(self):
+        return self.ego[self.n_local:]
+
+    def _whole_output(self):
+        """the output table for readers of ALL its rows (evaluation, tests): after a training step only the batch's rows are
+        valid (the last layer is computed for those only, and on several ranks the other item rows may even differ between
+        the replicas); an unmasked ``propagate()`` makes it whole again"""
+        if not getattr(self, f"_{self.output}_whole", False):
+            raise ValueError(f"{type(self).__name__}.{self.output} holds only a batch's rows after train_step(): "
+                             f"call propagate() first")
+        return getattr(self, self.output)
+
+    def gather_user_rows(self, local_rows):
+        """[U, 64] on every rank from each rank's [U_local, 64] block"""
+        full = torch.zeros((self.num_users, 64), dtype=torch.float32, device=self.device)
+        full[torch.from_numpy(self.mine).to(self.device)] = local_rows
+        self.ctx.all_reduce(full)
+        return full
+
+    def gather_user_table(self):
+        """full [U, 64] user table on every rank (tests / checkpoints)"""
+        return self.gather_user_rows(self.ego[:self.n_local])
+
+    # ---- a GLOBAL batch's rows -------------------------------------------------------------------
+    def _step_masks(self, users, pos, neg, grad_rows):
+        """the head of a step: the marks of the batch's rows (``_batch_rows``), with ``grad_rows`` zero outside them; None
+        under SKR_LIGHTGCN_DENSE=1, which computes everything"""
+        if os.environ.get("SKR_LIGHTGCN_DENSE") == "1":
+            grad_rows.zero_()
+            self._mask_u = None
+            return None
+        return self._batch_rows(users, pos, neg, grad_rows=grad_rows)
+
+    def _batch_rows(self, users, pos, neg, grad_rows=None):
+        """(uint8 [n_local], uint8 [I]) for a GLOBAL batch (global user ids): the rows it touches -- this rank's users,
+        EVERY rank's items (the item rows are replicated and summed over the ranks, so each rank needs the same set).
+        Also keeps the batch's item ids (pos ++ neg, identical on every rank) for the compact exchanges."""
+        L, st, world, rank = _hip.lib(), _hip.stream(), self.ctx.world, self.ctx.rank
+        if getattr(self, "_mask_u", None) is None:
+            self._mask_u = torch.zeros(self.n_local, dtype=torch.uint8, device=self.device)
+            self._mask_i = torch.zeros(self.num_items, dtype=torch.uint8, device=self.device)
+            if grad_rows is not None:
+                grad_rows.zero_()
+        elif grad_rows is not None:
+            # the buffer the BPR kernel scatters dL/d(output rows) into is zero outside the PREVIOUS batch's rows: those rows
+            # are cleared, and their marks with them, instead of filling the whole [n_local + I, 64] buffer
+            nl = self.n_local
+            _hip.check(L.skr_clear_marked_rows(_hip.ptr(self._mask_u), nl, 1, _hip.ptr(grad_rows[:nl]), 64, st))
+            _hip.check(L.skr_clear_marked_rows(_hip.ptr(self._mask_i), self.num_items, 1, _hip.ptr(grad_rows[nl:]), 64, st))
+        else:
+            self._mask_u.zero_()
+            self._mask_i.zero_()
+        if world > 1:   # local rows of the users this rank owns; the others become -1 (skipped)
+            ul = torch.where((users % world) == rank, torch.div(users, world, rounding_mode="floor"), torch.full_like(users, -1))
+        else:
+            ul = users
+        _hip.check(L.skr_mark_ids(_hip.ptr(ul.contiguous()), ul.numel(), 0, _hip.ptr(self._mask_u), st))
+        self._batch_item_ids = torch.cat([pos, neg]).contiguous()
+        _hip.check(L.skr_mark_ids(_hip.ptr(self._batch_item_ids), self._batch_item_ids.numel(), 0, _hip.ptr(self._mask_i), st))
+        return self._mask_u, self._mask_i
+
+    def _rows_exchange_begin(self, block, ids):
+        """Sum the rows `ids` of a replicated [I, 64] block over the ranks, compactly: the rows are gathered into a
+        [len(ids), 64] buffer, the ranks' buffers all-gathered (started here, on the collective's stream) ..."""
+        import torch.distributed as dist
+        n, world = ids.numel(), self.ctx.world
+        if getattr(self, "_xrows", None) is None or self._xrows.shape[0] != n:
+            self._xrows = torch.empty((n, 64), dtype=torch.float32, device=self.device)
+            self._xall = torch.empty((world, n, 64), dtype=torch.float32, device=self.device)
+        _hip.check(_hip.lib().skr_gather_rows(_hip.ptr(block), _hip.ptr(ids), n, 64, _hip.ptr(self._xrows), _hip.stream()))
+        if dist.get_backend() == "nccl":
+            return dist.all_gather_into_tensor(self._xall, self._xrows, async_op=True)
+        return dist.all_gather([self._xall[r] for r in range(world)], self._xrows, async_op=True)
+
+    def _rows_exchange_end(self, work, ids, block):
+        """... and added up in RANK ORDER by every rank itself (skr_sum_blocks): the replicas end with identical bits
+        whatever order the collective library reduces in; the sums go back into the block's rows."""
+        work.wait()
+        L, st, n = _hip.lib(), _hip.stream(), ids.numel()
+        _hip.check(L.skr_sum_blocks(_hip.ptr(self._xall), self.ctx.world, n * 64, _hip.ptr(self._xrows), st))
+        _hip.check(L.skr_scatter_rows(_hip.ptr(self._xrows), _hip.ptr(ids), n, 64, _hip.ptr(block), st))
 
 
-class ShardedLightGCN(object):
+class ShardedLightGCN(ShardedGraphEngine):
     """LightGCN step / propagation for one rank of a user-sharded job.
 
     adj        scipy sparse [(U+I), (U+I)], the reference's normalised adjacency (symmetric types only)
     user0/item0  full initial tables (numpy or CPU tensors), identical on every rank
     """
+
+    output = "final"
 
     def __init__(self, ctx, adj, user0, item0, n_layers, lr, reg, batch_size_cfg, device=None):
         self.ctx = ctx
@@ -142,7 +240,7 @@ class ShardedLightGCN(object):
         self.num_users, self.num_items = user0.shape[0], item0.shape[0]
         assert user0.shape[1] == 64 and item0.shape[1] == 64, "the MI355X kernels are specialised for 64 dims"
         self.n_layers, self.reg, self.batch_size_cfg = int(n_layers), float(reg), int(batch_size_cfg)
-        U, I = self.num_users, self.num_items
+        U = self.num_users
         adj = sp.csr_matrix(adj).astype(np.float32)
         block = adj[:U, U:]
         if abs(block - adj[U:, :U].T).max() > 1e-7 or abs(adj[:U, :U]).sum() != 0 or abs(adj[U:, U:]).sum() != 0:
@@ -152,16 +250,17 @@ class ShardedLightGCN(object):
         a_ui = sp.csr_matrix(block[self.mine])                     # [U_loc, I]
         self.a_ui = DeviceCSR(a_ui, self.device)
         self.a_iu = DeviceCSR(sp.csr_matrix(a_ui.T), self.device)    # [I, U_loc]
-        nl = self.n_local
-        self.ego = torch.cat([user0[self.mine], item0], dim=0).to(self.device).contiguous()   # [U_loc + I, 64]
-        self.optimizer = DenseAdam(self.ego.view(-1), lr=lr)
-        self._g_ego = self.optimizer.grad.view(nl + I, 64)
+        self._alloc_parameters(user0[self.mine], item0, lr)
+        self._alloc_work()
+
+    def _alloc_work(self):
+        """the layer mean, its gradient and the ping-pong tables of both passes, user and item halves apart"""
+        nl, I = self.n_local, self.num_items
         z = lambda n: torch.zeros((n, 64), dtype=torch.float32, device=self.device)  # noqa: E731
         self.final = z(nl + I)
         self._xu, self._xi = [z(nl), z(nl)], [z(I), z(I)]
         self._g_final = z(nl + I)
         self._gu, self._gi = [z(nl), z(nl)], [z(I), z(I)]
-        self.loss = torch.zeros(2, dtype=torch.float32, device=self.device)
 
     @classmethod
     def from_device_edges(cls, ctx, users, items, num_users, num_items, user0, item0, n_layers, lr, reg, batch_size_cfg):
@@ -184,31 +283,11 @@ class ShardedLightGCN(object):
         sel = (u % ctx.world) == ctx.rank
         ul, il = torch.div(u[sel], ctx.world, rounding_mode="floor"), i[sel]
         vals = du[u[sel]] * di[il]
-        self.a_ui = _csr_from_device_coo(ul, il, vals, nl, num_items)
-        self.a_iu = _csr_from_device_coo(il, ul, vals, num_items, nl)
-        self.ego = torch.cat([user0.to(dev), item0.to(dev)], dim=0).contiguous()
-        assert self.ego.shape == (nl + num_items, 64)
-        self.optimizer = DenseAdam(self.ego.view(-1), lr=lr)
-        self._g_ego = self.optimizer.grad.view(nl + num_items, 64)
-        z = lambda n: torch.zeros((n, 64), dtype=torch.float32, device=dev)  # noqa: E731
-        self.final = z(nl + num_items)
-        self._xu, self._xi = [z(nl), z(nl)], [z(num_items), z(num_items)]
-        self._g_final = z(nl + num_items)
-        self._gu, self._gi = [z(nl), z(nl)], [z(num_items), z(num_items)]
-        self.loss = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.a_ui = DeviceCSR.from_coo(ul, il, vals, nl, num_items)
+        self.a_iu = DeviceCSR.from_coo(il, ul, vals, num_items, nl)
+        self._alloc_parameters(user0.to(dev), item0.to(dev), lr)
+        self._alloc_work()
         return self
-
-    # ---- helpers ---------------------------------------------------------------------------------
-    def _axpy(self, a, x, y):
-        _hip.check(_hip.lib().skr_axpy(float(a), _hip.ptr(x), _hip.ptr(y), x.numel(), _hip.stream()))
-
-    @property
-    def user_rows(self):
-        return self.ego[:self.n_local]
-
-    @property
-    def item_rows(self):
-        return self.ego[self.n_local:]
 
     # ---- forward ---------------------------------------------------------------------------------
     def propagate(self, last_rows=None):
@@ -273,62 +352,9 @@ class ShardedLightGCN(object):
         self.a_iu.spmm(xu, ni, row_mask=mi)
         return ni, mi
 
-    def _batch_rows(self, users, pos, neg, grad_rows=None):
-        """(uint8 [n_local], uint8 [I]) for a GLOBAL batch (global user ids): the rows it touches -- this rank's users,
-        EVERY rank's items (the item rows are replicated and summed over the ranks, so each rank needs the same set).
-        Also keeps the batch's item ids (pos ++ neg, identical on every rank) for the compact exchanges."""
-        L, st, world, rank = _hip.lib(), _hip.stream(), self.ctx.world, self.ctx.rank
-        if getattr(self, "_mask_u", None) is None:
-            self._mask_u = torch.zeros(self.n_local, dtype=torch.uint8, device=self.device)
-            self._mask_i = torch.zeros(self.num_items, dtype=torch.uint8, device=self.device)
-            if grad_rows is not None:
-                grad_rows.zero_()
-        elif grad_rows is not None:
-            # the buffer the BPR kernel scatters dL/d(output rows) into is zero outside the PREVIOUS batch's rows: those rows
-            # are cleared, and their marks with them, instead of filling the whole [n_local + I, 64] buffer
-            nl = self.n_local
-            _hip.check(L.skr_clear_marked_rows(_hip.ptr(self._mask_u), nl, 1, _hip.ptr(grad_rows[:nl]), 64, st))
-            _hip.check(L.skr_clear_marked_rows(_hip.ptr(self._mask_i), self.num_items, 1, _hip.ptr(grad_rows[nl:]), 64, st))
-        else:
-            self._mask_u.zero_()
-            self._mask_i.zero_()
-        if world > 1:   # local rows of the users this rank owns; the others become -1 (skipped)
-            ul = torch.where((users % world) == rank, torch.div(users, world, rounding_mode="floor"), torch.full_like(users, -1))
-        else:
-            ul = users
-        _hip.check(L.skr_mark_ids(_hip.ptr(ul.contiguous()), ul.numel(), 0, _hip.ptr(self._mask_u), st))
-        self._batch_item_ids = torch.cat([pos, neg]).contiguous()
-        _hip.check(L.skr_mark_ids(_hip.ptr(self._batch_item_ids), self._batch_item_ids.numel(), 0, _hip.ptr(self._mask_i), st))
-        return self._mask_u, self._mask_i
-
-    def _rows_exchange_begin(self, block, ids):
-        """Sum the rows `ids` of a replicated [I, 64] block over the ranks, compactly: the rows are gathered into a
-        [len(ids), 64] buffer, the ranks' buffers all-gathered (started here, on the collective's stream) ..."""
-        import torch.distributed as dist
-        n, world = ids.numel(), self.ctx.world
-        if getattr(self, "_xrows", None) is None or self._xrows.shape[0] != n:
-            self._xrows = torch.empty((n, 64), dtype=torch.float32, device=self.device)
-            self._xall = torch.empty((world, n, 64), dtype=torch.float32, device=self.device)
-        _hip.check(_hip.lib().skr_gather_rows(_hip.ptr(block), _hip.ptr(ids), n, 64, _hip.ptr(self._xrows), _hip.stream()))
-        if dist.get_backend() == "nccl":
-            return dist.all_gather_into_tensor(self._xall, self._xrows, async_op=True)
-        return dist.all_gather([self._xall[r] for r in range(world)], self._xrows, async_op=True)
-
-    def _rows_exchange_end(self, work, ids, block):
-        """... and added up in RANK ORDER by every rank itself (skr_sum_blocks): the replicas end with identical bits
-        whatever order the collective library reduces in; the sums go back into the block's rows."""
-        work.wait()
-        L, st, n = _hip.lib(), _hip.stream(), ids.numel()
-        _hip.check(L.skr_sum_blocks(_hip.ptr(self._xall), self.ctx.world, n * 64, _hip.ptr(self._xrows), st))
-        _hip.check(L.skr_scatter_rows(_hip.ptr(self._xrows), _hip.ptr(ids), n, 64, _hip.ptr(block), st))
-
     def whole_final(self):
-        """``final`` for readers of ALL its rows (evaluation, tests): after a training step only the batch's rows are valid
-        (the last layer is computed for those only, and on several ranks the other item rows may even differ between
-        the replicas); an unmasked ``propagate()`` makes it whole again"""
-        if not getattr(self, "_final_whole", False):
-            raise ValueError("ShardedLightGCN.final holds only a batch's rows after train_step(): call propagate() first")
-        return self.final
+        """``final`` for readers of ALL its rows: valid after ``propagate()`` without ``last_rows`` only"""
+        return self._whole_output()
 
     # ---- one training step on a GLOBAL batch -----------------------------------------------------------
     def train_step(self, users, pos, neg):
@@ -342,12 +368,7 @@ class ShardedLightGCN(object):
         # entries that would multiply rows of dL/dfinal that are zero (everything outside the batch).  SKR_LIGHTGCN_DENSE=1
         # computes everything.
         gF, gE = self._g_final, self._g_ego
-        if os.environ.get("SKR_LIGHTGCN_DENSE") == "1":
-            masks = None
-            gF.zero_()
-            self._mask_u = None
-        else:
-            masks = self._batch_rows(users, pos, neg, grad_rows=gF)
+        masks = self._step_masks(users, pos, neg, gF)
         self.propagate(last_rows=masks)
         self.loss.zero_()
         # the whole GLOBAL batch goes to the kernel, which keeps the triples of the users this rank owns: no selection on
@@ -419,15 +440,8 @@ class ShardedLightGCN(object):
             gEi.copy_(gi)                          # identical on every rank -> identical Adam update
         self.optimizer.step()
 
-    def gather_user_table(self):
-        """full [U, 64] user table on every rank (tests / checkpoints)"""
-        full = torch.zeros((self.num_users, 64), dtype=torch.float32, device=self.device)
-        full[torch.from_numpy(self.mine).to(self.device)] = self.ego[:self.n_local]
-        self.ctx.all_reduce(full)
-        return full
 
-
-class ShardedLayerGCN(object):
+class ShardedLayerGCN(ShardedGraphEngine):
     """LayerGCN step / propagation for one rank of a user-sharded job (reference maths: LayerGCN.py:199-252).
 
     edge_u / edge_i   int64 device tensors, the FULL (possibly pruned) train edge list, identical on every rank
@@ -435,6 +449,8 @@ class ShardedLayerGCN(object):
     Rows are laid out [local users ; all items].  Item rows of every intermediate are replicated: each rank
     computes them from all-reduced inputs, so they stay bit-identical without being exchanged again.
     """
+
+    output = "out"
 
     def __init__(self, ctx, edge_u, edge_i, num_users, num_items, user0, item0, n_layers, lr, reg, device=None):
         self.ctx = ctx
@@ -447,9 +463,7 @@ class ShardedLayerGCN(object):
         self.mine = ctx.owned_users(self.num_users)
         nl = self.n_local = len(self.mine)
         n = nl + self.num_items
-        self.ego = torch.cat([user0[self.mine], item0], dim=0).to(dev).contiguous()
-        self.optimizer = DenseAdam(self.ego.view(-1), lr=lr)
-        self._g_ego = self.optimizer.grad.view(n, 64)
+        self._alloc_parameters(user0[self.mine], item0, lr)
         z = lambda: torch.zeros((n, 64), dtype=torch.float32, device=dev)  # noqa: E731
         K = self.n_layers
         self.out = z()
@@ -458,7 +472,6 @@ class ShardedLayerGCN(object):
         self._z = [z(), z()]
         self._g_out = z()
         self._t = [z(), z()]
-        self.loss = torch.zeros(2, dtype=torch.float32, device=dev)
         self.full_blocks = self._blocks(edge_u, edge_i)
         self.train_blocks = self.full_blocks
 
@@ -474,19 +487,12 @@ class ShardedLayerGCN(object):
         sel = (u % world) == rank
         ul, il = torch.div(u[sel], world, rounding_mode="floor"), i[sel]
         vals = (du[u[sel]] * di[il]).float()
-        return (_csr_from_device_coo(ul, il, vals, self.n_local, self.num_items),
-                _csr_from_device_coo(il, ul, vals, self.num_items, self.n_local))
+        return (DeviceCSR.from_coo(ul, il, vals, self.n_local, self.num_items),
+                DeviceCSR.from_coo(il, ul, vals, self.num_items, self.n_local))
 
     def set_train_edges(self, edge_u=None, edge_i=None):
         """the pruned graph of this epoch (LayerGCN.py:133-152); None restores the full graph"""
         self.train_blocks = self.full_blocks if edge_u is None else self._blocks(edge_u, edge_i)
-
-    @property
-    def item_rows(self):
-        return self.ego[self.n_local:]
-
-    def _axpy(self, a, x, y):
-        _hip.check(_hip.lib().skr_axpy(float(a), _hip.ptr(x), _hip.ptr(y), x.numel(), _hip.stream()))
 
     def propagate(self, train=False, last_rows=None):
         """out = sum_k  w_k * (A X_k),  w_k = cos(A X_k, E0) row-wise,  X_{k+1} = w_k * (A X_k).
@@ -512,14 +518,14 @@ class ShardedLayerGCN(object):
                           refine_fwd=(self.ego[:nl], wk[:nl], zk[:nl]), accum_mask=au)
                 x = zk
                 continue
-            # several ranks, software-pipelined (as ShardedLightGCN.propagate): layer k's exchange runs beside the user-side
+            # several ranks, software-pipelined (as in ShardedLightGCN's propagate): layer k's exchange runs beside the user-side
             # product of layer k (whose refinement rides in its row epilogue) and the item-side partial product of layer
             # k + 1, which reads only the user rows of z_k that epilogue has just written
             if k == 0 or not pipelined:
                 a_iu.spmm(x[:nl], y[nl:], row_mask=mi)            # partial items <- local users
             compact = self._batch_item_ids if mi is not None else None
             if compact is not None:
-                work = ShardedLightGCN._rows_exchange_begin(self, y[nl:], compact)
+                work = self._rows_exchange_begin(y[nl:], compact)
             else:
                 work = self.ctx.all_reduce_begin(y[nl:])
             a_ui.spmm(x[nl:], y[:nl], row_mask=mu, accum=self.out[:nl], accum_init=first,
@@ -528,7 +534,7 @@ class ShardedLayerGCN(object):
                 mi_next = last_rows[1] if (last_rows is not None and k + 1 == K - 1) else None
                 a_iu.spmm(zk[:nl], self._y[k + 1][nl:], row_mask=mi_next)
             if compact is not None:
-                ShardedLightGCN._rows_exchange_end(self, work, compact, y[nl:])
+                self._rows_exchange_end(work, compact, y[nl:])
             else:
                 self.ctx.all_reduce_end(work)
             # the item rows' refinement needs the summed rows: a launch of its own over the item block
@@ -540,14 +546,9 @@ class ShardedLayerGCN(object):
         self._out_whole = last_rows is None
         return self.out
 
-    _batch_rows = ShardedLightGCN._batch_rows
-
     def whole_out(self):
-        """``out`` for readers of ALL its rows: valid after ``propagate()`` without ``last_rows`` only (see
-        ShardedLightGCN.whole_final)"""
-        if not getattr(self, "_out_whole", False):
-            raise ValueError("ShardedLayerGCN.out holds only a batch's rows after train_step(): call propagate() first")
-        return self.out
+        """``out`` for readers of ALL its rows: valid after ``propagate()`` without ``last_rows`` only"""
+        return self._whole_output()
 
     def train_step(self, users, pos, neg):
         """global batch in (global user ids, identical on every rank); ``self.loss`` = global (bpr sum, l2) afterwards"""
@@ -559,12 +560,7 @@ class ShardedLayerGCN(object):
         # not computed: rows of the last layer's product the batch does not read and, in the first backward hop, the
         # products with rows of dY_K that are zero (as in the one-GPU engine, recommender/LayerGCN.py train_step)
         gO, gE = self._g_out, self._g_ego
-        if os.environ.get("SKR_LIGHTGCN_DENSE") == "1":
-            masks = None
-            gO.zero_()
-            self._mask_u = None
-        else:
-            masks = self._batch_rows(users, pos, neg, grad_rows=gO)
+        masks = self._step_masks(users, pos, neg, gO)
         self.propagate(train=True, last_rows=masks)
         self.loss.zero_()
         # the whole GLOBAL batch goes to the kernel, which keeps the triples of the users this rank owns
@@ -578,8 +574,8 @@ class ShardedLayerGCN(object):
         if masks is not None and active:
             # both item-side blocks are zero outside the global batch's item rows: compact exchanges
             ids = self._batch_item_ids
-            ShardedLightGCN._rows_exchange_end(self, ShardedLightGCN._rows_exchange_begin(self, gO[nl:], ids), ids, gO[nl:])
-            ShardedLightGCN._rows_exchange_end(self, ShardedLightGCN._rows_exchange_begin(self, gE[nl:], ids), ids, gE[nl:])
+            self._rows_exchange_end(self._rows_exchange_begin(gO[nl:], ids), ids, gO[nl:])
+            self._rows_exchange_end(self._rows_exchange_begin(gE[nl:], ids), ids, gE[nl:])
         else:
             self.ctx.all_reduce(gO[nl:])          # dL/d out, item rows: now the full value everywhere
             self.ctx.all_reduce(gE[nl:])          # the regulariser's part of the item gradient
@@ -616,7 +612,7 @@ class ShardedLayerGCN(object):
                 rb_u = (self.ego[:nl], wb[:nl], yb[:nl], gE[:nl])
                 rb_i = (self.ego[nl:], wb[nl:], yb[nl:], gE[nl:])
                 # (the item side of the FIRST hop -- dY_K's user rows are zero outside the batch's users: the batch users' own rows
-                #  are scattered instead of every item row scanning its users, as in ShardedLightGCN.train_step)
+                #  are scattered instead of every item row scanning its users, as in ShardedLightGCN's train_step)
                 transposed = cu is not None and scatter_ok
                 if not active:
                     if transposed:
@@ -662,16 +658,6 @@ class ShardedLayerGCN(object):
         if self._tmp_i[slot] is None:
             self._tmp_i[slot] = torch.zeros((self.num_items, 64), dtype=torch.float32, device=self.device)
         return self._tmp_i[slot]
-
-    def gather_user_rows(self, local_rows):
-        """[U, 64] on every rank from each rank's [U_local, 64] block"""
-        full = torch.zeros((self.num_users, 64), dtype=torch.float32, device=self.device)
-        full[torch.from_numpy(self.mine).to(self.device)] = local_rows
-        self.ctx.all_reduce(full)
-        return full
-
-    def gather_user_table(self):
-        return self.gather_user_rows(self.ego[:self.n_local])
 
 
 def sharded_evaluate(ctx, evaluator, model, test_users, device):

@@ -63,7 +63,7 @@ class BPRMF(AbstractRecommender):
         self.config = BPRMFConfig(**model_config)
         super().__init__(run_config, self.config)
         self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        from .LightGCN import pad_columns, padded_width
+        from ._sparse import pad_columns, padded_width
         self.dp = padded_width(self.config.n_dim)       # row width of the tables in HBM (zero-padded to a multiple of 64)
         self.device = _hip.require_gpu()
         U, V, b = _init_tables(self.num_users, self.num_items, self.config.n_dim)

@@ -52,7 +52,7 @@ class FPMC(SeqPairwiseRecommender):
 
     def _build(self, last_items=None):
         super()._build(last_items)
-        from .LightGCN import pad_columns, padded_width
+        from ._sparse import pad_columns, padded_width
         nu, ni, e = self.num_users, self.num_items, self.config.embed_size
         self.dp = d = padded_width(e)
         tabs = [pad_columns(t, d) for t in _init_tables(nu, ni, e)]

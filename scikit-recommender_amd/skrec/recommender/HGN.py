@@ -126,7 +126,7 @@ class HGN(SeqPairwiseRecommender):
     def _build(self, windows=None, last_items=None):
         """``windows``: int32 [num_users, seq_L], every user's last seq_L training items, left-padded with the padding item
         (``detached``'s default: item 0 in every position)"""
-        from .LightGCN import pad_columns
+        from ._sparse import pad_columns
         super()._build(last_items)
         cfg = self.config
         e, Lw, T = cfg.embed_size, cfg.seq_L, cfg.seq_T

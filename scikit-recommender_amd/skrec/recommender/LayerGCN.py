@@ -29,11 +29,11 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import PairwiseIterator
 from ..run_config import RunConfig
 from ..utils.py import ModelConfig
-from .base import AbstractRecommender, DenseAdam, DeviceRecommender, on_compute_stream
-from .LightGCN import DEVICE_ADJ_MIN_PAIRS, DeviceCSR, pad_columns, padded_width
+from ._fullgraph import FullGraphBPR
+from ._sparse import DeviceCSR, pad_columns
+from .LightGCN import DEVICE_ADJ_MIN_PAIRS
 
 __all__ = ["LayerGCN", "LayerGCNConfig"]
 
@@ -72,31 +72,26 @@ def build_layergcn_adjacency(inter_coo, n_users, n_items):
     return (d * A * d).astype(np.float32)
 
 
-class LayerGCN(DeviceRecommender):
+class LayerGCN(FullGraphBPR):
+    width_field = "embed_dim"
+
     def __init__(self, run_config: RunConfig, model_config: Dict):
         self.config = LayerGCNConfig(**model_config)
-        AbstractRecommender.__init__(self, run_config, self.config)
+        self._open(run_config)
         cfg = self.config
-        self.num_users, self.num_items = self.dataset.num_users, self.dataset.num_items
-        self.dp = padded_width(cfg.embed_dim)        # row width of the tables in HBM (zero-padded to a multiple of 64)
         if not 0.0 <= cfg.dropout < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         if cfg.prune_draws not in ("reference", "device"):
             raise ValueError("prune_draws must be 'reference' or 'device'")
-        self.device = _hip.require_gpu()
-        from ..parallel import init_from_env, ShardedLayerGCN
-        self.dist = init_from_env()      # one process per GPU under torchrun; world 1 otherwise
+        self._connect(run_config)
         inter = self.dataset.train_data.to_coo_matrix().astype(np.float32)
         # parameters first, like _LayerGCN.__init__ (:114-115): xavier_uniform on plain tensors
         ue = nn.init.xavier_uniform_(torch.empty(self.num_users, cfg.embed_dim))
         ie = nn.init.xavier_uniform_(torch.empty(self.num_items, cfg.embed_dim))
         self.pruning_random = False                     # LayerGCN.py:121
-        self.step_losses = None
-        self.sampler_mode = getattr(run_config, "sampler_mode", None)
-        self.engine = None
-        if self.dist.active and cfg.embed_dim > 64:
-            raise NotImplementedError("one process per GPU: the sharded engines take embed_dim <= 64 (rows of 64 floats)")
+        self._refuse_wide_shards()
         if self.dist.active:
+            from ..parallel import ShardedLayerGCN
             # user-sharded rows, replicated item rows (skrec/parallel.py); duplicate pairs collapse to one edge
             pairs = np.unique(np.stack([inter.row, inter.col], 1).astype(np.int64), axis=0)
             self._edge_u = torch.from_numpy(pairs[:, 0].copy()).to(self.device)
@@ -116,31 +111,14 @@ class LayerGCN(DeviceRecommender):
         self._edge_u = torch.from_numpy(np.asarray(inter.row, dtype=np.int64)).to(self.device)
         self._edge_i = torch.from_numpy(np.asarray(inter.col, dtype=np.int64)).to(self.device)
         self._edge_values = self._normalize_edges(self._edge_u, self._edge_i)
-        N = self.num_users + self.num_items
-        dp = self.dp
-        self.ego = pad_columns(torch.cat([ue, ie], dim=0), dp).to(self.device).contiguous()
-        self.optimizer = DenseAdam(self.ego.view(-1), lr=cfg.lr)
-        self._g_ego = self.optimizer.grad.view(N, dp)
-        z = lambda: torch.zeros((N, dp), dtype=torch.float32, device=self.device)  # noqa: E731
-        K = cfg.n_layers
+        z = self._one_gpu_parameters(ue, ie)
+        N, K = self.num_users + self.num_items, cfg.n_layers
         self.out = z()                                   # sum of refined layers
         self._y = [z() for _ in range(K)]                # A X_k kept for the backward
         self._w = [torch.zeros(N, dtype=torch.float32, device=self.device) for _ in range(K)]
         self._z = [z(), z()]                             # refined layer ping-pong
         self._g_out = z()
         self._t = [z(), z()]
-
-    @property
-    def user_embeddings(self):
-        if self.engine is not None:
-            return self.engine.gather_user_table()[:, :self.config.embed_dim]
-        return self.ego[:self.num_users, :self.config.embed_dim]
-
-    @property
-    def item_embeddings(self):
-        if self.engine is not None:
-            return self.engine.item_rows[:, :self.config.embed_dim]
-        return self.ego[self.num_users:, :self.config.embed_dim]
 
     def _device_adjacency(self, inter):
         """get_norm_adj_mat (LayerGCN.py:173-197) on the device: binary bipartite graph (duplicate pairs are one
@@ -153,7 +131,7 @@ class LayerGCN(DeviceRecommender):
         du = (torch.bincount(u, minlength=nu).double() + 1e-7).pow(-0.5)
         di = (torch.bincount(i, minlength=self.num_items).double() + 1e-7).pow(-0.5)
         vals = (du[u] * di[i]).float()
-        return DeviceCSR.from_device_coo(torch.cat([u, i + nu]), torch.cat([i + nu, u]), torch.cat([vals, vals]), n)
+        return DeviceCSR.from_coo(torch.cat([u, i + nu]), torch.cat([i + nu, u]), torch.cat([vals, vals]), n)
 
     def _normalize_edges(self, u, i):
         """_normalize_adj_m (LayerGCN.py:154-163): 1/sqrt((deg_u + 1e-7)(deg_i + 1e-7)) on the given edges"""
@@ -209,7 +187,7 @@ class LayerGCN(DeviceRecommender):
         n = self.num_users + self.num_items
         rows = torch.cat([u, i + self.num_users])
         cols = torch.cat([i + self.num_users, u])
-        self.train_adj = DeviceCSR.from_device_coo(rows, cols, torch.cat([vals, vals]), n)
+        self.train_adj = DeviceCSR.from_coo(rows, cols, torch.cat([vals, vals]), n)
 
     def forward(self, adj=None, last_rows=None):
         """``last_rows`` (uint8 [N], training only): the rows of ``out`` that will be read -- the LAST layer's product is
@@ -237,18 +215,7 @@ class LayerGCN(DeviceRecommender):
         # the products with rows of dY_K that are zero (dL/d out is zero outside the batch's rows, and the refinement's
         # backward is row-local).  SKR_LIGHTGCN_DENSE=1 computes everything.
         gO, gE = self._g_out, self._g_ego
-        if os.environ.get("SKR_LIGHTGCN_DENSE") == "1":
-            rows = None
-            gO.zero_()
-            self._row_mask = None
-        else:
-            # dL/d out is zero outside the previous batch's rows: those are cleared (with their marks), not the whole buffer
-            if getattr(self, "_row_mask", None) is None:
-                self._row_mask = torch.zeros(self.num_users + self.num_items, dtype=torch.uint8, device=self.device)
-                gO.zero_()
-            else:
-                _hip.check(L.skr_clear_marked_rows(_hip.ptr(self._row_mask), N, 1, _hip.ptr(gO), self.dp, st))
-            rows = self._batch_rows(users, pos, neg)
+        rows = self._step_rows(gO, users, pos, neg)
         self.forward(adj, last_rows=rows)
         _hip.check(L.skr_bpr_step_dim(
             _hip.ptr(self.out[:nu]), _hip.ptr(self.out[nu:]), None, _hip.ptr(self.ego[:nu]), _hip.ptr(self.ego[nu:]),
@@ -272,28 +239,6 @@ class LayerGCN(DeviceRecommender):
                 adj.spmm(dy, None, accum=gE, accum_scale=1.0, col_mask=cm)
         self.optimizer.step()
 
-    def _batch_rows(self, users, pos, neg):
-        """uint8 [N]: 1 on the rows of [U; V] a batch touches (the gathers of calculate_loss, LayerGCN.py:245-253)"""
-        m, L, st, nu = self._row_mask, _hip.lib(), _hip.stream(), self.num_users
-        _hip.check(L.skr_mark_ids(_hip.ptr(users), users.numel(), 0, _hip.ptr(m), st))
-        _hip.check(L.skr_mark_ids(_hip.ptr(pos), pos.numel(), nu, _hip.ptr(m), st))
-        _hip.check(L.skr_mark_ids(_hip.ptr(neg), neg.numel(), nu, _hip.ptr(m), st))
-        return m
-
-    @on_compute_stream
-    def train_epoch(self, data_iter):
-        self.step_losses = torch.zeros((len(data_iter), 2), dtype=torch.float32, device=self.device)
-        for k, (u, i, j) in enumerate(data_iter.iter_device()):
-            if self.engine is not None:      # every rank walks the same global batches and keeps its users
-                self.engine.train_step(u, i, j)
-                self.step_losses[k] = self.engine.loss
-            else:
-                self.train_step(u.contiguous(), i.contiguous(), j.contiguous(), self.step_losses[k])
-
-    def _make_iterator(self):
-        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True,
-                                drop_last=False, sampler_mode=self.sampler_mode)
-
     def _run_epoch(self, data_iter, epoch):
         self.pre_epoch_processing()
         self.train_epoch(data_iter)
@@ -306,14 +251,6 @@ class LayerGCN(DeviceRecommender):
             self._full_user_out = e.gather_user_rows(e.whole_out()[:e.n_local])   # every rank can rank any user
         else:
             self.forward()
-
-    @on_compute_stream
-    def evaluate(self, test_users=None):
-        self._refresh_outputs()
-        if self.engine is None:
-            return self.evaluator.evaluate(self, test_users)
-        from ..parallel import sharded_evaluate
-        return sharded_evaluate(self.dist, self.evaluator, self, test_users, self.device)
 
     def predict_factors(self):
         if self.engine is not None:

@@ -55,7 +55,7 @@ class TransRec(SeqPairwiseRecommender):
 
     def _build(self, last_items=None):
         super()._build(last_items)
-        from .LightGCN import pad_columns, padded_width
+        from ._sparse import pad_columns, padded_width
         nu, ni, e = self.num_users, self.num_items, self.config.embed_size
         self.dp = d = padded_width(e)
         U, V, b, T = _init_tables(nu, ni, e)

@@ -4,15 +4,13 @@ linear block of the flat parameter buffer, and ``GraphRecommender`` -- the epoch
 half on ``DeviceRecommender`` (base.py).  A model keeps its config, its limits, its draws, ``_build``, ``gradient_step``,
 ``train_step`` and what is its own in ``propagate``.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _hip
 from ..io import InteractionIterator
 from .base import DeviceRecommender, on_compute_stream
-from .LightGCN import DeviceCSR
+from ._sparse import DeviceCSR
 
 __all__ = ["GraphRecommender", "normalized_adjacency", "selfcf_adjacency", "train_csr", "upload_csr", "run_plan",
            "propagate_mean", "linear_block"]
@@ -35,15 +33,7 @@ def upload_csr(rowptr, items, device):
             torch.from_numpy(np.ascontiguousarray(items, dtype=np.int32)).to(device))
 
 
-def _device_csr(shape, rowptr, col, val):
-    """a DeviceCSR around arrays that are already in HBM"""
-    m = DeviceCSR.__new__(DeviceCSR)
-    m.shape, m.nnz = shape, int(col.numel())
-    m.rowptr, m.col, m.val = rowptr.contiguous(), col.contiguous(), val.contiguous()
-    if m.nnz == 0:
-        m.col = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
-        m.val = torch.zeros(1, dtype=torch.float32, device=rowptr.device)
-    return m
+_device_csr = DeviceCSR.from_arrays     # (shape, rowptr, col, val): a DeviceCSR around arrays that are already in HBM
 
 
 def _adjacency(rowptr, col, num_users, num_items, value, want_perm):
@@ -88,12 +78,10 @@ def selfcf_adjacency(rowptr, col, num_users, num_items):
 # ---- plan runs ---------------------------------------------------------------------------------------
 def run_plan(mat, X, Y=None, addend=None, accum=None, accum_base=None, accum_scale=1.0):
     """one product of ``mat``'s plan with 64-column rows of X and the plain epilogue (skr_spmm_epilogue): Y = mat X
-    (+ addend); accum = accum_scale * (accum_base + Y) with a base, accum += accum_scale * Y without"""
-    ep = _hip.SpmmEpilogue()
-    ep.mode = _hip.EPI_PLAIN
-    ep.addend, ep.Y, ep.accum, ep.accum_base = _hip.ptr(addend), _hip.ptr(Y), _hip.ptr(accum), _hip.ptr(accum_base)
-    ep.accum_scale = accum_scale
-    _hip.check(_hip.lib().skr_spmm_plan_run_ex(mat._plan_handle(), _hip.ptr(X), 64, ctypes.byref(ep), None, None, _hip.stream()))
+    (+ addend); accum = accum_scale * (accum_base + Y) with a base, accum += accum_scale * Y without.  Always the plan,
+    whatever the matrix's size; the epilogue itself is filled by ``DeviceCSR._run_epilogue``"""
+    mat._run_epilogue(_hip.ptr(X), None, None, _hip.EPI_PLAIN, 0, _hip.ptr(addend), _hip.ptr(Y), _hip.ptr(accum), _hip.ptr(accum_base),
+                      accum_scale)
 
 
 def propagate_mean(adj, adj_t, X0, num_users, L, pooled, ping=None, hops=None):

@@ -10,7 +10,7 @@ for p in (REPO, os.path.join(REPO, "scikit-recommender_amd")):
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from skrec.parallel import _csr_from_device_coo  # noqa: E402
+from skrec.recommender._sparse import DeviceCSR  # noqa: E402
 
 dev = torch.device("cuda", 0)
 U, I, E = 1_000_000, 100_000, 50_000_000
@@ -18,7 +18,7 @@ ds = bench.synth_dataset(U, I, E, 20260101, dev)
 u, it = ds["users"].long(), ds["items"].long()
 du, di = torch.bincount(u, minlength=U).float(), torch.bincount(it, minlength=I).float()
 vals = torch.where(du > 0, du.pow(-0.5), du)[u] * torch.where(di > 0, di.pow(-0.5), di)[it]
-a_iu = _csr_from_device_coo(it, u, vals, I, U)
+a_iu = DeviceCSR.from_coo(it, u, vals, I, U)
 X = torch.randn((U, 64), device=dev)
 Y = torch.empty((I, 64), device=dev)
 for _ in range(3):

@@ -419,12 +419,11 @@ if "deep" in WHAT:
                      max_err=float((YA - YA_ref).abs().max()), item_total_ms=round(tA + tR + bestB, 4))
 
 if "plan" in WHAT:
-    from skrec.recommender.LightGCN import DeviceCSR, build_adjacency_device
+    from skrec.recommender._sparse import DeviceCSR
+    from skrec.recommender.LightGCN import build_adjacency_device
 
     def mk(rp, col, val, shape):
-        c = DeviceCSR.__new__(DeviceCSR)
-        c.shape, c.nnz, c.rowptr, c.col, c.val = shape, int(rp[-1]), rp, col, val
-        return c
+        return DeviceCSR.from_arrays(shape, rp, col, val)
     for name, c, X, Yref in (("user", mk(ui_rp, ui_col, ui_val, (U, I)), X_i, Yu_ref), ("item", mk(iu_rp, iu_col, iu_val, (I, U)), X_u, Yi_ref)):
         Y = torch.empty(c.shape[0], 64, device=dev)
         os.environ["SKR_SPMM_PLAN"] = "1"

@@ -14,7 +14,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from skrec import _hip  # noqa: E402
-from skrec.recommender.LightGCN import DeviceCSR  # noqa: E402
+from skrec.recommender._sparse import DeviceCSR  # noqa: E402
 
 dev = torch.device("cuda", 0)
 LAB = C.CDLL(os.path.join(REPO, "tools", "lab", "libsweep_lab.so"))
@@ -41,14 +41,7 @@ def timeit(fn, n=10, warm=3):
     return e0.elapsed_time(e1) / n
 
 
-def make_csr(rows, cols, vals, n_rows, n_cols):
-    order = torch.argsort(rows * n_cols + cols)
-    c = DeviceCSR.__new__(DeviceCSR)
-    c.shape, c.nnz = (n_rows, n_cols), int(rows.numel())
-    c.rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
-    c.rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
-    c.col, c.val = cols[order].int().contiguous(), vals[order].float().contiguous()
-    return c
+make_csr = DeviceCSR.from_coo
 
 
 ds = bench.synth_dataset(U, I, E, 20260101, dev)
