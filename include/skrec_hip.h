@@ -1190,6 +1190,89 @@ size_t skr_knn_workspace(int n_rows, int k);
 int skr_knn_topk(const float* d_X, int n_rows, int feat_dim, int feat_ld, int k, int32_t* d_ids, float* d_sims, void* d_work,
                  size_t work_bytes, void* stream);
 
+/* ============================================================================================
+ * L -- FREEDOM, frozen item graph and degree-sensitive edge pruning (csrc/freedom.hip)
+ * replaces: _FREEDOM.pre_epoch_processing / _normalize_adj_m / forward / calculate_loss and FREEDOM.fit's step
+ * (recommender/FREEDOM.py:175-252, 285-295) at embed_dim <= 64.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  Feature tables and projection blocks are section J's: [n_items][feat_ld] and W [64][feat_ld] | b [64].
+ * R is the binary train matrix in CSR (nnz entries, columns ascending), R^T its transpose, perm[e] the position in R^T's
+ * entry order of entry e of R's.  S is the frozen item graph [n_items, n_items] (section K, build_item_graph).
+ * ========================================================================================== */
+#define SKR_FREEDOM_MAX_BATCH 2048
+#define SKR_FREEDOM_MAX_LAYERS 4
+#define SKR_FREEDOM_MAX_FEAT 4096
+#define SKR_FREEDOM_MAX_NNZ 2147483647LL
+/* The pruning of one epoch (FREEDOM.py:175-190) in three entries.
+ * d_keys[e] = d_w[e] / E_e with E_e a unit exponential from 32 random bits of fast_rng.h's generator keyed by (seed, epoch, e),
+ * the division in float64: the n_keep largest keys are a sample without replacement with probabilities proportional to w.
+ * torch.multinomial is built the same way on another generator: the kept set equals the reference's in law only.  A key is
+ * finite, and positive where w is. */
+int skr_freedom_keys(const float* d_w, int64_t nnz, uint64_t seed, uint64_t epoch, float* d_keys, void* stream);
+/* d_keep[e] (uint8 [nnz]) = 1 for exactly n_keep entries: those with the largest keys, equal keys ranked by ascending e.
+ * Keys must be >= 0 and no NaN: the select is a radix select on their bit patterns -- four histogram passes of 8 bits
+ * (integer atomics), then one ordered pass that admits the ties at the threshold by index.  0 <= n_keep <= nnz.  d_work:
+ * skr_freedom_select_workspace(nnz) bytes, 16-byte aligned, no initial contents.  Two calls give the same bytes. */
+size_t skr_freedom_select_workspace(int64_t nnz);
+int skr_freedom_select(const float* d_keys, int64_t nnz, int64_t n_keep, uint8_t* d_keep, void* d_work, size_t work_bytes,
+                       void* stream);
+/* The kept entries (d_keep, uint8 [nnz] in R's entry order) as the CSR of R' and of R'^T, every array sized for nnz entries
+ * (an empty row is fine): rowptr int64, columns int32 ascending, values fp32
+ *   float(pow(1e-7 + kept entries of the row, -0.5)) * float(pow(1e-7 + kept entries of the column, -0.5))
+ * with the powers in float64 and one fp32 product (_normalize_adj_m, FREEDOM.py:192-201, whose fp32 powers are within 1 ulp).
+ * d_n_kept[0] = the number of kept entries.  d_work: skr_freedom_pruned_workspace bytes, 16-byte aligned. */
+size_t skr_freedom_pruned_workspace(int n_users, int n_items, int64_t nnz);
+int skr_freedom_pruned_csr(int n_users, int n_items, int64_t nnz, const int64_t* d_rowptr, const int32_t* d_col,
+                           const int64_t* d_rowptr_t, const int32_t* d_col_t, const int32_t* d_perm, const uint8_t* d_keep,
+                           int64_t* d_out_rowptr, int32_t* d_out_col, float* d_out_val, int64_t* d_out_rowptr_t,
+                           int32_t* d_out_col_t, float* d_out_val_t, int64_t* d_n_kept, void* d_work, size_t work_bytes,
+                           void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   M = mean_{k=0..n_ui_layers} A'^k X_0 through skr_spmm_plan_run_ex (2 n_ui_layers runs), then M_items += S^n_mm_layers
+ *   X_0 items (n_mm_layers runs; with n_mm_layers == 0, X_0's item rows);
+ *   u = M[users], p = M[n_users + pos], q = M[n_users + neg], x_g = <u, p - q>; at reg > 0, per present modality m,
+ *   x_m = <u, P_m - Q_m> with P_m / Q_m = skr_bm3_project at pos / neg; ls(x) = min(x, 0) - log1p(exp(-|x|));
+ *   loss[0] = -mean ls(x_g), loss[1] = reg * sum_m -mean ls(x_m), loss[2] = their sum                   WRITTEN
+ *   grad: the gradient of loss[2] with respect to the [n_users + n_items, 64] rows, every element        WRITTEN
+ *   at reg > 0: trs_grad[m] (W: every element; b: exact zeros, it cancels in x_m) and feat_grad[m] -- first the rows named
+ *   by clear_items are zeroed, then the row of every distinct item of pos || neg is written; other rows are left alone.
+ * At reg == 0 the modal arguments are not looked at and nothing is launched for them.  Rows with a user or item out of range
+ * contribute nothing.  No floating-point atomic, every sum in a fixed order: the step is bit-reproducible. */
+typedef struct skr_freedom_step_args {
+    const skr_spmm_plan* plan_a;       /* A' [n_users, n_items]: this epoch's pruned matrix; may be NULL if n_ui_layers == 0 */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    const skr_spmm_plan* plan_s;       /* S [n_items, n_items]; may be NULL if n_mm_layers == 0 */
+    const skr_spmm_plan* plan_st;      /* its transpose */
+    int32_t n_users, n_items, dim, n_ui_layers, n_mm_layers, n;
+    int32_t feat_dim[2];               /* image, text; 0 = the modality is absent */
+    int32_t feat_ld[2];
+    const float* params;               /* [n_users + n_items, 64] */
+    const float* trs[2];               /* W [64][feat_ld], then b [64] */
+    const float* feat[2];              /* [n_items][feat_ld] */
+    const int32_t* users;              /* [n] */
+    const int32_t* pos;                /* [n] */
+    const int32_t* neg;                /* [n] */
+    const int32_t* clear_items;        /* [n_clear <= 2 * SKR_FREEDOM_MAX_BATCH] item ids whose feat_grad rows are zeroed first */
+    int32_t n_clear;
+    float reg;
+    float* M;                          /* [n_users + n_items, 64] */
+    float* ping[2];                    /* scratch, [n_users + n_items, 64] each; NULL if both layer counts are < 2 */
+    float* G;                          /* scratch, [n_users + n_items, 64] */
+    float* grad;                       /* [n_users + n_items, 64] */
+    float* trs_grad[2];
+    float* feat_grad[2];
+    float* loss;                       /* [3] */
+    void* work;                        /* skr_freedom_workspace(n) bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_freedom_step_args;
+size_t skr_freedom_workspace(int n);
+int skr_freedom_step(const skr_freedom_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_FREEDOM_GROUPS launch groups (user-item plan runs forward; item-graph
+ * runs; clear and projections; batch kernel and loss; clear of G, rank and seg_add; projection backward; backward plan runs of
+ * both graphs): h_ms[k] (host) = milliseconds of group k; synchronises the stream (timing tools). */
+#define SKR_FREEDOM_GROUPS 7
+int skr_freedom_step_timed(const skr_freedom_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,14 @@ SIGNATURES = {
     "skr_bm3_queries": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "skr_knn_workspace": (sz, [i32, i32]),
     "skr_knn_topk": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "skr_freedom_keys": (i32, [vp, i64, u64, u64, vp, vp]),
+    "skr_freedom_select_workspace": (sz, [i64]),
+    "skr_freedom_select": (i32, [vp, i64, i64, vp, vp, sz, vp]),
+    "skr_freedom_pruned_workspace": (sz, [i32, i32, i64]),
+    "skr_freedom_pruned_csr": (i32, [i32, i32, i64] + [vp] * 14 + [sz, vp]),
+    "skr_freedom_workspace": (sz, [i32]),
+    "skr_freedom_step": (i32, [vp, vp]),
+    "skr_freedom_step_timed": (i32, [vp, vp, vp]),
 }
 
 
@@ -202,6 +210,17 @@ class BM3StepArgs(C.Structure):
                 ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
 
 
+class FreedomStepArgs(C.Structure):
+    """skr_freedom_step_args (include/skrec_hip.h): the plans of both graphs, the parameters, the feature blocks (image, text),
+    the batch and the scratch of one FREEDOM step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("plan_s", vp), ("plan_st", vp), ("n_users", C.c_int32), ("n_items", C.c_int32),
+                ("dim", C.c_int32), ("n_ui_layers", C.c_int32), ("n_mm_layers", C.c_int32), ("n", C.c_int32),
+                ("feat_dim", C.c_int32 * 2), ("feat_ld", C.c_int32 * 2), ("params", vp), ("trs", vp * 2), ("feat", vp * 2),
+                ("users", vp), ("pos", vp), ("neg", vp), ("clear_items", vp), ("n_clear", C.c_int32), ("reg", C.c_float), ("M", vp),
+                ("ping", vp * 2), ("G", vp), ("grad", vp), ("trs_grad", vp * 2), ("feat_grad", vp * 2), ("loss", vp), ("work", vp),
+                ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -218,6 +237,8 @@ SKR_SELFCF_PRED_FLOATS = 64 * 64 + 64    # the predictor's block of the flat par
 SKR_BM3_MAX_BATCH, SKR_BM3_MAX_LAYERS, SKR_BM3_MAX_FEAT, SKR_BM3_GROUPS = 2048, 4, 4096, 7   # skr_bm3_step limits
 SKR_BM3_PRED_FLOATS = 64 * 64 + 64       # the predictor's block of BM3's parameter buffer
 SKR_BM3_DRAW_USER, SKR_BM3_DRAW_ITEM, SKR_BM3_DRAW_TEXT, SKR_BM3_DRAW_IMAGE = 0, 1, 2, 3   # the tables of the target draws
+SKR_FREEDOM_MAX_BATCH, SKR_FREEDOM_MAX_LAYERS, SKR_FREEDOM_MAX_FEAT, SKR_FREEDOM_GROUPS = 2048, 4, 4096, 7   # skr_freedom_step limits
+SKR_FREEDOM_MAX_NNZ = 2 ** 31 - 1         # skr_freedom_keys / _select / _pruned_csr: entries of the train matrix
 SKR_KNN_MAX_K = 32                       # skr_knn_topk: neighbours per row
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
