@@ -28,6 +28,23 @@ def test_registry_finds_model_with_reference_defaults(name):
         config_class(lr=1)._validate()      # the reference asserts a float
 
 
+@pytest.mark.parametrize("name", ["FPMC", "TransRec"])
+def test_embed_size_beyond_256_is_refused_before_any_launch(monkeypatch, name):
+    """rows are padded to 64, 128, 192 or 256 floats: embed_size = 257 raises padded_width's NotImplementedError in
+    ``_build``, before the tables are drawn and before anything of the kernel library is called"""
+    import importlib
+    import torch
+    from skrec import _hip
+
+    def no_lib():
+        raise AssertionError("the kernel library is called before the width is checked")
+    monkeypatch.setattr(_hip, "require_gpu", lambda: torch.device("cpu"))
+    monkeypatch.setattr(_hip, "lib", no_lib)
+    cls = getattr(importlib.import_module(f"skrec.recommender.{name}"), name)
+    with pytest.raises(NotImplementedError, match="embedding widths up to 256"):
+        cls.detached(8, 8, dict(embed_size=257))
+
+
 def _err(L):
     return L.skr_last_error().decode()
 
