@@ -575,6 +575,40 @@ int skr_bpr_fused_block2(float* d_p, float* d_m, float* d_v, int64_t n, float* d
                          int64_t step_t0, int k, float reg, float* d_loss64, int64_t loss_stride_floats,
                          const int32_t* d_slot_block, const int32_t* d_slot_fin, const int32_t* d_n_slots,
                          const int32_t* d_tag_next, int32_t tag_next_value, const float* d_pre, void* stream);
+/* The loss words off the step's path.  Nothing reads a step's loss words before its block has ended, so the step launch
+ * need not add them to d_loss64 itself (512 float atomics on 256 bytes at n_batch = 1 024):
+ *   skr_bpr_fused_step3   as _step2, but every launched wavefront stores its two sums, with one plain 8-byte store, into
+ *                         row s of d_loss_part (exact zeros where the wavefront had no interaction); d_loss64 is not
+ *                         touched.  d_loss_part: float[skr_bpr_fused_loss_part_floats(n_batch, k)], 8-byte aligned, of any
+ *                         content: every pair _end3 reads was written by the block's own launches.  One buffer serves
+ *                         all blocks of a stream.
+ *   skr_bpr_fused_end3    as _end; with which 0 / 1 the launch also folds the k rows of d_loss_part into the block's loss
+ *                         words: d_loss64[s * loss_stride_floats + 2 * q + c] += the sum over the workgroups q,
+ *                         q + SKR_LOSS_SLOTS, ... (ascending) of ((w0 + w1) + w2) + w3, the workgroup's four wavefronts --
+ *                         _step2's sums, in a FIXED order: two runs give the same bits.  It adds to what is there (one
+ *                         atomic per word and step: a stride of 0 sums the steps); a pair no workgroup feeds receives
+ *                         +0.0f.  which = 2 folds nothing.  n_batch: the step launches'.
+ *   skr_bpr_fused_block3  as _block2 through _step3 / _end3: the same k + 1 launches.
+ *   skr_bpr_fused_loss_part_floats   k * 8 * min(ceil(n_batch / 4), 4 096) (one pair per wavefront of a step launch's grid;
+ *                         256 KB at k = 32, n_batch = 1 024); 0 for an empty batch.
+ * Parameters and moments: _step2's bits. */
+int64_t skr_bpr_fused_loss_part_floats(int n_batch, int k);
+int skr_bpr_fused_step3(const float* d_p, const float* d_m, const float* d_v, int64_t n, float* d_work, int64_t cap,
+                        const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch,
+                        int64_t user_block0, int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2,
+                        float eps, int64_t step_t0, int k, int s, float reg, float* d_loss64, const float* d_pre,
+                        float* d_loss_part, void* stream);
+int skr_bpr_fused_end3(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_slot_block,
+                       const int32_t* d_slot_fin, const int32_t* d_n_slots, float lr, float beta1, float beta2, float eps,
+                       int64_t step_t0, int k, const int32_t* d_tag_next, int32_t tag_next_value, int which,
+                       const float* d_loss_part, float* d_loss64, int64_t loss_stride_floats, int n_batch, void* stream);
+int skr_bpr_fused_block3(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_u,
+                         const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch, int64_t user_block0,
+                         int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2, float eps,
+                         int64_t step_t0, int k, float reg, float* d_loss64, int64_t loss_stride_floats,
+                         const int32_t* d_slot_block, const int32_t* d_slot_fin, const int32_t* d_n_slots,
+                         const int32_t* d_tag_next, int32_t tag_next_value, const float* d_pre, float* d_loss_part,
+                         void* stream);
 
 /* The cold pass sorts each 64-float block, by the values it starts from, into one of three exact evaluations of
  * the same k updates: AT REST (the update provably rounds to p + q == p for all k steps: only the moments decay),

@@ -60,6 +60,9 @@ struct FusedWork {
     int64_t cap;
 };
 
+// (the one element of the deferred step kernel's parameter pack)
+__device__ __forceinline__ float* fused_loss_part(float* row) { return row; }
+
 // One wavefront per interaction, its five rows one after the other (dbg: timing switches of tools/fused_lab.py).  A
 // workgroup of five wavefronts per interaction (one per row, the rows meeting in LDS) was tried and is slower (18.4 vs 12.7 us
 // per launch alone on the chip): a CU holds four interactions either way, so the catch-up arithmetic per SIMD is the same,
@@ -84,12 +87,21 @@ struct FusedWork {
 // on one path are load destinations on the others, so all older loads must have returned first): up to five dependent
 // trips for the rows, and four for the arguments and tables in front of them.  The values that reach chain_advance are
 // the same: the kernel stays bit-identical.
+//
+// The loss words, two forms.  bpr_fused_step_kernel<> adds one pair per WORKGROUP to the step's SKR_LOSS_SLOTS pairs.  The
+// DEFERRED form, bpr_fused_step_kernel<float*>, takes one more argument at the END of the list (the first 14 dwords stay
+// where they are): the step's row of the block's partials buffer, float[2 * BPR_WAVES * gridDim.x].  Lane 0 of every
+// launched wavefront stores its two sums there with one 8-byte store -- exact zeros where the wavefront had no interaction,
+// so that every pair of the row is written by this launch and the buffer never needs clearing -- and the block's end launch
+// folds the rows into the pairs (bpr_fused_end_kernel).  No LDS, no barrier and no atomic on the loss in that form.
+template <typename... LossPart>
 __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
     const int32_t* __restrict__ u_ids, const int32_t* __restrict__ i_ids, const int32_t* __restrict__ j_ids,
     const int32_t* __restrict__ meta, int n, int s_now, int dbg, int loss_slots, const float* __restrict__ P,
     const float* __restrict__ M, const float* __restrict__ V, int64_t n_par, FusedWork w, int64_t ublk0, int64_t iblk0,
-    int64_t bblk0, AdamBlockArgs a, float reg, float* __restrict__ loss, const float* __restrict__ pre) {
-    __shared__ float s_loss[BPR_WAVES], s_l2[BPR_WAVES];
+    int64_t bblk0, AdamBlockArgs a, float reg, float* __restrict__ loss, const float* __restrict__ pre, LossPart... loss_part) {
+    constexpr bool DEFER = sizeof...(LossPart) == 1;
+    static_assert(sizeof...(LossPart) <= 1, "the existing form, or one pointer to the step's row of partials");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // round 1: the ids and the words in two loads -- lane L works for row L >> 2 (lanes 20 .. 63: row 4 again) and fetches
     // that row's id and word.  The first interaction's are issued here, before anything branches and beside the tables below
@@ -108,6 +120,7 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
     asm volatile("" ::"s"(ublk0), "s"(iblk0), "s"(bblk0), "s"(s_now), "s"(reg), "s"(loss_slots), "s"(dbg), "s"(ca.stats), "s"(ca.first_unit));
     asm volatile("" ::"s"(ca.one_minus_b1), "s"(ca.b2), "s"(ca.one_minus_b2), "s"(ca.eps), "s"(ca.rest_eps), "s"(ca.rest_b2k), "s"(ca.fast_vlo),
                  "s"(ca.fast_mlo), "s"(ca.fast_mhi));
+    if constexpr (DEFER) asm volatile("" ::"s"(fused_loss_part(loss_part...)));
     // Issue priority over the cold pass that shares the SIMDs (side stream); dbg & 16 switches it off.  (Set behind the
     // argument loads: in front of them its test of dbg is a dependent scalar round of its own.)  Round 2 measured it
     // alone (the step +6 %, but the cold pass 0.47 -> 0.57 ms, which then bounded the block) and left it off; round 3 pairs it
@@ -239,23 +252,39 @@ __global__ __launch_bounds__(BPR_WAVES * 64) void bpr_fused_step_kernel(
         acc_loss += l;
         acc_l2 += 0.5f * sq;
     }
-    // the loss words: one pair of adds per WORKGROUP.  The SKR_LOSS_SLOTS pairs of a step lie in four 128-byte lines, and what
-    // the adds cost follows their number per line: 1.5 us of the launch for these 512 (SKR_FUSED_DBG=8 takes them out), 9 us
-    // for one pair per wavefront issued ahead of the gradient traffic -- built, measured, removed
-    if (lane == 0) {
-        s_loss[wv] = acc_loss;
-        s_l2[wv] = acc_l2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && !(dbg & 8)) {
-        float x = 0.0f, y = 0.0f;
-        for (int q = 0; q < BPR_WAVES; ++q) {
-            x += s_loss[q];
-            y += s_l2[q];
+    if constexpr (DEFER) {
+        // the loss words: one pair per WAVEFRONT, stored, for the end launch to fold
+        // (b0 < BPR_WAVES * gridDim.x: inside the row.  A plain store: write-through as the owner stores, dbg & 32 for
+        // tools/fused_lab.py, measured 0.14 us per launch slower -- 9.20 against 9.06 us)
+        if (lane == 0 && !(dbg & 8)) {
+            float* part = fused_loss_part(loss_part...) + 2 * b0;
+            if (dbg & 32)
+                __hip_atomic_store(reinterpret_cast<uint64_t*>(part),
+                                   static_cast<uint64_t>(__float_as_uint(acc_l2)) << 32 | __float_as_uint(acc_loss), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            else
+                *reinterpret_cast<float2*>(part) = make_float2(acc_loss, acc_l2);
         }
-        const int sl = 2 * (static_cast<int>(blockIdx.x) % loss_slots);
-        atomicAdd(&loss[sl], x);
-        atomicAdd(&loss[sl + 1], y);
+    } else {
+        // the loss words: one pair of adds per WORKGROUP.  The SKR_LOSS_SLOTS pairs of a step lie in four 128-byte lines, and what
+        // the adds cost follows their number per line: 1.5 us of the launch for these 512 (SKR_FUSED_DBG=8 takes them out), 9 us
+        // for one pair per wavefront issued ahead of the gradient traffic -- built, measured, removed
+        __shared__ float s_loss[BPR_WAVES], s_l2[BPR_WAVES];
+        if (lane == 0) {
+            s_loss[wv] = acc_loss;
+            s_l2[wv] = acc_l2;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && !(dbg & 8)) {
+            float x = 0.0f, y = 0.0f;
+            for (int q = 0; q < BPR_WAVES; ++q) {
+                x += s_loss[q];
+                y += s_l2[q];
+            }
+            const int sl = 2 * (static_cast<int>(blockIdx.x) % loss_slots);
+            atomicAdd(&loss[sl], x);
+            atomicAdd(&loss[sl + 1], y);
+        }
     }
 }
 
@@ -293,12 +322,35 @@ __global__ __launch_bounds__(256) void bpr_fused_pre_kernel(const int32_t* __res
 // updates up to the later of the two rows' last namings; from there to the block's end two rows that both passed the
 // ordinary test advance together on the packed pair form (adam_pair_ordinary: the cold pass's, the same operations per
 // component).  A pair with a row that failed the test or that the `which` filter drops, and a lone last slot, run one by one.
+//
+// The fold of the deferred loss words (fold_wgs > 0; skr_bpr_fused_end3): the first fold_wgs workgroups of the grid -- in front,
+// so that they are dispatched first and are not the launch's tail -- take one step of the block per wavefront and sum the row
+// of partials its launch wrote (part_wgs workgroups of BPR_WAVES pairs).  Lane L owns word L & 1 of pair L >> 1: for the
+// workgroups g = pair, pair + SKR_LOSS_SLOTS, ... in ascending order it adds ((w0 + w1) + w2) + w3 of the workgroup's four
+// wavefronts -- the association of the step kernel's other form, in a fixed order instead of the atomics' -- and adds the
+// sum to the step's loss word with ONE atomic (the contract stays "adds to what is there", and a stride of 0 lets the
+// steps collide).  The slot workgroups' index shifts by fold_wgs.
 __global__ __launch_bounds__(256) void bpr_fused_end_kernel(const int32_t* __restrict__ n_slots, const int32_t* __restrict__ slot_blk,
                                                             const int32_t* __restrict__ slot_fin, const int32_t* __restrict__ tag_next,
                                                             int32_t tag_next_value, int which, int64_t n_par, float* __restrict__ P,
-                                                            float* __restrict__ M, float* __restrict__ V, FusedWork w, AdamBlockArgs a) {
+                                                            float* __restrict__ M, float* __restrict__ V, FusedWork w, AdamBlockArgs a,
+                                                            int fold_wgs, int part_wgs, const float* __restrict__ loss_part,
+                                                            float* __restrict__ loss, int64_t loss_stride) {
     const int lane = threadIdx.x & 63;
-    const int64_t slot0 = 2 * (static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (static_cast<int>(blockIdx.x) < fold_wgs) {
+        const int s = static_cast<int>(blockIdx.x) * 4 + wave;
+        if (s >= a.k) return;
+        const float* row = loss_part + static_cast<int64_t>(s) * part_wgs * (2 * BPR_WAVES) + (lane & 1);
+        float sum = 0.0f;
+        for (int g = lane >> 1; g < part_wgs; g += SKR_LOSS_SLOTS) {
+            const float* p = row + g * (2 * BPR_WAVES);
+            sum += ((p[0] + p[2]) + p[4]) + p[6];
+        }
+        atomicAdd(&loss[s * loss_stride + lane], sum);
+        return;
+    }
+    const int64_t slot0 = 2 * ((static_cast<int64_t>(blockIdx.x) - fold_wgs) * 4 + wave);
     const int64_t n = *n_slots;
     if (slot0 >= n) return;
     FusedRow r[2];
@@ -487,10 +539,19 @@ int skr_bpr_fused_step(const float* d_p, const float* d_m, const float* d_v, int
                                beta1, beta2, eps, step_t0, k, s, reg, d_loss64, nullptr, stream);
 }
 
-int skr_bpr_fused_step2(const float* d_p, const float* d_m, const float* d_v, int64_t n, float* d_work, int64_t cap,
-                        const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch,
-                        int64_t user_block0, int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2,
-                        float eps, int64_t step_t0, int k, int s, float reg, float* d_loss64, const float* d_pre, void* stream) {
+// workgroups of a step launch (4 096: the grid's cap, wavefronts loop beyond it); the deferred form's row of partials has
+// BPR_WAVES pairs per workgroup
+static int fused_step_wgs(int n_batch) {
+    const int wgs = (n_batch + BPR_WAVES - 1) / BPR_WAVES;
+    return wgs > 256 * 16 ? 256 * 16 : wgs;
+}
+
+// d_loss_part: NULL, the form that adds to d_loss64; else the block's partials, of which step s writes row s
+static int fused_step_launch(const float* d_p, const float* d_m, const float* d_v, int64_t n, float* d_work, int64_t cap,
+                             const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch,
+                             int64_t user_block0, int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2,
+                             float eps, int64_t step_t0, int k, int s, float reg, float* d_loss64, const float* d_pre,
+                             float* d_loss_part, void* stream) {
     SKR_REQUIRE(d_p && d_m && d_v && d_work && d_u && d_i && d_j && d_meta && d_loss64, "skr_bpr_fused_step: NULL argument");
     SKR_REQUIRE(n >= 0 && n_batch >= 0 && cap >= 1 && cap <= (1 << FUSED_SLOT_BITS), "skr_bpr_fused_step: need 1 <= cap <= 2^%d",
                 FUSED_SLOT_BITS);
@@ -499,13 +560,41 @@ int skr_bpr_fused_step2(const float* d_p, const float* d_m, const float* d_v, in
     if (n_batch == 0) return SKR_OK;
     const AdamBlockArgs& a = fused_block_args(lr, beta1, beta2, eps, step_t0, k);
     static const int dbg = [] { const char* e = getenv("SKR_FUSED_DBG"); return e ? atoi(e) : 0; }();
-    int blocks = (n_batch + BPR_WAVES - 1) / BPR_WAVES;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(bpr_fused_step_kernel, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_u, d_i, d_j, d_meta,
-                       n_batch, s, dbg, SKR_LOSS_SLOTS, d_p, d_m, d_v, n, fused_work(d_work, cap), user_block0, item_block0,
-                       bias_block0, a, reg, d_loss64, d_pre);
+    const int blocks = fused_step_wgs(n_batch);
+    if (d_loss_part)
+        hipLaunchKernelGGL(bpr_fused_step_kernel<float*>, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_u, d_i, d_j,
+                           d_meta, n_batch, s, dbg, SKR_LOSS_SLOTS, d_p, d_m, d_v, n, fused_work(d_work, cap), user_block0, item_block0,
+                           bias_block0, a, reg, d_loss64, d_pre, d_loss_part + static_cast<int64_t>(s) * blocks * (2 * BPR_WAVES));
+    else
+        hipLaunchKernelGGL(bpr_fused_step_kernel<>, dim3(blocks), dim3(BPR_WAVES * 64), 0, skr::as_stream(stream), d_u, d_i, d_j, d_meta,
+                           n_batch, s, dbg, SKR_LOSS_SLOTS, d_p, d_m, d_v, n, fused_work(d_work, cap), user_block0, item_block0,
+                           bias_block0, a, reg, d_loss64, d_pre);
     SKR_LAUNCH_CHECK();
     return SKR_OK;
+}
+
+int skr_bpr_fused_step2(const float* d_p, const float* d_m, const float* d_v, int64_t n, float* d_work, int64_t cap,
+                        const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch,
+                        int64_t user_block0, int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2,
+                        float eps, int64_t step_t0, int k, int s, float reg, float* d_loss64, const float* d_pre, void* stream) {
+    return fused_step_launch(d_p, d_m, d_v, n, d_work, cap, d_u, d_i, d_j, d_meta, n_batch, user_block0, item_block0, bias_block0, lr,
+                             beta1, beta2, eps, step_t0, k, s, reg, d_loss64, d_pre, nullptr, stream);
+}
+
+int64_t skr_bpr_fused_loss_part_floats(int n_batch, int k) {
+    if (n_batch <= 0 || k <= 0) return 0;
+    return static_cast<int64_t>(k) * (2 * BPR_WAVES) * fused_step_wgs(n_batch);
+}
+
+int skr_bpr_fused_step3(const float* d_p, const float* d_m, const float* d_v, int64_t n, float* d_work, int64_t cap,
+                        const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch,
+                        int64_t user_block0, int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2,
+                        float eps, int64_t step_t0, int k, int s, float reg, float* d_loss64, const float* d_pre,
+                        float* d_loss_part, void* stream) {
+    SKR_REQUIRE(d_loss_part, "skr_bpr_fused_step3: NULL argument");
+    SKR_REQUIRE((reinterpret_cast<uintptr_t>(d_loss_part) & 7) == 0, "skr_bpr_fused_step3: d_loss_part must be 8-byte aligned");
+    return fused_step_launch(d_p, d_m, d_v, n, d_work, cap, d_u, d_i, d_j, d_meta, n_batch, user_block0, item_block0, bias_block0, lr,
+                             beta1, beta2, eps, step_t0, k, s, reg, d_loss64, d_pre, d_loss_part, stream);
 }
 
 int skr_bpr_fused_plan(const int32_t* d_u, const int32_t* d_i, const int32_t* d_j, int n_batch, int k, int64_t user_block0,
@@ -564,18 +653,42 @@ int skr_bpr_fused_pre(const float* d_p, const float* d_m, const float* d_v, int6
     return SKR_OK;
 }
 
-int skr_bpr_fused_end(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_slot_block,
-                      const int32_t* d_slot_fin, const int32_t* d_n_slots, float lr, float beta1, float beta2, float eps,
-                      int64_t step_t0, int k, const int32_t* d_tag_next, int32_t tag_next_value, int which, void* stream) {
+// fold_wgs > 0: the launch also folds the block's deferred loss words (part_wgs: the workgroups of its step launches)
+static int fused_end_launch(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_slot_block,
+                            const int32_t* d_slot_fin, const int32_t* d_n_slots, float lr, float beta1, float beta2, float eps,
+                            int64_t step_t0, int k, const int32_t* d_tag_next, int32_t tag_next_value, int which, int fold_wgs,
+                            int part_wgs, const float* d_loss_part, float* d_loss64, int64_t loss_stride_floats, void* stream) {
     SKR_REQUIRE(d_p && d_m && d_v && d_work && d_slot_block && d_slot_fin && d_n_slots, "skr_bpr_fused_end: NULL argument");
     SKR_REQUIRE(n >= 0 && cap >= 1 && cap <= (1 << FUSED_SLOT_BITS), "skr_bpr_fused_end: need 1 <= cap <= 2^%d", FUSED_SLOT_BITS);
     SKR_REQUIRE(step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "skr_bpr_fused_end: need 1 <= k <= %d", AB_KMAX);
     SKR_REQUIRE(which >= 0 && which <= 2 && (which == 0 || d_tag_next), "skr_bpr_fused_end: which must be 0, or 1 / 2 with the next block's tags");
     const AdamBlockArgs& a = fused_block_args(lr, beta1, beta2, eps, step_t0, k);
-    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>((cap + 7) / 8)), dim3(256), 0, skr::as_stream(stream), d_n_slots,
-                       d_slot_block, d_slot_fin, d_tag_next, tag_next_value, which, n, d_p, d_m, d_v, fused_work(d_work, cap), a);
+    hipLaunchKernelGGL(bpr_fused_end_kernel, dim3(static_cast<unsigned>(fold_wgs + (cap + 7) / 8)), dim3(256), 0, skr::as_stream(stream),
+                       d_n_slots, d_slot_block, d_slot_fin, d_tag_next, tag_next_value, which, n, d_p, d_m, d_v, fused_work(d_work, cap), a,
+                       fold_wgs, part_wgs, d_loss_part, d_loss64, loss_stride_floats);
     SKR_LAUNCH_CHECK();
     return SKR_OK;
+}
+
+int skr_bpr_fused_end(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_slot_block,
+                      const int32_t* d_slot_fin, const int32_t* d_n_slots, float lr, float beta1, float beta2, float eps,
+                      int64_t step_t0, int k, const int32_t* d_tag_next, int32_t tag_next_value, int which, void* stream) {
+    return fused_end_launch(d_p, d_m, d_v, n, d_work, cap, d_slot_block, d_slot_fin, d_n_slots, lr, beta1, beta2, eps, step_t0, k,
+                            d_tag_next, tag_next_value, which, 0, 0, nullptr, nullptr, 0, stream);
+}
+
+int skr_bpr_fused_end3(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_slot_block,
+                       const int32_t* d_slot_fin, const int32_t* d_n_slots, float lr, float beta1, float beta2, float eps,
+                       int64_t step_t0, int k, const int32_t* d_tag_next, int32_t tag_next_value, int which,
+                       const float* d_loss_part, float* d_loss64, int64_t loss_stride_floats, int n_batch, void* stream) {
+    SKR_REQUIRE(d_loss_part && d_loss64, "skr_bpr_fused_end3: NULL argument");
+    SKR_REQUIRE(loss_stride_floats >= 0 && n_batch >= 0, "skr_bpr_fused_end3: bad shape");
+    // one wavefront per step, four to a workgroup; the which = 2 launch (the leftovers, on another stream) folds nothing, and
+    // an empty batch launched no step
+    const bool fold = which != 2 && n_batch > 0 && k >= 1;
+    return fused_end_launch(d_p, d_m, d_v, n, d_work, cap, d_slot_block, d_slot_fin, d_n_slots, lr, beta1, beta2, eps, step_t0, k,
+                            d_tag_next, tag_next_value, which, fold ? (k + 3) / 4 : 0, fused_step_wgs(n_batch), d_loss_part, d_loss64,
+                            loss_stride_floats, stream);
 }
 
 int skr_bpr_fused_block(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_u,
@@ -605,6 +718,26 @@ int skr_bpr_fused_block2(float* d_p, float* d_m, float* d_v, int64_t n, float* d
     }
     return skr_bpr_fused_end(d_p, d_m, d_v, n, d_work, cap, d_slot_block, d_slot_fin, d_n_slots, lr, beta1, beta2, eps, step_t0, k,
                              d_tag_next, tag_next_value, d_tag_next ? 1 : 0, stream);
+}
+
+int skr_bpr_fused_block3(float* d_p, float* d_m, float* d_v, int64_t n, float* d_work, int64_t cap, const int32_t* d_u,
+                         const int32_t* d_i, const int32_t* d_j, const int32_t* d_meta, int n_batch, int64_t user_block0,
+                         int64_t item_block0, int64_t bias_block0, float lr, float beta1, float beta2, float eps, int64_t step_t0,
+                         int k, float reg, float* d_loss64, int64_t loss_stride_floats, const int32_t* d_slot_block,
+                         const int32_t* d_slot_fin, const int32_t* d_n_slots, const int32_t* d_tag_next, int32_t tag_next_value,
+                         const float* d_pre, float* d_loss_part, void* stream) {
+    SKR_REQUIRE(k >= 1 && k <= AB_KMAX && n_batch >= 0 && loss_stride_floats >= 0, "skr_bpr_fused_block3: bad shape");
+    SKR_REQUIRE(d_loss_part && d_loss64, "skr_bpr_fused_block3: NULL argument");
+    for (int s = 0; s < k; ++s) {
+        const int64_t o = static_cast<int64_t>(s) * n_batch;
+        const int rc = skr_bpr_fused_step3(d_p, d_m, d_v, n, d_work, cap, d_u + o, d_i + o, d_j + o, d_meta + 5 * o, n_batch, user_block0,
+                                           item_block0, bias_block0, lr, beta1, beta2, eps, step_t0, k, s, reg, d_loss64, d_pre,
+                                           d_loss_part, stream);
+        if (rc != SKR_OK) return rc;
+    }
+    return skr_bpr_fused_end3(d_p, d_m, d_v, n, d_work, cap, d_slot_block, d_slot_fin, d_n_slots, lr, beta1, beta2, eps, step_t0, k,
+                              d_tag_next, tag_next_value, d_tag_next ? 1 : 0, d_loss_part, d_loss64, loss_stride_floats, n_batch,
+                              stream);
 }
 
 }  // extern "C"

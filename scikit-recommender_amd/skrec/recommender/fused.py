@@ -90,7 +90,10 @@ class FusedBlocks(object):
     The split write-back is OFF by default (``SKR_FUSED_SPLIT_END=1`` turns it on): it takes 50 of the write-back's 63 us
     off the current stream, but the side stream -- whose cold pass (0.54 ms of a 0.70 ms block in the steady state of an
     epoch) is the other bound -- gets them, and the next cold pass starts that much later: an epoch took 1.19 s instead of
-    1.09 s.  Without it the whole write-back runs on the current stream after the block's last step."""
+    1.09 s.  Without it the whole write-back runs on the current stream after the block's last step.
+
+    The loss words of a block are written by its end launch on the current stream: the step launches store their sums per
+    wavefront into ``loss_part`` and the end launch folds them (``SKR_FUSED_LOSS_DEFER=0``: every step launch adds its own)."""
 
     def __init__(self, opt, user_block0, item_block0, bias_block0, reg):
         import os
@@ -108,6 +111,11 @@ class FusedBlocks(object):
         # side stream behind the previous block's cold pass, for the rows that block did not touch (skr_bpr_fused_pre);
         # SKR_FUSED_PRE=0: the step launch that first names a row catches it up itself
         self.pre_advance = os.environ.get("SKR_FUSED_PRE", "1") != "0"
+        # the step launches store their loss sums per wavefront into `loss_part`, and the block's end launch folds them into
+        # the caller's loss words (skr_bpr_fused_step3 / _end3 / _block3); SKR_FUSED_LOSS_DEFER=0: every step launch adds
+        # to the loss words itself (_step2 / _end / _block2)
+        self.loss_defer = os.environ.get("SKR_FUSED_LOSS_DEFER", "1") != "0"
+        self.loss_part = None
         self._ev_pre = [torch.cuda.Event(), torch.cuda.Event()]
         self._plan_stream = torch.cuda.Stream(device=dev)
         self._ev_plan = [torch.cuda.Event(), torch.cuda.Event()]
@@ -132,6 +140,13 @@ class FusedBlocks(object):
             self.n_slots = torch.zeros((2, 1), dtype=torch.int32, device=dev)
             self.pre = torch.zeros((2, 3 * cap * 64), dtype=torch.float32, device=dev) if self.pre_advance else None
             self._used = [False, False]
+        # the deferred loss sums, a tensor of its own (the workspace's gradient planes stay all-zero between blocks).  One
+        # buffer: its only reader, a block's end launch, sits behind all of its writers on the current stream and in front
+        # of the next block's.  Never cleared: the fold reads only what the block's own step launches wrote
+        need = int(_hip.lib().skr_bpr_fused_loss_part_floats(bsz, k)) if self.loss_defer else 0
+        if need > (0 if self.loss_part is None else self.loss_part.numel()):
+            torch.cuda.synchronize(self.opt.flat.device)
+            self.loss_part = torch.empty(need, dtype=torch.float32, device=self.opt.flat.device)
 
     def _plan(self, q, pu, pi, pj, k, bsz, serial, prev=None, inline=False):
         """words, slot tables and hot-block tags of one block into set q, on the planning stream; ``prev`` = (tags, value) of
@@ -209,6 +224,7 @@ class FusedBlocks(object):
                 cur.wait_event(self._ev_plan[q ^ 1])                 # the next block's tags decide what is written back where
             ptag = self.tags[q ^ 1].data_ptr() if split else None
             pw = self.work[q if self.split_end else 0].data_ptr()
+            defer, ppart = self.loss_defer, (self.loss_part.data_ptr() if self.loss_defer else None)
             # measurement hook (bench.py): `block_timing` receives (start, steps done, end done, k) -- HIP events on the current
             # stream around the block's k step launches and around its end launch -- with event triples from `block_event_pool`
             # (made beforehand), after `block_timing_skip` unbracketed blocks; no pool or an empty one: no bracket.  A
@@ -218,7 +234,12 @@ class FusedBlocks(object):
                 self.block_timing_skip -= 1
                 bt = None
             trip = self.block_event_pool.pop() if (bt is not None and getattr(self, "block_event_pool", None)) else None
-            if trip is None:
+            if trip is None and defer:
+                rc = L.skr_bpr_fused_block3(pp, pm, pv, n_par, pw, cap, pu + o, pi + o, pj + o, self.meta[q].data_ptr(), bsz, u0, i0, b0,
+                                            lr, b1, b2, eps, t0, k, reg, ploss + blk * k * loss_stride_bytes, loss_stride_bytes // 4,
+                                            self.slot_block[q].data_ptr(), self.slot_fin[q].data_ptr(), self.n_slots[q].data_ptr(),
+                                            ptag, serial0 + blk + 1, ppre, ppart, st)
+            elif trip is None:
                 rc = L.skr_bpr_fused_block2(pp, pm, pv, n_par, pw, cap, pu + o, pi + o, pj + o, self.meta[q].data_ptr(), bsz, u0, i0, b0,
                                             lr, b1, b2, eps, t0, k, reg, ploss + blk * k * loss_stride_bytes, loss_stride_bytes // 4,
                                             self.slot_block[q].data_ptr(), self.slot_fin[q].data_ptr(), self.n_slots[q].data_ptr(),
@@ -228,13 +249,24 @@ class FusedBlocks(object):
                 trip[0].record(cur)
                 for s_ in range(k):
                     os_ = o + 4 * s_ * bsz
-                    rc |= L.skr_bpr_fused_step2(pp, pm, pv, n_par, pw, cap, pu + os_, pi + os_, pj + os_, pmeta + 20 * s_ * bsz, bsz, u0,
-                                                i0, b0, lr, b1, b2, eps, t0, k, s_, reg, ploss + (blk * k + s_) * loss_stride_bytes,
-                                                ppre, st)
+                    if defer:
+                        rc |= L.skr_bpr_fused_step3(pp, pm, pv, n_par, pw, cap, pu + os_, pi + os_, pj + os_, pmeta + 20 * s_ * bsz, bsz,
+                                                    u0, i0, b0, lr, b1, b2, eps, t0, k, s_, reg, ploss + blk * k * loss_stride_bytes,
+                                                    ppre, ppart, st)
+                    else:
+                        rc |= L.skr_bpr_fused_step2(pp, pm, pv, n_par, pw, cap, pu + os_, pi + os_, pj + os_, pmeta + 20 * s_ * bsz, bsz,
+                                                    u0, i0, b0, lr, b1, b2, eps, t0, k, s_, reg,
+                                                    ploss + (blk * k + s_) * loss_stride_bytes, ppre, st)
                 trip[1].record(cur)
-                rc |= L.skr_bpr_fused_end(pp, pm, pv, n_par, pw, cap, self.slot_block[q].data_ptr(), self.slot_fin[q].data_ptr(),
-                                          self.n_slots[q].data_ptr(), lr, b1, b2, eps, t0, k, ptag, serial0 + blk + 1,
-                                          1 if ptag else 0, st)
+                if defer:
+                    rc |= L.skr_bpr_fused_end3(pp, pm, pv, n_par, pw, cap, self.slot_block[q].data_ptr(), self.slot_fin[q].data_ptr(),
+                                               self.n_slots[q].data_ptr(), lr, b1, b2, eps, t0, k, ptag, serial0 + blk + 1,
+                                               1 if ptag else 0, ppart, ploss + blk * k * loss_stride_bytes, loss_stride_bytes // 4,
+                                               bsz, st)
+                else:
+                    rc |= L.skr_bpr_fused_end(pp, pm, pv, n_par, pw, cap, self.slot_block[q].data_ptr(), self.slot_fin[q].data_ptr(),
+                                              self.n_slots[q].data_ptr(), lr, b1, b2, eps, t0, k, ptag, serial0 + blk + 1,
+                                              1 if ptag else 0, st)
                 trip[2].record(cur)
                 bt.append((trip[0], trip[1], trip[2], k))
             self._ev_block.record(cur)

@@ -1,6 +1,8 @@
 """Where the time of skr_bpr_fused_step goes: k launches of a block timed with HIP events, nothing beside them.
 SKR_FUSED_DBG (one-wavefront kernel only; results are then wrong, timing only): 1 no catch-up arithmetic, 2 no gradient
-atomics, 4 no owner stores, 8 no loss atomics.  SKR_FUSED_STATS=1: prints the census of the evaluations (skr_fused_census;
+atomics, 4 no owner stores, 8 no loss atomics / no store of the loss partials, 32 the partials' store write-through instead of
+plain.  The step launches are the deferred-loss form (skr_bpr_fused_step3 / _end3: partials per wavefront, folded by
+the end launch); SKR_FUSED_LOSS_DEFER=0 times the form that adds to the loss words itself.  SKR_FUSED_STATS=1: prints the census of the evaluations (skr_fused_census;
 its counters slow the launches -- not for timing).
 --per-step: an event pair around EACH of the k step launches of a block, and the mean launch time per step index 0 .. k - 1
 (the events between the launches cost time themselves: compare builds step by step, not with the figure without the option);
@@ -38,6 +40,8 @@ ns = torch.zeros(1, dtype=torch.int32, device=dev)
 nfb = (n_par + 63) // 64
 scratch = torch.zeros(28 * nfb // 8 + 1, dtype=torch.int64, device=dev)
 loss = torch.zeros(64, device=dev)
+defer = os.environ.get("SKR_FUSED_LOSS_DEFER", "1") != "0"
+part = torch.empty(int(L.skr_bpr_fused_loss_part_floats(b, k)), device=dev)
 ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
 t_plan, t_steps, t_end, t_each = [], [], [], []
 t = 0
@@ -54,14 +58,23 @@ for blk in range(n_blocks):
         if per_step:
             es[s].record()
         q = o + 4 * s * b
-        rc |= L.skr_bpr_fused_step(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, u.data_ptr() + q,
-                                   i.data_ptr() + q, j.data_ptr() + q, meta.data_ptr() + 20 * s * b, b, 0, nU, nU + nI, 1e-3, 0.9, 0.999,
-                                   1e-8, t, k, s, 1e-3, loss.data_ptr(), st)
+        if defer:
+            rc |= L.skr_bpr_fused_step3(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, u.data_ptr() + q,
+                                        i.data_ptr() + q, j.data_ptr() + q, meta.data_ptr() + 20 * s * b, b, 0, nU, nU + nI, 1e-3, 0.9,
+                                        0.999, 1e-8, t, k, s, 1e-3, loss.data_ptr(), None, part.data_ptr(), st)
+        else:
+            rc |= L.skr_bpr_fused_step(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, u.data_ptr() + q,
+                                       i.data_ptr() + q, j.data_ptr() + q, meta.data_ptr() + 20 * s * b, b, 0, nU, nU + nI, 1e-3, 0.9,
+                                       0.999, 1e-8, t, k, s, 1e-3, loss.data_ptr(), st)
     if per_step:
         es[k].record()
     e[2].record()
-    rc |= L.skr_bpr_fused_end(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, sb.data_ptr(), sf.data_ptr(),
-                              ns.data_ptr(), 1e-3, 0.9, 0.999, 1e-8, t, k, None, 0, 0, st)
+    if defer:
+        rc |= L.skr_bpr_fused_end3(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, sb.data_ptr(), sf.data_ptr(),
+                                   ns.data_ptr(), 1e-3, 0.9, 0.999, 1e-8, t, k, None, 0, 0, part.data_ptr(), loss.data_ptr(), 0, b, st)
+    else:
+        rc |= L.skr_bpr_fused_end(flat.data_ptr(), m1.data_ptr(), m2.data_ptr(), n_par, work.data_ptr(), cap, sb.data_ptr(), sf.data_ptr(),
+                                  ns.data_ptr(), 1e-3, 0.9, 0.999, 1e-8, t, k, None, 0, 0, st)
     e[3].record()
     _hip.check(rc)
     t += k
@@ -70,7 +83,7 @@ for blk in range(n_blocks):
     if per_step:
         t_each.append([es[s].elapsed_time(es[s + 1]) for s in range(k)])
 h = n_blocks // 2
-print(f"k={k} dbg={os.environ.get('SKR_FUSED_DBG', '0')}: "
+print(f"k={k} dbg={os.environ.get('SKR_FUSED_DBG', '0')} loss {'deferred (step3 / end3)' if defer else 'added per step (step / end)'}: "
       f"plan {np.mean(t_plan[h:]) * 1e3:.1f} us/block, steps {np.mean(t_steps[h:]) * 1e3 / k:.2f} us/step, end {np.mean(t_end[h:]) * 1e3:.1f} us/block"
       f"  (slots {int(ns)})")
 if per_step:
