@@ -1307,6 +1307,109 @@ int skr_freedom_step(const skr_freedom_step_args* args, void* stream);
 #define SKR_FREEDOM_GROUPS 7
 int skr_freedom_step_timed(const skr_freedom_step_args* args, void* stream, float* h_ms);
 
+/* ============================================================================================
+ * M -- MGCN, multi-view graph convolution with a purifier and a fuser (csrc/mgcn.hip)
+ * replaces: _MGCN.forward / calculate_loss / full_sort_predict and MGCN.fit's step (recommender/MGCN.py:250-361, 388-396) at
+ * embed_dim <= 64, sparse branch.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables,
+ * user rows first.  Feature tables and projection blocks are section J's: [n_items][feat_ld] and W [64][feat_ld] | b [64];
+ * modality 0 is the image block, 1 the text block, and both are required.  A gate block is W [64 out][64 in] | b [64]
+ * (SKR_MGCN_GATE_FLOATS), zero beyond dim.  The query block is the gate block of query_common.0 followed by q [64]
+ * (query_common.2.weight): SKR_MGCN_QUERY_FLOATS floats.
+ * DEVIATION from "every product on v_mfma_f32_16x16x4_f32": operands are fp32 in mfma_tile.h's layouts everywhere, but only the
+ * fuser's four products run on that instruction.  The projections forward and backward, the gate and rows-times-W products,
+ * InfoNCE's two products and the reductions over rows behind the weight gradients add the same operands on
+ * v_mfma_f64_16x16x4_f64 (mfma_tile.h's float64 helpers; half the matrix rate) and round once.  With fp32 accumulators the
+ * golden replay of the reference missed its bound in one tensor through one element whose first gradient lies beside Adam's eps
+ * (MGCN).  No floating-point atomic, every sum in a fixed order: all entries are bit-reproducible.
+ * ========================================================================================== */
+#define SKR_MGCN_MAX_BATCH 2048
+#define SKR_MGCN_MAX_LAYERS 4
+#define SKR_MGCN_MAX_FEAT 4096
+#define SKR_MGCN_GATE_FLOATS (64 * 64 + 64)
+#define SKR_MGCN_QUERY_FLOATS (64 * 64 + 64 + 64)
+/* d_Y[r, :] = X[r, :feat_dim] W^T + b for ALL n_rows rows (nn.Linear on the whole nn.Embedding, MGCN.py:251-254): d_X
+ * [n_rows][feat_ld], d_trs = W [64][feat_ld] then b [64], d_Y [n_rows][64].  skr_bm3_project's tile without the gather (that
+ * entry takes at most SKR_BM3_MAX_BATCH rows), summed in float64. */
+int skr_mgcn_project(const float* d_X, int n_rows, int feat_dim, int feat_ld, const float* d_trs, float* d_Y, void* stream);
+/* The rows of one row block of the reductions over rows below (a multiple of 16, 256 up to 16 384 rows): a reduction over
+ * n_rows rows adds ceil(n_rows / block) partial sums in block order. */
+int skr_mgcn_row_block(int n_rows);
+/* The backward of skr_mgcn_project given d_dF [n_rows][64]: d_dtrs = dW [64][feat_ld] = dF^T X, then db [64] = the column sums
+ * of dF; d_dX [n_rows][feat_ld] = dF W.  EVERY element of d_dtrs and d_dX is WRITTEN.  dW and db are reductions over the rows:
+ * per-row-block partial sums in d_work, added in block order.  d_work: skr_mgcn_project_bwd_workspace bytes, 16-byte aligned. */
+size_t skr_mgcn_project_bwd_workspace(int n_rows, int feat_ld);
+int skr_mgcn_project_bwd(const float* d_dF, const float* d_X, int n_rows, int feat_dim, int feat_ld, const float* d_trs,
+                         float* d_dtrs, float* d_dX, void* d_work, size_t work_bytes, void* stream);
+/* The purifier (MGCN.py:257-258): d_g = sigmoid(F Wg^T + bg) (zero beyond dim), d_X = E * g, all [n_rows][64]; the gate lies
+ * in LDS, a wavefront owns a 16-row tile. */
+int skr_mgcn_purify(const float* d_F, const float* d_E, const float* d_gate, int n_rows, int dim, float* d_g, float* d_X,
+                    void* stream);
+/* Its backward given d_dX: d_dE += dX g (ACCUMULATED); dz = dX E g (1 - g); d_dF = dz Wg (WRITTEN); d_dgate = dz^T F | the
+ * column sums of dz (WRITTEN, ordered partial sums as above).  d_work: skr_mgcn_purify_bwd_workspace bytes. */
+size_t skr_mgcn_purify_bwd_workspace(int n_rows);
+int skr_mgcn_purify_bwd(const float* d_dX, const float* d_E, const float* d_g, const float* d_F, const float* d_gate, int n_rows,
+                        float* d_dE, float* d_dF, float* d_dgate, void* d_work, size_t work_bytes, void* stream);
+/* The fuser (MGCN.py:291-305), row-local over n_rows rows of M, Zv, Zt [n_rows][64], forward only:
+ *   a_m = q . tanh(Wc z_m + bc); (w_v, w_t) = softmax(a_v, a_t); c = w_v z_v + w_t z_t; s_m = z_m - c;
+ *   p_v = sigmoid(W_ip M + b_ip), p_t = sigmoid(W_tp M + b_tp); d_out = M + (p_v s_v + p_t s_t + c) / 3.
+ * d_query: SKR_MGCN_QUERY_FLOATS floats; d_pref_v / d_pref_t: gate blocks.  d_w [n_rows][2] receives (w_v, w_t), or NULL. */
+int skr_mgcn_fuse(const float* d_M, const float* d_Zv, const float* d_Zt, const float* d_query, const float* d_pref_v,
+                  const float* d_pref_t, int64_t n_rows, int dim, float* d_out, float* d_w, void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   F_m = skr_mgcn_project of modality m; X_m = S_m^n_layers (E_items * g_m) (skr_mgcn_purify, n_layers runs of plan_s[m]);
+ *   Z_m = [R X_m; X_m] (one run of plan_a); M = mean_{k=0..n_ui_layers} A-hat^k params (2 n_ui_layers runs);
+ *   the fuser at the batch's 3 n rows (users, n_users + pos, n_users + neg) only -> out, side;
+ *   loss[0] = -mean logsigmoid(<o_u, o_i - o_j>), loss[1] = reg (|o_u|^2 + |o_i|^2 + |o_j|^2) / (2 n),
+ *   loss[2] = cl_loss * (InfoNCE(side[pos], M[pos]) + InfoNCE(side[users], M[users])), InfoNCE(a, b) = mean_r [-<a_r, b_r> / 0.2
+ *   + log sum_k exp(<a_r, b_k> / 0.2)] over rows normalised with eps 1e-12, all n columns, no [n, n] array in HBM;
+ *   loss[3] = their sum                                                                                     WRITTEN
+ *   grad (the rows), trs_grad, feat_grad, gate_grad, query_grad, prefer_grad: the gradient of loss[3], every element WRITTEN.
+ * A batch row with an id out of range contributes nothing (n stays the divisor).  With n == 0 nothing is launched and NOTHING is
+ * written, neither loss nor a gradient (the arguments are still checked).  Bit-reproducible. */
+typedef struct skr_mgcn_step_args {
+    const skr_spmm_plan* plan_a;       /* R [n_users, n_items], D^-1/2 A D^-1/2 */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    const skr_spmm_plan* plan_s[2];    /* S_m [n_items, n_items]; may be NULL if n_layers == 0 */
+    const skr_spmm_plan* plan_st[2];   /* their transposes */
+    int32_t n_users, n_items, dim, n_ui_layers, n_layers, n;
+    int32_t feat_dim[2];
+    int32_t feat_ld[2];
+    const float* params;               /* [n_users + n_items, 64] */
+    const float* trs[2];               /* W [64][feat_ld], then b [64] */
+    const float* feat[2];              /* [n_items][feat_ld] */
+    const float* gate[2];              /* gate_v, gate_t */
+    const float* query;                /* query_common: Wc | bc | q */
+    const float* prefer[2];            /* gate_image_prefer, gate_text_prefer */
+    const int32_t* users;              /* [n] */
+    const int32_t* pos;                /* [n] */
+    const int32_t* neg;                /* [n] */
+    float reg, cl_loss;
+    float* F[2];                       /* [n_items, 64] the projected features */
+    float* gate_out[2];                /* [n_items, 64] g_m */
+    float* Z[2];                       /* [n_users + n_items, 64] */
+    float* M;                          /* [n_users + n_items, 64] */
+    float* G[3];                       /* scratch, [n_users + n_items, 64] each: dM, dZv, dZt */
+    float* ping[2];                    /* scratch, [n_users + n_items, 64] each */
+    float* grad;                       /* [n_users + n_items, 64] */
+    float* trs_grad[2];
+    float* feat_grad[2];
+    float* gate_grad[2];
+    float* query_grad;
+    float* prefer_grad[2];
+    float* loss;                       /* [4] */
+    void* work;                        /* skr_mgcn_workspace bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_mgcn_step_args;
+size_t skr_mgcn_workspace(int n, int n_items, int feat_ld_max);
+int skr_mgcn_step(const skr_mgcn_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_MGCN_GROUPS launch groups (projections; user-item plan runs; purifier,
+ * item-graph runs and R; fuser, BPR, InfoNCE and loss at the batch; the batch backward with its weight gradients, rank and
+ * seg_add; the mean's backward chain; the image side's R^T and S^T runs with its purifier and projection backward; the text
+ * side's): h_ms[k] (host) = milliseconds of group k; synchronises the stream (timing tools). */
+#define SKR_MGCN_GROUPS 8
+int skr_mgcn_step_timed(const skr_mgcn_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
 #include <cstdarg>
 
-#define SKR_ABI_VERSION 16
+#define SKR_ABI_VERSION 17
 
 namespace skr {
 static thread_local std::string g_err;

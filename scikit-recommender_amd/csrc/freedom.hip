@@ -444,7 +444,6 @@ __global__ __launch_bounds__(256) void fd_add_kernel(float* dst, const float* sr
 // of the step -- up to 2 048 terms of either sign that nearly cancel -- and an element that starts with a gradient beside
 // Adam's eps has its fp32 rounding magnified by up to lr / eps in the first update.  In float64 only the terms' own
 // rounding is left; the sum is rounded to fp32 once.
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 __global__ __launch_bounds__(HW * 64) void fd_trs_wgrad_kernel(const float* __restrict__ X, int n_rows, int ld, const int32_t* __restrict__ pos,
                                                                const int32_t* __restrict__ neg, int n, const float* __restrict__ dY,
                                                                float* __restrict__ dW) {

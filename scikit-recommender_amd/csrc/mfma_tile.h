@@ -157,4 +157,51 @@ __device__ __forceinline__ void logits_tile(f32x4 acc[4], const float a[16], con
     }
 }
 
+// ---- float64 accumulators ------------------------------------------------------------------------
+// The same fp32 operands in the same lanes, added on v_mfma_f64_16x16x4_f64 and rounded once by the caller: for the sums whose
+// fp32 noise an optimiser magnifies (freedom.hip's weight gradient, mgcn.hip's products).  The lane's four results are the rows
+// g + 4 rr -- not 4 g + rr -- of column 16 nb + r.
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+__device__ __forceinline__ void zero_acc64(f64x4 acc[4]) {
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = f64x4{0.0, 0.0, 0.0, 0.0};
+}
+__device__ __forceinline__ f64x4 mfma64(float a, float b, f64x4 c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(static_cast<double>(a), static_cast<double>(b), c, 0, 0, 0);
+}
+__device__ __forceinline__ double sum16d(double v) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// tile_product of mfma_tile.h with float64 accumulators: acc[nb][rr] += sum_k A[g + 4 rr][k] * B[16 nb + r][k]
+template <int LDS, int K>
+__device__ __forceinline__ void tile_product64(f64x4 acc[4], const float (&a)[K], const float* __restrict__ sB, int r, int g) {
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {
+        float4 w[4];
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) w[nb] = *reinterpret_cast<const float4*>(sB + (nb * 16 + r) * LDS + K * g + 4 * q);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(a[4 * q + 0], w[nb].x, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(a[4 * q + 1], w[nb].y, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(a[4 * q + 2], w[nb].z, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(a[4 * q + 3], w[nb].w, acc[nb]);
+    }
+}
+// logits_tile of mfma_tile.h with float64 accumulators: acc[nb][rr] = <Q[row g + 4 rr], W[row 16 nb + r]>
+template <int LDS>
+__device__ __forceinline__ void logits_tile64(f64x4 acc[4], const float a[16], const float* __restrict__ sW, int r, int g) {
+    zero_acc64(acc);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(a[kk], sW[(nb * 16 + r) * LDS + 4 * kk + g], acc[nb]);
+    }
+}
+
 }  // namespace skr

@@ -168,6 +168,17 @@ SIGNATURES = {
     "skr_freedom_workspace": (sz, [i32]),
     "skr_freedom_step": (i32, [vp, vp]),
     "skr_freedom_step_timed": (i32, [vp, vp, vp]),
+    "skr_mgcn_project": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "skr_mgcn_row_block": (i32, [i32]),
+    "skr_mgcn_project_bwd_workspace": (sz, [i32, i32]),
+    "skr_mgcn_project_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "skr_mgcn_purify": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "skr_mgcn_purify_bwd_workspace": (sz, [i32]),
+    "skr_mgcn_purify_bwd": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "skr_mgcn_fuse": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "skr_mgcn_workspace": (sz, [i32, i32, i32]),
+    "skr_mgcn_step": (i32, [vp, vp]),
+    "skr_mgcn_step_timed": (i32, [vp, vp, vp]),
 }
 
 
@@ -228,6 +239,18 @@ class FreedomStepArgs(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+class MGCNStepArgs(C.Structure):
+    """skr_mgcn_step_args (include/skrec_hip.h): the plans of the three graphs, the parameter blocks, the batch, the forward's
+    tables and the scratch of one MGCN step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("plan_s", vp * 2), ("plan_st", vp * 2), ("n_users", C.c_int32), ("n_items", C.c_int32),
+                ("dim", C.c_int32), ("n_ui_layers", C.c_int32), ("n_layers", C.c_int32), ("n", C.c_int32), ("feat_dim", C.c_int32 * 2),
+                ("feat_ld", C.c_int32 * 2), ("params", vp), ("trs", vp * 2), ("feat", vp * 2), ("gate", vp * 2), ("query", vp),
+                ("prefer", vp * 2), ("users", vp), ("pos", vp), ("neg", vp), ("reg", C.c_float), ("cl_loss", C.c_float), ("F", vp * 2),
+                ("gate_out", vp * 2), ("Z", vp * 2), ("M", vp), ("G", vp * 3), ("ping", vp * 2), ("grad", vp), ("trs_grad", vp * 2),
+                ("feat_grad", vp * 2), ("gate_grad", vp * 2), ("query_grad", vp), ("prefer_grad", vp * 2), ("loss", vp), ("work", vp),
+                ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -247,6 +270,8 @@ SKR_BM3_DRAW_USER, SKR_BM3_DRAW_ITEM, SKR_BM3_DRAW_TEXT, SKR_BM3_DRAW_IMAGE = 0,
 SKR_FREEDOM_MAX_BATCH, SKR_FREEDOM_MAX_LAYERS, SKR_FREEDOM_MAX_FEAT, SKR_FREEDOM_GROUPS = 2048, 4, 4096, 7   # skr_freedom_step limits
 SKR_FREEDOM_MAX_NNZ = 2 ** 31 - 1         # skr_freedom_keys / _select / _pruned_csr: entries of the train matrix
 SKR_KNN_MAX_K = 32                       # skr_knn_topk: neighbours per row
+SKR_MGCN_MAX_BATCH, SKR_MGCN_MAX_LAYERS, SKR_MGCN_MAX_FEAT, SKR_MGCN_GROUPS = 2048, 4, 4096, 8   # skr_mgcn_step limits
+SKR_MGCN_GATE_FLOATS, SKR_MGCN_QUERY_FLOATS = 64 * 64 + 64, 64 * 64 + 64 + 64   # a gate block; query_common's W | b | q
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 

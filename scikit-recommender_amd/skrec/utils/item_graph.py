@@ -5,6 +5,9 @@ MGCN start from the same construction).
 ``skr_knn_topk`` (csrc/knn.hip) on the fp32 matrix pipe without ever forming the [I, I] similarity matrix the reference
 builds with ``torch.mm`` + ``torch.topk``.  There is no fallback: without the library or a GPU it raises.
 
+``build_weighted_item_graph`` is MGCN's (and LATTICE's) variant of the host half: one modality, entries weighted by the
+similarities themselves (MGCN.py:67-80, 101-111).
+
 ``build_item_graph`` is the host half, pure torch on whatever device its inputs live on (CPU tensors included): neighbour
 lists -> the reference's normalised, weighted, coalesced graph ``S`` and its transpose, both as CSR triples.  Nothing is
 cached: the reference stores the graph in the data set's cache directory under a name that ignores the features, here it is
@@ -14,7 +17,7 @@ import torch
 
 from skrec import _hip
 
-__all__ = ["knn_topk", "build_item_graph", "check_knn_limits"]
+__all__ = ["knn_topk", "build_item_graph", "build_weighted_item_graph", "check_knn_limits"]
 
 
 def check_knn_limits(knn_k, feat_dim=None, what="feature"):
@@ -108,3 +111,30 @@ def build_item_graph(knn_ids_img, knn_ids_txt, knn_k, weight):
     tkeys = cols * n_items + rows
     order = torch.argsort(tkeys)                # the keys are distinct: any sort gives the one order
     return _csr(ukeys, uvals, n_items), _csr(tkeys[order], uvals[order], n_items)
+
+
+def build_weighted_item_graph(knn_ids, knn_sims):
+    """One modality's graph ``S`` [I, I] of MGCN.py:101-111 (sparse branch, 'sym') from the neighbour lists ``knn_ids``
+    [I, k] and their cosine similarities ``knn_sims`` [I, k]: the entry (i, j) of a kept neighbour is
+    ``deg_i^-0.5 * s_ij * deg_j^-0.5`` with ``deg`` the ROW sums of the kept similarities (inf -> 0), in the reference's fp32
+    operations.  ``S`` is directed, weighted, has exactly k entries per row and is not symmetric.
+
+    Returns ``((rowptr, col, val), (rowptr_t, col_t, val_t))``: ``S`` and ``S^T`` as CSR with ascending columns, rowptr
+    int64, col int32, val float32, on the inputs' device.  Pure torch: it runs on CPU tensors as well."""
+    ids = knn_ids.to(torch.int64)
+    assert ids.dim() == 2 and knn_sims.shape == ids.shape, "build_weighted_item_graph: ids and sims must both be [n_items, k]"
+    n_items = int(ids.shape[0])
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_items):
+        raise ValueError("build_weighted_item_graph: a neighbour id is outside [0, n_items)")
+    rows = torch.arange(n_items, dtype=torch.int64, device=ids.device).unsqueeze(1).expand_as(ids).reshape(-1)
+    cols = ids.reshape(-1)
+    v = knn_sims.to(torch.float32).reshape(-1)
+    deg = torch.zeros(n_items, dtype=torch.float32, device=ids.device).index_add_(0, rows, v)
+    deg_inv_sqrt = deg.pow(-0.5)
+    deg_inv_sqrt.masked_fill_(deg_inv_sqrt == float("inf"), 0)
+    vals = deg_inv_sqrt[rows] * v * deg_inv_sqrt[cols]
+    keys = rows * n_items + cols
+    order = torch.argsort(keys)                 # a row's neighbours are distinct: the keys are, too
+    tkeys = cols * n_items + rows
+    order_t = torch.argsort(tkeys)
+    return _csr(keys[order], vals[order], n_items), _csr(tkeys[order_t], vals[order_t], n_items)
