@@ -1410,6 +1410,94 @@ int skr_mgcn_step(const skr_mgcn_step_args* args, void* stream);
 #define SKR_MGCN_GROUPS 8
 int skr_mgcn_step_timed(const skr_mgcn_step_args* args, void* stream, float* h_ms);
 
+/* ============================================================================================
+ * N -- LATTICE, a learned item graph (csrc/lattice.hip)
+ * replaces: _LATTICE.forward / calculate_loss / full_sort_predict and LATTICE.fit's step (recommender/LATTICE.py:203-302,
+ * 326-337) at embed_dim, feat_embed_dim <= 64 and cf_model in {lightgcn, mf}, without any dense [I, I] matrix.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned.  A neighbour list is [n_items][k] (ids int32, values fp32); the
+ * four lists of a row are, in this order, the learned image list, the learned text list (ids and cosine similarities of
+ * skr_knn_topk on the projected rows) and the frozen image and text lists (columns and values of build_weighted_item_graph's
+ * CSR, k entries per row).  The ids of ONE list are distinct; an id outside [0, n_items) is ignored.  An absent list is NULL.
+ * No floating-point atomic, every sum in a fixed order: every entry point is bit-reproducible.
+ * ============================================================================================ */
+#define SKR_LATTICE_MAX_BATCH 2048
+#define SKR_LATTICE_MAX_LAYERS 4
+#define SKR_LATTICE_CF_LIGHTGCN 0
+#define SKR_LATTICE_CF_MF 1
+/* The mixed graph S = item_adj (LATTICE.py:209-228) as CSR over the union pattern of the up to four lists of a row, columns
+ * ascending, duplicates merged (at most 4 k <= 128 entries per row, merged inside one wavefront):
+ *   L_ij = w[0] s_v,ij + w[1] s_t,ij (a missing term is 0);  r_i = sum_j L_ij;  q_i = r_i^-1/2, 0 where r_i <= 0 (the
+ *   reference gives 0 at r = 0 and NaN below);  S_ij = (1 - lam) (q_i L_ij) q_j + lam (w[0] O_v,ij + w[1] O_t,ij).
+ * d_ids, d_vals: HOST arrays of the four lists' device addresses.  d_w [2] (device): the modal weights; with one modality
+ * pass 1 at the present one.
+ * WRITTEN: d_rowptr [n_items + 1]; d_col, d_val [4 k n_items] (entries beyond d_rowptr[n_items]: column 0, value 0);
+ * d_slots [4 k n_items][4]: the position of the entry in each of the four lists of its row, or -1 (beyond the last entry: -1);
+ * d_r, d_q [n_items].  d_work: skr_lattice_graph_workspace bytes, 16-byte aligned. */
+size_t skr_lattice_graph_workspace(int n_items);
+int skr_lattice_graph(int n_items, int k, const int32_t* const* d_ids, const float* const* d_vals, const float* d_w, double lam,
+                      int64_t* d_rowptr, int32_t* d_col, float* d_val, int32_t* d_slots, float* d_r, float* d_q, void* d_work,
+                      size_t work_bytes, void* stream);
+/* The sampled product over the entries of a CSR pattern: g[e] (+)= sum_{l < n_layers} <A_l[row(e)], B_l[col(e)]> with
+ * A_l = d_A + l * stride_a and B_l = d_B + l * stride_b (floats), the layers added in order.  d_row_mask (uint8 [n_rows] or
+ * NULL): the rows with a 0 byte are not visited; without `accumulate` their entries are written as zeros. */
+int skr_lattice_sddmm(int n_rows, int n_cols, const int64_t* d_rowptr, const int32_t* d_col, const float* d_A, int64_t stride_a,
+                      const float* d_B, int64_t stride_b, int n_layers, const uint8_t* d_row_mask, int accumulate, float* d_g,
+                      void* stream);
+/* The backward of skr_lattice_graph given d_g [nnz] = dLoss/dS: through the surviving similarities, the normalisation and the
+ * modal weights, then through the cosine of the projected rows d_F[m] [n_items][64] (NULL: the modality is absent):
+ *   a = (1 - lam) g;  t_i = sum_(row i) a L q_j + sum_(column i) a L q_k;  rho_i = -1/2 q_i^3 t_i;  dL_ij = a q_i q_j + rho_i
+ *   ds_m = w[m] dL;  dw_m = sum dL s_m + lam sum g O_m;  dF_i += ds_ij (f^_j - s_ij f^_i) / |f_i| and the same at j.
+ * The column-side sums are taken by the wavefront of row i of S^T (d_rowptr_t, d_col_t; d_perm_t [nnz]: the entry of S that
+ * entry e of S^T is).  WRITTEN: d_dF[m] [n_items][64], every element; d_dw [4] = dw_0, dw_1 and the gradient of the two
+ * softmax logits w_m (dw_m - sum_n w_n dw_n).  d_work: skr_lattice_graph_bwd_workspace bytes, 16-byte aligned. */
+size_t skr_lattice_graph_bwd_workspace(int n_items, int64_t nnz);
+int skr_lattice_graph_bwd(int n_items, int k, int64_t nnz, const float* d_g, const int64_t* d_rowptr, const int32_t* d_col,
+                          const int32_t* d_slots, const int64_t* d_rowptr_t, const int32_t* d_col_t, const int32_t* d_perm_t,
+                          const int32_t* const* d_ids, const float* const* d_vals, const float* d_w, double lam, const float* d_q,
+                          const float* const* d_F, float* const* d_dF, float* d_dw, void* d_work, size_t work_bytes, void* stream);
+/* d_out[r] += d_h[r] / max(|d_h[r]|, 1e-12) over n_rows rows of 64 floats: the item rows' + F.normalize(h) of the ranking
+ * (LATTICE.py:265, 268). */
+int skr_lattice_add_normalized(const float* d_h, int64_t n_rows, float* d_out, void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   lightgcn: M = mean_{k=0..n_ui_layers} P^k X_0 with P = D^-1 (A + I) on the square [n_users + n_items] adjacency (plan_p,
+ *   the diagonal inside; plan_pt its transpose, whose values differ);  mf: M = X_0;
+ *   h = S^n_layers X_0 items (the last run at the batch's item rows only);  item rows: M_i + h_i / max(|h_i|, 1e-12);
+ *   loss[0] = -mean logsigmoid(<u, p> - <u, q>), loss[1] = reg (|u|^2 + |p|^2 + |q|^2) / (2 n), loss[2] = their sum   WRITTEN
+ *   grad: the gradient of loss[2] with respect to the [n_users + n_items, 64] rows, every element                     WRITTEN
+ *   with g_out (a build step): g_out[e] = dLoss/dS_e = sum_l <dh_l[row(e)], h_(l-1)[col(e)]> over the entries of S   WRITTEN
+ * Rows with a user or item out of range contribute nothing. */
+typedef struct skr_lattice_step_args {
+    const skr_spmm_plan* plan_p;       /* P [N, N], N = n_users + n_items; may be NULL with mf or n_ui_layers == 0 */
+    const skr_spmm_plan* plan_pt;      /* its transpose */
+    const skr_spmm_plan* plan_s;       /* S [n_items, n_items]; may be NULL if n_layers == 0 */
+    const skr_spmm_plan* plan_st;      /* its transpose */
+    int32_t n_users, n_items, dim, n_ui_layers, n_layers, cf_model, n;
+    float reg;
+    const float* params;               /* [N, 64] */
+    const int32_t* users;              /* [n] */
+    const int32_t* pos;                /* [n] */
+    const int32_t* neg;                /* [n] */
+    float* M;                          /* [N, 64]; not used with mf or n_ui_layers == 0 */
+    float* ping[2];                    /* scratch, [N, 64] each */
+    float* G;                          /* scratch, [N, 64] */
+    float* DH;                         /* scratch, [max(n_layers, 1)][n_items][64]: dh_1 .. dh_n */
+    float* H;                          /* with g_out: [n_layers][n_items][64] receives h_0 .. h_(n-1); otherwise not used */
+    float* grad;                       /* [N, 64] */
+    float* g_out;                      /* [nnz of S] or NULL */
+    const int64_t* s_rowptr;           /* with g_out: the CSR pattern of S */
+    const int32_t* s_col;
+    float* loss;                       /* [3] */
+    void* work;                        /* skr_lattice_workspace bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_lattice_step_args;
+size_t skr_lattice_workspace(int n, int n_items);
+int skr_lattice_step(const skr_lattice_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_LATTICE_GROUPS launch groups (user-item runs forward; runs of S; batch
+ * kernel and loss; clears, rank and ordered adds; user-item runs backward; runs of S^T; the sampled product): h_ms[k] (host) =
+ * milliseconds of group k; synchronises the stream (timing tools). */
+#define SKR_LATTICE_GROUPS 7
+int skr_lattice_step_timed(const skr_lattice_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
 #include <cstdarg>
 
-#define SKR_ABI_VERSION 17
+#define SKR_ABI_VERSION 18
 
 namespace skr {
 static thread_local std::string g_err;

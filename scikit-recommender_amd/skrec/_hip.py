@@ -179,6 +179,15 @@ SIGNATURES = {
     "skr_mgcn_workspace": (sz, [i32, i32, i32]),
     "skr_mgcn_step": (i32, [vp, vp]),
     "skr_mgcn_step_timed": (i32, [vp, vp, vp]),
+    "skr_lattice_graph_workspace": (sz, [i32]),
+    "skr_lattice_graph": (i32, [i32, i32, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "skr_lattice_sddmm": (i32, [i32, i32, vp, vp, vp, i64, vp, i64, i32, vp, i32, vp, vp]),
+    "skr_lattice_graph_bwd_workspace": (sz, [i32, i64]),
+    "skr_lattice_graph_bwd": (i32, [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, sz, vp]),
+    "skr_lattice_add_normalized": (i32, [vp, i64, vp, vp]),
+    "skr_lattice_workspace": (sz, [i32, i32]),
+    "skr_lattice_step": (i32, [vp, vp]),
+    "skr_lattice_step_timed": (i32, [vp, vp, vp]),
 }
 
 
@@ -251,6 +260,16 @@ class MGCNStepArgs(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+class LatticeStepArgs(C.Structure):
+    """skr_lattice_step_args (include/skrec_hip.h): the plans of the square adjacency and of the item graph, the parameters, the
+    batch, the layer tables and the scratch of one LATTICE step"""
+    _fields_ = [("plan_p", vp), ("plan_pt", vp), ("plan_s", vp), ("plan_st", vp), ("n_users", C.c_int32), ("n_items", C.c_int32),
+                ("dim", C.c_int32), ("n_ui_layers", C.c_int32), ("n_layers", C.c_int32), ("cf_model", C.c_int32), ("n", C.c_int32),
+                ("reg", C.c_float), ("params", vp), ("users", vp), ("pos", vp), ("neg", vp), ("M", vp), ("ping", vp * 2), ("G", vp),
+                ("DH", vp), ("H", vp), ("grad", vp), ("g_out", vp), ("s_rowptr", vp), ("s_col", vp), ("loss", vp), ("work", vp),
+                ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -272,6 +291,8 @@ SKR_FREEDOM_MAX_NNZ = 2 ** 31 - 1         # skr_freedom_keys / _select / _pruned
 SKR_KNN_MAX_K = 32                       # skr_knn_topk: neighbours per row
 SKR_MGCN_MAX_BATCH, SKR_MGCN_MAX_LAYERS, SKR_MGCN_MAX_FEAT, SKR_MGCN_GROUPS = 2048, 4, 4096, 8   # skr_mgcn_step limits
 SKR_MGCN_GATE_FLOATS, SKR_MGCN_QUERY_FLOATS = 64 * 64 + 64, 64 * 64 + 64 + 64   # a gate block; query_common's W | b | q
+SKR_LATTICE_MAX_BATCH, SKR_LATTICE_MAX_LAYERS, SKR_LATTICE_GROUPS = 2048, 4, 7   # skr_lattice_step limits
+SKR_LATTICE_CF_LIGHTGCN, SKR_LATTICE_CF_MF = 0, 1                               # skr_lattice_step_args.cf_model
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 
