@@ -1498,6 +1498,87 @@ int skr_lattice_step(const skr_lattice_step_args* args, void* stream);
 #define SKR_LATTICE_GROUPS 7
 int skr_lattice_step_timed(const skr_lattice_step_args* args, void* stream, float* h_ms);
 
+/* ============================================================================================
+ * O -- SLMRec, self-supervised multimedia recommendation (csrc/slmrec.hip; skr_slmrec_project_bwd_w beside the projection
+ * backward it shares its kernels with, csrc/mgcn.hip)
+ * replaces: _SLMRec.compute / infonce / fac / full_sort_predict and SLMRec.fit's step (recommender/SLMRec.py:132-177, 337-376,
+ * 423-432, 559-566) at rec_dim <= 64, ssl_task = "FAC", mm_fusion_mode = "concat", adj_type = "pre", both modalities.
+ * Tables of 64-float rows, zero beyond dim, 16-byte aligned; users and items share flat [n_users + n_items, 64] tables, user
+ * rows first.  Feature tables and projection blocks are section J's: [n_items][feat_ld] and W [64][feat_ld] | b [64]; modality
+ * 0 is the image block (v_dense), 1 the text block (t_dense); the feature tables are CONSTANTS (row-normalised once by the
+ * caller) and get no gradient.  A gate block is W [64 out][64 in] | b [64] (SKR_SLMREC_GATE_FLOATS), zero beyond the layer's
+ * widths (dim / 2 rows for g_iva_ivat and g_t_ivat).  A fusion block is W [64 out][192 in] | b [64]
+ * (SKR_SLMREC_FUSION_FLOATS): input column 64 t + c is column c of table t (Mi, Mv, Mt), the reference's column t dim + c.
+ * The fusion runs on v_mfma_f32_16x16x4_f32; the five chain layers, the three log-sum-exp products and every backward product
+ * add the same fp32 operands on v_mfma_f64_16x16x4_f64 and round once, as section M's do.  No floating-point atomic, every sum
+ * in a fixed order: all entries are bit-reproducible.
+ * ========================================================================================== */
+#define SKR_SLMREC_MAX_BATCH 2048
+#define SKR_SLMREC_MAX_LAYERS 4
+#define SKR_SLMREC_MAX_FEAT 4096
+#define SKR_SLMREC_GATE_FLOATS (64 * 64 + 64)
+#define SKR_SLMREC_FUSION_FLOATS (64 * 192 + 64)
+/* The weight part of skr_mgcn_project_bwd alone, by the same kernels and bit for bit the same values: d_dtrs = dW [64][feat_ld]
+ * = dF^T X, then db [64] = the column sums of dF, EVERY element WRITTEN; dX is not formed (the feature table is a constant:
+ * at 100 k items of 4 096 columns it would be a 1.6 GB write per step).  d_work: skr_mgcn_project_bwd_workspace bytes. */
+int skr_slmrec_project_bwd_w(const float* d_dF, const float* d_X, int n_rows, int feat_dim, int feat_ld, float* d_dtrs,
+                             void* d_work, size_t work_bytes, void* stream);
+/* The fusion over all rows of one side (SLMRec.py:174-175), row-local: d_out[r] = W [Mi_r | Mv_r | Mt_r] + b over n_rows rows
+ * of d_Mi, d_Mv, d_Mt [n_rows][64]; d_fusion: a fusion block in HBM, staged through LDS.  For the ranking only. */
+int skr_slmrec_fuse(const float* d_Mi, const float* d_Mv, const float* d_Mt, const float* d_fusion, int64_t n_rows, int dim,
+                    float* d_out, void* stream);
+/* One training step, forward and backward, issued on `stream`.  Every pointer is a device pointer except the plans.
+ *   D_m = skr_mgcn_project of modality m; M[0] = P([E_u; E_i]), M[1] = P([E_u; D_0]), M[2] = P([E_u; D_1]) with
+ *   P(x) = mean_{k=0..n_layers} A^k x (2 n_layers plan runs per table, the mean in the accum epilogue); A is symmetric:
+ *   plan_a is its user x item block, plan_at that block's transpose;
+ *   at the batch's n rows only: user = fusion_user [M[t][users]], item = fusion_item [M[t][n_users + pos]];
+ *   x = g_i_iv(M[0] item row), y = g_v_iv(M[1] item row), z = g_iva_ivat(g_iv_iva(x)), w = g_t_ivat(M[2] item row);
+ *   CE(a, b, tau) = mean_r [log sum_k exp(<a_r, b_k> / tau) - <a_r, b_r> / tau], the running maximum subtracted, all n columns,
+ *   no [n, n] array in HBM;
+ *   loss[0] = CE(user / max(|user|, 1e-12), item / max(|item|, 1e-12), temp), loss[1] = ssl_alpha CE(x, y, ssl_temp),
+ *   loss[2] = ssl_alpha CE(z, w, ssl_temp), loss[3] = their sum                                                     WRITTEN
+ *   grad (the rows), dense_grad, fusion_*_grad, chain_grad: the gradient of loss[3], every element                  WRITTEN
+ *   M[0..2] keep the three propagated tables (the ranking fuses them with skr_slmrec_fuse).
+ * A batch row with an id out of range contributes nothing (n stays the divisor).  With n == 0 nothing is launched and NOTHING is
+ * written, neither loss nor a gradient (the arguments are still checked).  Bit-reproducible. */
+typedef struct skr_slmrec_step_args {
+    const skr_spmm_plan* plan_a;       /* the user x item block of the 'pre' adjacency */
+    const skr_spmm_plan* plan_at;      /* its transpose */
+    int32_t n_users, n_items, dim, n_layers, n;
+    int32_t feat_dim[2];
+    int32_t feat_ld[2];
+    float temp, ssl_temp, ssl_alpha;
+    const float* params;               /* [n_users + n_items, 64] */
+    const float* dense[2];             /* v_dense, t_dense: W [64][feat_ld], then b [64] */
+    const float* feat[2];              /* [n_items][feat_ld], constants */
+    const float* fusion_user;          /* embedding_user_after_GCN: a fusion block */
+    const float* fusion_item;          /* embedding_item_after_GCN */
+    const float* chain[5];             /* gate blocks: g_i_iv, g_v_iv, g_iv_iva, g_iva_ivat, g_t_ivat */
+    const int32_t* users;              /* [n] */
+    const int32_t* pos;                /* [n] */
+    float* D[2];                       /* [n_items, 64] the projected features */
+    float* M[3];                       /* [n_users + n_items, 64] */
+    float* G[3];                       /* scratch, [n_users + n_items, 64] each */
+    float* ping[2];                    /* scratch, [n_users + n_items, 64] each */
+    float* dD;                         /* scratch, [n_items, 64] */
+    float* grad;                       /* [n_users + n_items, 64] */
+    float* dense_grad[2];
+    float* fusion_user_grad;
+    float* fusion_item_grad;
+    float* chain_grad[5];
+    float* loss;                       /* [4] */
+    void* work;                        /* skr_slmrec_workspace bytes, 16-byte aligned, no initial contents */
+    size_t work_bytes;
+} skr_slmrec_step_args;
+size_t skr_slmrec_workspace(int n, int n_items, int feat_ld_max);
+int skr_slmrec_step(const skr_slmrec_step_args* args, void* stream);
+/* The same step with an event after each of its SKR_SLMREC_GROUPS launch groups (projections; the 6 n_layers plan runs of the
+ * forward; the batch forward: fusion, chain, norms, log-sum-exp, loss; the batch backward with its weight gradients; clears,
+ * rank and ordered adds; the backward chain of M[0]; that of M[1] with v_dense's weight gradient; that of M[2] with t_dense's):
+ * h_ms[k] (host) = milliseconds of group k; synchronises the stream (timing tools). */
+#define SKR_SLMREC_GROUPS 8
+int skr_slmrec_step_timed(const skr_slmrec_step_args* args, void* stream, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@
 #include "skr_common.h"
 #include "mfma_tile.h"
 #include "step_common.h"
+#include "dense_ops.h"
 
 #include <algorithm>
 
@@ -933,6 +934,17 @@ int run_step(const skr_mgcn_step_args* a, void* stream, float* h_ms) {
 
 }  // namespace
 
+// dense_ops.h: the two dense products over rows, for the other models' steps (slmrec.hip)
+namespace skr {
+int64_t dense_xty_floats(int64_t n, int ld) { return xty_floats(n, ld); }
+int dense_xty(const float* Dm, const float* Y, int64_t n, int ld, float* part, float* out, hipStream_t st) {
+    return launch_xty(Dm, Y, n, ld, part, out, st);
+}
+int dense_rows_w(const float* Dm, int64_t n, int ld, const float* W, float* out, int accumulate, hipStream_t st) {
+    return launch_rows_w(Dm, n, ld, W, out, accumulate, st);
+}
+}  // namespace skr
+
 extern "C" {
 
 int skr_mgcn_project(const float* d_X, int n_rows, int feat_dim, int feat_ld, const float* d_trs, float* d_Y, void* stream) {
@@ -966,6 +978,22 @@ int skr_mgcn_project_bwd(const float* d_dF, const float* d_X, int n_rows, int fe
                   reinterpret_cast<uintptr_t>(d_dtrs) | reinterpret_cast<uintptr_t>(d_dX) | reinterpret_cast<uintptr_t>(d_work)) & 15) == 0,
                 "skr_mgcn_project_bwd: the tables and work must be 16-byte aligned");
     return project_bwd(d_dF, d_X, n_rows, feat_ld, d_trs, d_dtrs, d_dX, static_cast<float*>(d_work), skr::as_stream(stream));
+}
+
+// the weight part of skr_mgcn_project_bwd alone -- the same launches, without dX = dF W: for a model whose feature table is a
+// constant (SLMRec)
+int skr_slmrec_project_bwd_w(const float* d_dF, const float* d_X, int n_rows, int feat_dim, int feat_ld, float* d_dtrs, void* d_work,
+                             size_t work_bytes, void* stream) {
+    SKR_REQUIRE(d_dF && d_X && d_dtrs && d_work, "skr_slmrec_project_bwd_w: NULL argument");
+    SKR_REQUIRE(n_rows > 0, "skr_slmrec_project_bwd_w: n_rows = %d", n_rows);
+    const int rc = check_feature("skr_slmrec_project_bwd_w", feat_dim, feat_ld);
+    if (rc != SKR_OK) return rc;
+    SKR_REQUIRE(work_bytes >= skr_mgcn_project_bwd_workspace(n_rows, feat_ld), "skr_slmrec_project_bwd_w: work holds %zu bytes, %zu are needed",
+                work_bytes, skr_mgcn_project_bwd_workspace(n_rows, feat_ld));
+    SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_dF) | reinterpret_cast<uintptr_t>(d_X) | reinterpret_cast<uintptr_t>(d_dtrs) |
+                  reinterpret_cast<uintptr_t>(d_work)) & 15) == 0,
+                "skr_slmrec_project_bwd_w: the tables and work must be 16-byte aligned");
+    return launch_xty(d_dF, d_X, n_rows, feat_ld, static_cast<float*>(d_work), d_dtrs, skr::as_stream(stream));
 }
 
 int skr_mgcn_purify(const float* d_F, const float* d_E, const float* d_gate, int n_rows, int dim, float* d_g, float* d_X, void* stream) {

@@ -188,6 +188,11 @@ SIGNATURES = {
     "skr_lattice_workspace": (sz, [i32, i32]),
     "skr_lattice_step": (i32, [vp, vp]),
     "skr_lattice_step_timed": (i32, [vp, vp, vp]),
+    "skr_slmrec_project_bwd_w": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+    "skr_slmrec_fuse": (i32, [vp, vp, vp, vp, i64, i32, vp, vp]),
+    "skr_slmrec_workspace": (sz, [i32, i32, i32]),
+    "skr_slmrec_step": (i32, [vp, vp]),
+    "skr_slmrec_step_timed": (i32, [vp, vp, vp]),
 }
 
 
@@ -270,6 +275,17 @@ class LatticeStepArgs(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+class SLMRecStepArgs(C.Structure):
+    """skr_slmrec_step_args (include/skrec_hip.h): the plans of the user-item graph, the parameter blocks, the constant feature
+    tables, the batch, the forward's tables and the scratch of one SLMRec step"""
+    _fields_ = [("plan_a", vp), ("plan_at", vp), ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32), ("n_layers", C.c_int32),
+                ("n", C.c_int32), ("feat_dim", C.c_int32 * 2), ("feat_ld", C.c_int32 * 2), ("temp", C.c_float), ("ssl_temp", C.c_float),
+                ("ssl_alpha", C.c_float), ("params", vp), ("dense", vp * 2), ("feat", vp * 2), ("fusion_user", vp), ("fusion_item", vp),
+                ("chain", vp * 5), ("users", vp), ("pos", vp), ("D", vp * 2), ("M", vp * 3), ("G", vp * 3), ("ping", vp * 2), ("dD", vp),
+                ("grad", vp), ("dense_grad", vp * 2), ("fusion_user_grad", vp), ("fusion_item_grad", vp), ("chain_grad", vp * 5),
+                ("loss", vp), ("work", vp), ("work_bytes", C.c_size_t)]
+
+
 SKR_MAX_TOPK = 128            # skr_eval_fused_topk
 SKR_MAX_TOPK_SCORES = 512     # skr_eval_scores, skr_rank_metrics
 SKR_LOSS_SLOTS = 32      # skr_bpr_step_spread: pairs of loss words per batch
@@ -293,6 +309,8 @@ SKR_MGCN_MAX_BATCH, SKR_MGCN_MAX_LAYERS, SKR_MGCN_MAX_FEAT, SKR_MGCN_GROUPS = 20
 SKR_MGCN_GATE_FLOATS, SKR_MGCN_QUERY_FLOATS = 64 * 64 + 64, 64 * 64 + 64 + 64   # a gate block; query_common's W | b | q
 SKR_LATTICE_MAX_BATCH, SKR_LATTICE_MAX_LAYERS, SKR_LATTICE_GROUPS = 2048, 4, 7   # skr_lattice_step limits
 SKR_LATTICE_CF_LIGHTGCN, SKR_LATTICE_CF_MF = 0, 1                               # skr_lattice_step_args.cf_model
+SKR_SLMREC_MAX_BATCH, SKR_SLMREC_MAX_LAYERS, SKR_SLMREC_MAX_FEAT, SKR_SLMREC_GROUPS = 2048, 4, 4096, 8   # skr_slmrec_step limits
+SKR_SLMREC_GATE_FLOATS, SKR_SLMREC_FUSION_FLOATS = 64 * 64 + 64, 64 * 192 + 64   # a chain layer's block; a fusion layer's W [64][192] | b
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 
 
