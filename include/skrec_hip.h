@@ -965,7 +965,10 @@ int skr_lightgcl_cl(const float* d_Q, int n, const float* d_E, int n_rows, float
  *          optimiser's weight decay 2 lambda2)
  *   sum  = E_u | E_i, the sums over the layers the reference keeps for evaluate()    WRITTEN
  * lambda1 == 0 skips the contrastive and low-rank work (factor tables, q and addend are then not used).  Ids out of range
- * are skipped.  n <= SKR_LIGHTGCL_MAX_QUERIES / 2 pairs.  No floating-point atomic: the step is bit-reproducible. */
+ * are skipped, each id on its own: the BPR term of a pair needs its three ids, the log-sum-exp and the positive score of a
+ * user (an item) need that id alone; n and 2 n stay the divisors of the means.  With n == 0 nothing is launched and NOTHING is
+ * written, neither loss, grad nor sum (the arguments are still checked).
+ * n <= SKR_LIGHTGCL_MAX_QUERIES / 2 pairs.  No floating-point atomic: the step is bit-reproducible. */
 typedef struct skr_lightgcl_step_args {
     const skr_spmm_plan* plan_a;       /* A [n_users, n_items], values 1 / sqrt(rowdeg coldeg) (LightGCL.py:185-196) */
     const skr_spmm_plan* plan_at;      /* its transpose */
@@ -1022,8 +1025,10 @@ int skr_lightgcl_step_timed(const skr_lightgcl_step_args* args, void* stream, fl
  *   grad = the gradient of loss[2] with respect to the flat parameter buffer          WRITTEN, every element
  *   sel_out[b, h] = k*(b, h)                                                           WRITTEN when not NULL
  *   sel_in[b, h] >= 0 forces k*(b, h) to that candidate (values beyond n_negs - 1 are clamped); -1: the kernel chooses
- * The gamma terms apply when gamma > 0.  Rows whose user or positive item is out of range contribute nothing; a candidate
- * out of range counts as a zero row.  Every product of the selection is fp32 (v_mfma_f32_16x16x4_f32 and fp32 VALU).
+ * The gamma terms apply when gamma > 0.  Rows whose user or positive item is out of range contribute nothing, neither to mf
+ * nor to emb nor to a gradient (n stays the divisor of both); a candidate out of range counts as a zero row.  With n == 0
+ * nothing is launched and NOTHING is written, neither loss, grad, sel_out nor a hop table (the arguments are still checked).
+ * Every product of the selection is fp32 (v_mfma_f32_16x16x4_f32 and fp32 VALU).
  * No floating-point atomic: the step is bit-reproducible. */
 typedef struct skr_dens_step_args {
     const skr_spmm_plan* plan_a;       /* A [n_users, n_items], values 1 / sqrt(rowdeg coldeg); may be NULL if n_hops == 0 */
@@ -1084,7 +1089,9 @@ int skr_selfcf_keeps(const int32_t* d_perm, int64_t nnz, const uint8_t* d_k1, co
  *   grad = the gradient of loss[2] with respect to the flat parameter buffer            WRITTEN, every element
  *   M                                                                                  WRITTEN
  * The targets carry no gradient.  ku / ki NULL: drawn on the device, keyed by (seed, step, side, row, column), the user
- * side first.  Rows whose user or item is out of range contribute nothing.  The predictor's products run as 16-row tiles on
+ * side first.  Rows whose user or item is out of range contribute nothing (n stays the divisor of the two means; loss[1] is a
+ * sum over the remaining rows).  With n == 0 nothing is launched and NOTHING is written, neither loss, grad nor M (the
+ * arguments are still checked).  The predictor's products run as 16-row tiles on
  * v_mfma_f32_16x16x4_f32 with fp32 operands.  No floating-point atomic: the step is bit-reproducible. */
 typedef struct skr_selfcf_step_args {
     const skr_spmm_plan* plan_a;       /* A [n_users, n_items]; may be NULL if n_layers == 0 */
@@ -1163,7 +1170,9 @@ int skr_bm3_draws(const int32_t* d_ids, int n, int table, float rate, uint64_t s
  *   (zero, if every step hands in the previous step's items).
  * keep[t] ([n, 64] bytes per table of SKR_BM3_DRAW_*; a repeated node must carry equal rows) are handed in together or all
  * NULL: drawn on the device, keyed by (seed, step, table, node id, column).  Rows whose user or item is out of range
- * contribute nothing.  The predictor's and the projections' products run on v_mfma_f32_16x16x4_f32 with fp32 operands.  No
+ * contribute nothing (n stays the divisor of every mean; loss[2] does not depend on the batch).  With n == 0 nothing is
+ * launched and NOTHING is written, neither loss, a gradient nor M, and no feat_grad row is cleared (the arguments are still
+ * checked).  The predictor's and the projections' products run on v_mfma_f32_16x16x4_f32 with fp32 operands.  No
  * floating-point atomic, every sum in a fixed order: the step is bit-reproducible. */
 typedef struct skr_bm3_step_args {
     const skr_spmm_plan* plan_a;       /* A [n_users, n_items]; may be NULL if n_layers == 0 */
@@ -1271,7 +1280,9 @@ int skr_freedom_pruned_csr(int n_users, int n_items, int64_t nnz, const int64_t*
  *   at reg > 0: trs_grad[m] (W: every element; b: exact zeros, it cancels in x_m) and feat_grad[m] -- first the rows named
  *   by clear_items are zeroed, then the row of every distinct item of pos || neg is written; other rows are left alone.
  * At reg == 0 the modal arguments are not looked at and nothing is launched for them.  Rows with a user or item out of range
- * contribute nothing.  No floating-point atomic, every sum in a fixed order: the step is bit-reproducible. */
+ * contribute nothing (n stays the divisor of every mean).  With n == 0 nothing is launched and NOTHING is written, neither
+ * loss, a gradient nor M, and no feat_grad row is cleared (the arguments are still checked).
+ * No floating-point atomic, every sum in a fixed order: the step is bit-reproducible. */
 typedef struct skr_freedom_step_args {
     const skr_spmm_plan* plan_a;       /* A' [n_users, n_items]: this epoch's pruned matrix; may be NULL if n_ui_layers == 0 */
     const skr_spmm_plan* plan_at;      /* its transpose */

@@ -375,7 +375,7 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
                     const int64_t o = static_cast<int64_t>(bD[rr]) * D + col;
                     const float gnv = gn[rowD[rr] * D + col], gpv = gp[rowD[rr] * D + col];
                     float dc = (PG[2 * nD + o] + PG[4 * nD + o] * gnv) + mm1[nb][rr];
-                    if (hD[rr] == 0 && cD >= 0) dc += regc * XD[(U + cD) * D + col];
+                    if (hD[rr] == 0 && cD >= 0 && uD[rr] >= 0 && pD[rr] >= 0) dc += regc * XD[(U + cD) * D + col];
                     Gc[rowD[rr] * D + col] = dc;
                     const float dpr = PG[3 * nD + o] + mm2[nb][rr];
                     pv = pD[rr] >= 0 ? XD[(U + pD[rr]) * D + col] : 0.0f;
@@ -418,9 +418,9 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
                 const int64_t o = static_cast<int64_t>(bD[rr]) * D + col;
                 float dp = (PG[1 * nD + o] + dpg[nb][rr]) + mm1[nb][rr];
                 float ds = PG[0 * nD + o] + mm2[nb][rr];
-                if (hD[rr] == 0) {
+                if (hD[rr] == 0 && uD[rr] >= 0 && pD[rr] >= 0) {     // a skipped row has no regulariser either (pool: sq = 0)
                     dp += regc * pDv[nb][rr];
-                    if (uD[rr] >= 0) ds += regc * XD[uD[rr] * D + col];
+                    ds += regc * XD[uD[rr] * D + col];
                 }
                 Gp[rowD[rr] * D + col] = dp;
                 Gs[rowD[rr] * D + col] = ds;

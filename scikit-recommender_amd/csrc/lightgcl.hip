@@ -129,8 +129,10 @@ __global__ __launch_bounds__(HW * 64) void cl_pass1_kernel(const float* __restri
 
 // merge: lse_b = log(sum exp(s) + 1e-8) from the partials in workgroup order (LightGCL.py:146-147, without the overflow
 // of exp(s) at s > 88 nor of exp(-max) at max < -88); loss[0] = weight * sum_b lse_b by a fixed tree
+// ids (may be NULL) / limit: a query whose id is out of range is a zero row; its lse stays out of the loss
 __global__ __launch_bounds__(1024) void cl_merge_kernel(const float* __restrict__ part, int n_wg, int n, int n4, float weight,
-                                                        float* __restrict__ lse, float* __restrict__ loss) {
+                                                        const int32_t* __restrict__ ids, int limit, float* __restrict__ lse,
+                                                        float* __restrict__ loss) {
     __shared__ float s_l[1024];
     const int t = threadIdx.x;
     float tot = 0.0f;
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(1024) void cl_merge_kernel(const float* __restrict_
         const float M2 = fmaxf(M, LOG_EPS);
         const float l = M2 + logf(S * expf(M - M2) + expf(LOG_EPS - M2));
         lse[b] = l;
-        tot += l;
+        if (ids == nullptr || (ids[b] >= 0 && ids[b] < limit)) tot += l;
     }
     s_l[t] = tot;
     __syncthreads();
@@ -575,12 +577,12 @@ __global__ __launch_bounds__(1024) void bk_loss_kernel(const float* __restrict__
 using Timer = StepTimer<SKR_LIGHTGCL_GROUPS + 1>;   // h_ms: an event after every launch group; otherwise nothing
 
 // the launches of one side's InfoNCE term; mk (may be NULL) gets a mark behind pass 1 + merge and one behind pass 2 + reduce
-int cl_run(const float* d_Q, int n, const float* d_E, int n_rows, float inv_temp, float weight, float* d_dQ, float* d_dE,
-           float* d_loss, float* w, hipStream_t st, Timer* mk) {
+int cl_run(const float* d_Q, int n, const float* d_E, int n_rows, float inv_temp, float weight, const int32_t* ids, float* d_dQ,
+           float* d_dE, float* d_loss, float* w, hipStream_t st, Timer* mk) {
     const int n_wg = n_workgroups(n_rows), tiles = (n_rows + TI - 1) / TI, n4 = static_cast<int>(round4(n));
     const ClLayout L = cl_layout(n, n_wg);
     hipLaunchKernelGGL(cl_pass1_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_E, d_Q, n, n4, n_rows, tiles, inv_temp, w + L.part);
-    hipLaunchKernelGGL(cl_merge_kernel, dim3(1), dim3(1024), 0, st, w + L.part, n_wg, n, n4, weight, w + L.lse, d_loss);
+    hipLaunchKernelGGL(cl_merge_kernel, dim3(1), dim3(1024), 0, st, w + L.part, n_wg, n, n4, weight, ids, n_rows, w + L.lse, d_loss);
     if (mk) SKR_HIP(mk->mark());
     hipLaunchKernelGGL(cl_pass2_kernel, dim3(n_wg), dim3(HW * 64), 0, st, d_E, d_Q, w + L.lse, n, n4, n_rows, tiles, inv_temp,
                        weight * inv_temp, d_dE, w + L.dqpart);
@@ -689,10 +691,10 @@ int run_step(const skr_lightgcl_step_args* a, void* stream, float* h_ms) {
         SKR_LAUNCH_CHECK();
         SKR_HIP(mk.mark());
         // LightGCL.py:146-147: the mean over the n users, resp. the 2n items, times lambda1
-        int rc = cl_run(w + L.Qu, n, a->sum, U, a->inv_temp, a->lambda1 / static_cast<float>(n), w + L.dQu, a->gsum, w + L.clloss,
+        int rc = cl_run(w + L.Qu, n, a->sum, U, a->inv_temp, a->lambda1 / static_cast<float>(n), a->uids, w + L.dQu, a->gsum, w + L.clloss,
                         w + L.cl, st, &mk);
         if (rc != SKR_OK) return rc;
-        rc = cl_run(w + L.Qi, 2 * n, a->sum + UO, I, a->inv_temp, a->lambda1 / static_cast<float>(2 * n), w + L.dQi, a->gsum + UO,
+        rc = cl_run(w + L.Qi, 2 * n, a->sum + UO, I, a->inv_temp, a->lambda1 / static_cast<float>(2 * n), iids, w + L.dQi, a->gsum + UO,
                     w + L.clloss + 1, w + L.cl, st, &mk);
         if (rc != SKR_OK) return rc;
     } else {
@@ -762,7 +764,7 @@ int skr_lightgcl_cl(const float* d_Q, int n, const float* d_E, int n_rows, float
                 n, n_rows, need);
     SKR_REQUIRE((reinterpret_cast<uintptr_t>(d_E) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0,
                 "skr_lightgcl_cl: d_E and d_work must be 16-byte aligned");
-    return cl_run(d_Q, n, d_E, n_rows, inv_temp, weight, d_dQ, d_dE, d_loss, static_cast<float*>(d_work), skr::as_stream(stream), nullptr);
+    return cl_run(d_Q, n, d_E, n_rows, inv_temp, weight, nullptr, d_dQ, d_dE, d_loss, static_cast<float*>(d_work), skr::as_stream(stream), nullptr);
 }
 
 size_t skr_lightgcl_workspace(int n, int n_users, int n_items) {

@@ -229,35 +229,16 @@ class BM3(GraphRecommender):
                                             self._step if step is None else int(step), _hip.ptr(out), _hip.stream()))
         return out
 
-    def gradient_step(self, users, items, target_keep=None, h_ms=None):
-        """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer,
-        the layer means (+ h) in ``self.M`` -> device tensor (graph cosines, modal cosines, reg, total).
-        ``target_keep`` = (ku, ki, kt, kv), [n, 64] each -- the flags of the user, item, text and image targets at the
-        batch's rows (the entries of an absent modality may be None) -- instead of the device draws;
-        ``h_ms``: a ctypes float array of SKR_BM3_GROUPS entries that receives the milliseconds of each launch group"""
-        cfg = self.config
-        du, di = self._ids(users), self._ids(items)
-        n, L = int(du.numel()), cfg.n_layers
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"BM3: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert di.numel() == n
-        self._grow_work(int(_hip.lib().skr_bm3_workspace(n)))
-        loss = torch.empty(4, dtype=torch.float32, device=self.device)
+    def _step_args(self, du, di, keeps, loss):
+        """``keeps``: None or the four [n, 64] uint8 device tensors of SKR_BM3_DRAW_*"""
+        cfg, L = self.config, self.config.n_layers
         a = _hip.BM3StepArgs()
-        keeps = None
-        if target_keep is not None:
-            ones = None
-            keeps = []
-            for k in target_keep:
-                if k is None:      # an absent modality: the kernel wants all four or none, and does not read this one
-                    ones = torch.ones((n, 64), dtype=torch.uint8, device=self.device) if ones is None else ones
-                    k = ones
-                keeps.append(self._flags(k, (n, 64)))
+        if keeps is not None:
             for t in range(4):
                 a.keep[t] = _hip.ptr(keeps[t])
         if L > 0:
             a.plan_a, a.plan_at = self.adj._plan_handle(), self.adj_t._plan_handle()
-        a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, n
+        a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, int(du.numel())
         a.params, a.users, a.items = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(di)
         a.grad = _hip.ptr(self._grad)
         for key, _, m in MODALITIES:
@@ -274,12 +255,41 @@ class BM3(GraphRecommender):
         a.M, a.G, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(loss)
         a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
         a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        return a
+
+    def gradient_step(self, users, items, target_keep=None, h_ms=None):
+        """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer,
+        the layer means (+ h) in ``self.M`` -> device tensor (graph cosines, modal cosines, reg, total).
+        ``target_keep`` = (ku, ki, kt, kv), [n, 64] each -- the flags of the user, item, text and image targets at the
+        batch's rows (the entries of an absent modality may be None) -- instead of the device draws;
+        ``h_ms``: a ctypes float array of SKR_BM3_GROUPS entries that receives the milliseconds of each launch group"""
+        cfg = self.config
+        du, di = self._ids(users), self._ids(items)
+        n, L = int(du.numel()), cfg.n_layers
+        if n > MAX_BATCH:
+            raise NotImplementedError(f"BM3: a batch holds at most {MAX_BATCH} rows (got {n})")
+        assert di.numel() == n
+        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        if n == 0:                     # skr_bm3_step launches nothing for an empty batch: a zero loss, a zero gradient
+            self._grad.zero_()
+            self._prev_items = None    # no feature-gradient row is left to clear
+            return loss
+        self._grow_work(int(_hip.lib().skr_bm3_workspace(n)))
+        keeps = None
+        if target_keep is not None:
+            ones = None
+            keeps = []
+            for k in target_keep:
+                if k is None:      # an absent modality: the kernel wants all four or none, and does not read this one
+                    ones = torch.ones((n, 64), dtype=torch.uint8, device=self.device) if ones is None else ones
+                    k = ones
+                keeps.append(self._flags(k, (n, 64)))
+        a = self._step_args(du, di, keeps, loss)
         if h_ms is None:
             _hip.check(_hip.lib().skr_bm3_step(ctypes.byref(a), _hip.stream()))
         else:
             _hip.check(_hip.lib().skr_bm3_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        if n > 0:
-            self._prev_items = di
+        self._prev_items = di
         self._step += 1
         return loss
 

@@ -187,6 +187,22 @@ class DENS(GraphRecommender):
         """1 - min(1, epoch / warmup) (DENS.py:247)"""
         return 1.0 - min(1.0, epoch / self.config.warmup)
 
+    def _step_args(self, du, dp, dc, dsel, sel_out, loss, epoch):
+        cfg, H = self.config, self.config.context_hops
+        a = _hip.DensStepArgs()
+        a.plan_a, a.plan_at = (self.adj._plan_handle(), self.adj_t._plan_handle()) if H > 0 else (None, None)
+        a.n_users, a.n_items, a.dim, a.n_hops, a.n_negs, a.n = self.num_users, self.num_items, cfg.dim, H, cfg.n_negs, int(du.numel())
+        a.params, a.uids, a.pos, a.cand = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(dp), _hip.ptr(dc)
+        a.sel_in, a.sel_out = _hip.ptr(dsel), _hip.ptr(sel_out)
+        a.w, a.gamma, a.l2 = self.selection_weight(epoch), cfg.gamma, cfg.l2
+        for h in range(H):
+            a.hop[h] = _hip.ptr(self._hops[h])
+        for h in range(len(self._G)):
+            a.G[h] = _hip.ptr(self._G[h])
+        a.ping, a.grad, a.loss = _hip.ptr(self._ping), _hip.ptr(self._grad), _hip.ptr(loss)
+        a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        return a
+
     def gradient_step(self, users, pos, cand, epoch, sel_in=None, h_ms=None):
         """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer
         -> (device tensor (mf, emb, total), device int32 [n, H + 1] of the chosen candidate index per row and hop).
@@ -198,25 +214,17 @@ class DENS(GraphRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"DENS: a batch holds at most {MAX_BATCH} rows (got {n})")
         assert dp.numel() == n and dc.numel() == n * cfg.n_negs
-        self._grow_work(int(_hip.lib().skr_dens_workspace(n, H)))
-        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(3, dtype=torch.float32, device=self.device)
         sel_out = torch.empty((n, H + 1), dtype=torch.int32, device=self.device)
+        if n == 0:                     # skr_dens_step launches nothing for an empty batch: a zero loss, a zero gradient
+            self._grad.zero_()
+            return loss, sel_out
+        self._grow_work(int(_hip.lib().skr_dens_workspace(n, H)))
         dsel = None
         if sel_in is not None:
             dsel = self._ids(sel_in)
             assert dsel.numel() == n * (H + 1)
-        a = _hip.DensStepArgs()
-        a.plan_a, a.plan_at = (self.adj._plan_handle(), self.adj_t._plan_handle()) if H > 0 else (None, None)
-        a.n_users, a.n_items, a.dim, a.n_hops, a.n_negs, a.n = self.num_users, self.num_items, cfg.dim, H, cfg.n_negs, n
-        a.params, a.uids, a.pos, a.cand = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(dp), _hip.ptr(dc)
-        a.sel_in, a.sel_out = _hip.ptr(dsel), _hip.ptr(sel_out)
-        a.w, a.gamma, a.l2 = self.selection_weight(epoch), cfg.gamma, cfg.l2
-        for h in range(H):
-            a.hop[h] = _hip.ptr(self._hops[h])
-        for h in range(len(self._G)):
-            a.G[h] = _hip.ptr(self._G[h])
-        a.ping, a.grad, a.loss = _hip.ptr(self._ping), _hip.ptr(self._grad), _hip.ptr(loss)
-        a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        a = self._step_args(du, dp, dc, dsel, sel_out, loss, epoch)
         if h_ms is None:
             _hip.check(_hip.lib().skr_dens_step(ctypes.byref(a), _hip.stream()))
         else:

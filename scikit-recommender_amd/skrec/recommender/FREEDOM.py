@@ -323,27 +323,17 @@ class FREEDOM(GraphRecommender):
         return DeviceCSR.from_arrays((nu, ni), rp, col[:k], val[:k]), DeviceCSR.from_arrays((ni, nu), rpt, colt[:k], valt[:k])
 
     # ---- training --------------------------------------------------------------------------------
-    def gradient_step(self, users, pos, neg, h_ms=None):
-        """forward and backward of one batch on the installed graph without the optimiser: the gradient is left in the
-        optimiser's gradient buffer, the layer means (+ h) in ``self.M`` -> device tensor (graph term, reg * modal terms,
-        total).  ``h_ms``: a ctypes float array of SKR_FREEDOM_GROUPS entries that receives the milliseconds of each launch group"""
+    def _step_args(self, du, dp, dn, loss):
         cfg = self.config
-        du, dp, dn = self._ids(users), self._ids(pos), self._ids(neg)
-        n, Lu, Lm = int(du.numel()), cfg.n_ui_layers, cfg.n_mm_layers
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"FREEDOM: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert dp.numel() == n and dn.numel() == n
-        self._grow_work(int(_hip.lib().skr_freedom_workspace(n)))
-        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        Lu, Lm = cfg.n_ui_layers, cfg.n_mm_layers
         a = _hip.FreedomStepArgs()
         if Lu > 0:
             a.plan_a, a.plan_at = self.adj_train._plan_handle(), self.adj_train_t._plan_handle()
         if Lm > 0:
             a.plan_s, a.plan_st = self.mm_adj._plan_handle(), self.mm_adj_t._plan_handle()
-        a.n_users, a.n_items, a.dim, a.n_ui_layers, a.n_mm_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, Lu, Lm, n
+        a.n_users, a.n_items, a.dim, a.n_ui_layers, a.n_mm_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, Lu, Lm, int(du.numel())
         a.params, a.users, a.pos, a.neg = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(dp), _hip.ptr(dn)
         a.grad, a.reg = _hip.ptr(self._grad), cfg.reg
-        items = None
         if self._modal_trained:
             for key, _, m in MODALITIES:
                 if not self.feat_dim[key]:
@@ -354,15 +344,34 @@ class FREEDOM(GraphRecommender):
             prev = self._prev_items
             if prev is not None:
                 a.clear_items, a.n_clear = _hip.ptr(prev), int(prev.numel())
-            items = torch.cat([dp, dn])
         a.M, a.G, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(loss)
         a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
         a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        return a
+
+    def gradient_step(self, users, pos, neg, h_ms=None):
+        """forward and backward of one batch on the installed graph without the optimiser: the gradient is left in the
+        optimiser's gradient buffer, the layer means (+ h) in ``self.M`` -> device tensor (graph term, reg * modal terms,
+        total).  ``h_ms``: a ctypes float array of SKR_FREEDOM_GROUPS entries that receives the milliseconds of each launch group"""
+        cfg = self.config
+        du, dp, dn = self._ids(users), self._ids(pos), self._ids(neg)
+        n, Lu, Lm = int(du.numel()), cfg.n_ui_layers, cfg.n_mm_layers
+        if n > MAX_BATCH:
+            raise NotImplementedError(f"FREEDOM: a batch holds at most {MAX_BATCH} rows (got {n})")
+        assert dp.numel() == n and dn.numel() == n
+        loss = torch.zeros(3, dtype=torch.float32, device=self.device)
+        if n == 0:                     # skr_freedom_step launches nothing for an empty batch: a zero loss, a zero gradient
+            self._grad.zero_()
+            self._prev_items = None    # no feature-gradient row is left to clear
+            return loss
+        self._grow_work(int(_hip.lib().skr_freedom_workspace(n)))
+        a = self._step_args(du, dp, dn, loss)
+        items = torch.cat([dp, dn]) if self._modal_trained else None
         if h_ms is None:
             _hip.check(_hip.lib().skr_freedom_step(ctypes.byref(a), _hip.stream()))
         else:
             _hip.check(_hip.lib().skr_freedom_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        if n > 0 and items is not None:
+        if items is not None:
             self._prev_items = items
         return loss
 

@@ -201,8 +201,11 @@ class LightGCL(GraphRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"LightGCL: a batch holds at most {MAX_BATCH} pairs (got {n})")
         assert dp.numel() == n and dn.numel() == n
+        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        if n == 0:                     # skr_lightgcl_step launches nothing for an empty batch: a zero loss, a zero gradient, and
+            self._grad.zero_()         # the sums are not those of the current parameters
+            return loss
         self._grow_work(int(_hip.lib().skr_lightgcl_workspace(n, self.num_users, self.num_items)))
-        loss = torch.empty(4, dtype=torch.float32, device=self.device)
         a = self._step_args(du, dp, dn, loss)
         if h_ms is None:
             _hip.check(_hip.lib().skr_lightgcl_step(ctypes.byref(a), _hip.stream()))

@@ -179,6 +179,23 @@ class SelfCF(GraphRecommender):
                                                _hip.ptr(f[2]), _hip.ptr(f[3]), _hip.stream()))
         return f
 
+    def _step_args(self, du, di, rate, edge_keep, ku, ki, loss):
+        cfg, L = self.config, self.config.n_layers
+        a = _hip.SelfCFStepArgs()
+        if L > 0:
+            f = self.edge_keeps(rate, edge_keep)
+            a.plan_a, a.plan_at = self.adj._plan_handle(), self.adj_t._plan_handle()
+            a.keep_fu, a.keep_fi, a.keep_bu, a.keep_bi = (_hip.ptr(f[k]) for k in range(4))
+        a.edge_scale = float(np.float32(1.0 / (1.0 - rate)))
+        a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, int(du.numel())
+        a.params, a.users, a.items = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(di)
+        a.ku, a.ki = _hip.ptr(ku), _hip.ptr(ki)
+        a.dropout, a.reg, a.seed, a.step = cfg.dropout, cfg.reg, self._seed, self._step
+        a.M, a.G, a.grad, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(self._grad), _hip.ptr(loss)
+        a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
+        a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        return a
+
     def gradient_step(self, users, items, rate=None, edge_keep=None, target_keep=None, h_ms=None):
         """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer,
         the masked layer means in ``self.M`` -> device tensor (cosine, reg, total).
@@ -191,28 +208,19 @@ class SelfCF(GraphRecommender):
         if n > MAX_BATCH:
             raise NotImplementedError(f"SelfCF: a batch holds at most {MAX_BATCH} rows (got {n})")
         assert di.numel() == n
+        loss = torch.zeros(3, dtype=torch.float32, device=self.device)
+        if n == 0:                     # skr_selfcf_step launches nothing for an empty batch: a zero loss, a zero gradient
+            self._grad.zero_()
+            return loss
         if rate is None:
             rate = np.random.random()
         rate = float(rate)
         assert 0.0 <= rate < 1.0
         self._grow_work(int(_hip.lib().skr_selfcf_workspace(n, L)))
-        loss = torch.empty(3, dtype=torch.float32, device=self.device)
         ku = ki = None
         if target_keep is not None:
             ku, ki = (self._flags(k, (n, 64)) for k in target_keep)
-        a = _hip.SelfCFStepArgs()
-        if L > 0:
-            f = self.edge_keeps(rate, edge_keep)
-            a.plan_a, a.plan_at = self.adj._plan_handle(), self.adj_t._plan_handle()
-            a.keep_fu, a.keep_fi, a.keep_bu, a.keep_bi = (_hip.ptr(f[k]) for k in range(4))
-        a.edge_scale = float(np.float32(1.0 / (1.0 - rate)))
-        a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, n
-        a.params, a.users, a.items = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(di)
-        a.ku, a.ki = _hip.ptr(ku), _hip.ptr(ki)
-        a.dropout, a.reg, a.seed, a.step = cfg.dropout, cfg.reg, self._seed, self._step
-        a.M, a.G, a.grad, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(self._grad), _hip.ptr(loss)
-        a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
-        a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
+        a = self._step_args(du, di, rate, edge_keep, ku, ki, loss)
         if h_ms is None:
             _hip.check(_hip.lib().skr_selfcf_step(ctypes.byref(a), _hip.stream()))
         else:

@@ -42,25 +42,27 @@ def forward_f64(Eu, Ei, R, n_layers):
     return su / (n_layers + 1), si / (n_layers + 1) + Ei
 
 
-def losses_f64(P, R, users, items, keeps, n_layers, dropout, reg, cl_weight):
+def losses_f64(P, R, users, items, keeps, n_layers, dropout, reg, cl_weight, n_div=None):
     """-> ((graph, modal, reg part), M_u, M_i) of one step.  ``P``: {name: float64 tensor}; ``keeps``: {"u", "i", "t", "v"} ->
-    [n, d] keep flags of the batch rows' targets (the entries of absent modalities are not read)"""
+    [n, d] keep flags of the batch rows' targets (the entries of absent modalities are not read); ``n_div``: the divisor of
+    the cosine means when it is not the number of rows handed in (rows the kernel skips leave n)"""
     Mu, Mi = forward_f64(P["user_embedding.weight"], P["item_id_embedding.weight"], R, n_layers)
     users, items = (torch.as_tensor(np.asarray(a), dtype=torch.int64) for a in (users, items))
     W, b = P["predictor.weight"], P["predictor.bias"]
     pred = lambda x: x @ W.T + b                                                 # noqa: E731
-    tgt = lambda x, k: (x * t64(keeps[k]) / (1.0 - dropout)).detach()            # noqa: E731
+    tgt = lambda x, k: (x * torch.as_tensor(np.asarray(keeps[k]), dtype=x.dtype) / (1.0 - dropout)).detach()     # noqa: E731
+    mean = (lambda v: v.mean()) if n_div is None else (lambda v: v.sum() / n_div)                                # noqa: E731
     u, i = Mu[users], Mi[items]
     tu, ti = tgt(u, "u"), tgt(i, "i")
-    graph = (1 - cosine(pred(u), ti).mean()) + (1 - cosine(pred(i), tu).mean())
-    modal = torch.zeros((), dtype=F64)
+    graph = (1 - mean(cosine(pred(u), ti))) + (1 - mean(cosine(pred(i), tu)))
+    modal = torch.zeros((), dtype=Mu.dtype)
     for key, (emb, w, bias) in (("t", TEXT), ("v", IMAGE)):
         if emb not in P:
             continue
         x = P[emb][items] @ P[w].T + P[bias]
         tx = tgt(x, key)
         px = pred(x)
-        modal = modal + (1 - cosine(px, ti).mean()) + (1 - cosine(px, tx).mean())
+        modal = modal + (1 - mean(cosine(px, ti))) + (1 - mean(cosine(px, tx)))
     regl = reg * (Mu.norm() + Mi.norm()) / Mi.shape[0]
     return (graph, cl_weight * modal, regl), Mu, Mi
 

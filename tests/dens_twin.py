@@ -40,11 +40,16 @@ def _lin(P, name, x):
     return x @ P[name + ".weight"].T + P[name + ".bias"]
 
 
-def gates_and_scores(P, s, p, c, w):
-    """s, p [n, H+1, d], c [n, K, H+1, d] -> (gp, p gp, gn, scores [n, K, H+1], scale [n, H+1], arg-max [n, H+1])"""
-    gp = torch.sigmoid(_lin(P, "item_gate", p) + _lin(P, "user_gate", s))
+def gates_and_scores(P, s, p, c, w, pre=None):
+    """s, p [n, H+1, d], c [n, K, H+1, d] -> (gp, p gp, gn, scores [n, K, H+1], scale [n, H+1], arg-max [n, H+1]);
+    ``pre`` (a dict) receives the two gates' pre-activations ``a`` and ``z``"""
+    a = _lin(P, "item_gate", p) + _lin(P, "user_gate", s)
+    gp = torch.sigmoid(a)
     pr = p * gp
-    gn = torch.sigmoid(_lin(P, "neg_gate", c) + _lin(P, "pos_gate", pr).unsqueeze(1))
+    z = _lin(P, "neg_gate", c) + _lin(P, "pos_gate", pr).unsqueeze(1)
+    gn = torch.sigmoid(z)
+    if pre is not None:
+        pre["a"], pre["z"] = a.detach().numpy(), z.detach().numpy()
     with torch.no_grad():
         terms = s.unsqueeze(1) * (w * c - c * gn)
         scores = terms.sum(-1)
@@ -53,15 +58,22 @@ def gates_and_scores(P, s, p, c, w):
     return gp, pr, gn, scores, scale, own
 
 
-def step_f64(P, A, users, pos, cand, H, w, gamma, l2, choices=None):
+def step_f64(P, A, users, pos, cand, H, w, gamma, l2, choices=None, n_div=None):
     """one step's forward on float64 tensors ``P`` (NAMES) -> dict: mf, emb, total (tensors with a graph), choices [n, H + 1]
-    (candidate index), scores [n, K, H + 1], scale [n, H + 1] (the group's largest sum of |terms| of a score)"""
-    nu = P["user_embed"].shape[0]
+    (candidate index), scores [n, K, H + 1], scale [n, H + 1] (the group's largest sum of |terms| of a score), x [5, n] (the
+    arguments of the five softplus terms), a [n, H + 1, d] and z [n, K, H + 1, d] (the gates' pre-activations).
+    A candidate outside [0, num_items) is a zero row; ``n_div``: the divisor of the batch means when it is not the number of
+    rows handed in (rows skipped by the kernel leave n as the divisor)"""
+    nu, ni = P["user_embed"].shape[0], P["item_embed"].shape[0]
     users, pos, cand = (torch.as_tensor(np.asarray(a), dtype=torch.int64) for a in (users, pos, cand))
     n, K = cand.shape
+    nd = n if n_div is None else n_div
     X = hop_tables(P, A, H)
-    s, p, c = X[users], X[nu + pos], X[nu + cand]                       # [n, H+1, d], [n, H+1, d], [n, K, H+1, d]
-    gp, pr, gn, scores, scale, own = gates_and_scores(P, s, p, c, w)
+    Xz = torch.cat([X, torch.zeros_like(X[:1])], 0)                     # one more row: the zero row of a candidate out of range
+    ci = torch.where((cand >= 0) & (cand < ni), nu + cand, torch.full_like(cand, X.shape[0]))
+    s, p, c = X[users], X[nu + pos], Xz[ci]                             # [n, H+1, d], [n, H+1, d], [n, K, H+1, d]
+    pre = {}
+    gp, pr, gn, scores, scale, own = gates_and_scores(P, s, p, c, w, pre)
     if choices is None:
         choices = own
     else:                                                               # -1: the step's own choice
@@ -74,12 +86,13 @@ def step_f64(P, A, users, pos, cand, H, w, gamma, l2, choices=None):
     Pir, Nir = Pm - Pr, Nm - Nr
     dot = lambda a, b: (a * b).sum(-1)      # noqa: E731
     sp = torch.nn.functional.softplus
-    mf = sp(dot(u, Nm) - dot(u, Pm)).mean()
+    x = [dot(u, Nm) - dot(u, Pm), dot(u, Pir) - dot(u, Pr), dot(u, Nr) - dot(u, Nir), dot(u, Nr) - dot(u, Pr), dot(u, Pir) - dot(u, Nir)]
+    mf = sp(x[0]).sum() / nd
     if gamma > 0:
-        mf = mf + gamma / 4 * (sp(dot(u, Pir) - dot(u, Pr)).mean() + sp(dot(u, Nr) - dot(u, Nir)).mean()
-                               + sp(dot(u, Nr) - dot(u, Pr)).mean() + sp(dot(u, Pir) - dot(u, Nir)).mean())
-    emb = l2 * ((s[:, 0] ** 2).sum() + (p[:, 0] ** 2).sum() + (cs[:, 0] ** 2).sum()) / 2 / n
-    return dict(mf=mf, emb=emb, total=mf + emb, choices=choices.numpy(), own=own.numpy(), scores=scores.numpy(), scale=scale.numpy())
+        mf = mf + gamma / 4 * (sp(x[1]).sum() / nd + sp(x[2]).sum() / nd + sp(x[3]).sum() / nd + sp(x[4]).sum() / nd)
+    emb = l2 * ((s[:, 0] ** 2).sum() + (p[:, 0] ** 2).sum() + (cs[:, 0] ** 2).sum()) / 2 / nd
+    return dict(mf=mf, emb=emb, total=mf + emb, choices=choices.numpy(), own=own.numpy(), scores=scores.numpy(), scale=scale.numpy(),
+                x=torch.stack(x).detach().numpy(), a=pre["a"], z=pre["z"])
 
 
 def margins(scores, scale, cand):

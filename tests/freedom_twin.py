@@ -108,18 +108,25 @@ def forward_f64(Eu, Ei, R, S, Lu, Lm):
     return su / (Lu + 1), si / (Lu + 1) + h
 
 
-def losses_f64(P, R, S, users, pos, neg, Lu, Lm, reg):
-    """-> ((graph term, reg * modal terms), M_u, M_i) of one step.  ``P``: {name: float64 tensor}"""
+def losses_f64(P, R, S, users, pos, neg, Lu, Lm, reg, n_div=None, args=None):
+    """-> ((graph term, reg * modal terms), M_u, M_i) of one step.  ``P``: {name: float64 tensor}; ``n_div``: the divisor of
+    the means when it is not the number of rows handed in (rows the kernel skips leave n); ``args`` (a list) receives the
+    arguments of the log-sigmoids: x_g, then x_m of the text and of the image block"""
     Mu, Mi = forward_f64(P["user_embedding.weight"], P["item_id_embedding.weight"], R, S, Lu, Lm)
     users, pos, neg = (torch.as_tensor(np.asarray(a), dtype=torch.int64) for a in (users, pos, neg))
+    mean = (lambda v: v.mean()) if n_div is None else (lambda v: v.sum() / n_div)       # noqa: E731
     u = Mu[users]
-    graph = -Fn.logsigmoid((u * (Mi[pos] - Mi[neg])).sum(-1)).mean()
-    modal = torch.zeros((), dtype=F64)
+    xs = [(u * (Mi[pos] - Mi[neg])).sum(-1)]
+    graph = mean(-Fn.logsigmoid(xs[0]))
+    modal = torch.zeros((), dtype=Mu.dtype)
     if reg > 0:
         for emb, w, _ in (TEXT, IMAGE):
             if emb in P:
                 diff = (P[emb][pos] - P[emb][neg]) @ P[w].T
-                modal = modal - Fn.logsigmoid((u * diff).sum(-1)).mean()
+                xs.append((u * diff).sum(-1))
+                modal = modal + mean(-Fn.logsigmoid(xs[-1]))
+    if args is not None:
+        args.extend(x.detach().numpy() for x in xs)
     return (graph, reg * modal), Mu, Mi
 
 

@@ -37,21 +37,40 @@ def forward_f64(Eu0, Ei0, A, factors, n_layers):
     return sum(Eu), sum(Ei), sum(Gu), sum(Gi)
 
 
-def losses_f64(Eu0, Ei0, A, factors, uids, pos, neg, n_layers, temp, lambda1, lambda2):
-    """-> ((bpr, cl, reg), E_u, E_i, (positive scores of the user side, of the item side) before the clamp)"""
+def _lse_eps(s):
+    """log(sum_k exp(s_k) + 1e-8) per row: as written in float64 (the reference's form); with the largest term taken out in
+    any narrower type, where exp(s) itself may overflow"""
+    if s.dtype == F64:
+        return torch.log(torch.exp(s).sum(1) + 1e-8)
+    m = s.detach().max(1).values.clamp_min(float(np.log(1e-8)))
+    return m + torch.log(torch.exp(s - m[:, None]).sum(1) + 1e-8 * torch.exp(-m))
+
+
+def losses_f64(Eu0, Ei0, A, factors, uids, pos, neg, n_layers, temp, lambda1, lambda2, valid=None):
+    """-> ((bpr, cl, reg), E_u, E_i, (positive scores of the user side, of the item side) before the clamp).
+    ``valid`` = (vu, vp, vq), bool [n] each: the ids the kernel does not skip (the others are out of range and are not looked
+    up).  Each id is skipped on its own: the BPR term of a pair needs its three ids, the log-sum-exp and the positive score of
+    a user or an item that id alone; n and 2 n stay the divisors"""
     Eu, Ei, Gu, Gi = forward_f64(Eu0, Ei0, A, factors, n_layers)
     uids, pos, neg = (torch.as_tensor(np.asarray(a), dtype=torch.int64) for a in (uids, pos, neg))
+    if valid is None:
+        mean = lambda v, w: v.mean()                                   # noqa: E731
+        wu = wi = wb = None
+    else:
+        vu, vp, vq = (torch.as_tensor(np.asarray(v), dtype=torch.bool) for v in valid)
+        uids, pos, neg = torch.where(vu, uids, 0), torch.where(vp, pos, 0), torch.where(vq, neg, 0)
+        wu, wi, wb = vu.to(Eu.dtype), torch.cat([vp, vq]).to(Eu.dtype), (vu & vp & vq).to(Eu.dtype)
+        mean = lambda v, w: (v * w).sum() / len(v)                     # noqa: E731
     iids = torch.cat([pos, neg])
-    cl = torch.zeros((), dtype=F64)
+    cl = torch.zeros((), dtype=Eu.dtype)
     ps_u = ps_i = None
     if lambda1 > 0:
-        neg_score = torch.log(torch.exp(Gu[uids] @ Eu.T / temp).sum(1) + 1e-8).mean() \
-            + torch.log(torch.exp(Gi[iids] @ Ei.T / temp).sum(1) + 1e-8).mean()
+        neg_score = mean(_lse_eps(Gu[uids] @ Eu.T / temp), wu) + mean(_lse_eps(Gi[iids] @ Ei.T / temp), wi)
         ps_u, ps_i = (Gu[uids] * Eu[uids]).sum(1) / temp, (Gi[iids] * Ei[iids]).sum(1) / temp
-        pos_score = torch.clamp(ps_u, -5.0, 5.0).mean() + torch.clamp(ps_i, -5.0, 5.0).mean()
+        pos_score = mean(torch.clamp(ps_u, -5.0, 5.0), wu) + mean(torch.clamp(ps_i, -5.0, 5.0), wi)
         cl = lambda1 * (neg_score - pos_score)
     x = (Eu[uids] * Ei[pos]).sum(-1) - (Eu[uids] * Ei[neg]).sum(-1)
-    bpr = -torch.nn.functional.logsigmoid(x).mean()
+    bpr = mean(-torch.nn.functional.logsigmoid(x), wb)
     reg = lambda2 * ((Eu0 ** 2).sum() + (Ei0 ** 2).sum())
     return (bpr, cl, reg), Eu, Ei, (ps_u, ps_i)
 

@@ -70,15 +70,19 @@ def forward_f64(Eu, Ei, R1, R2t, n_layers):
     return su / (n_layers + 1), si / (n_layers + 1)
 
 
-def losses_f64(Eu, Ei, W, b, R1, R2t, users, items, ku, ki, n_layers, dropout, reg):
-    """-> ((cosine part, reg part), M_u, M_i) of one step (SelfCF.py:205-233); ku / ki: [n, d] keep flags of the targets"""
+def losses_f64(Eu, Ei, W, b, R1, R2t, users, items, ku, ki, n_layers, dropout, reg, n_div=None):
+    """-> ((cosine part, reg part), M_u, M_i) of one step (SelfCF.py:205-233); ku / ki: [n, d] keep flags of the targets;
+    ``n_div``: the divisor of the two means when it is not the number of rows handed in (rows the kernel skips leave n)"""
     Mu, Mi = forward_f64(Eu, Ei, R1, R2t, n_layers)
     users, items = (torch.as_tensor(np.asarray(a), dtype=torch.int64) for a in (users, items))
     u, i = Mu[users], Mi[items]
-    tu = (u * t64(ku) / (1.0 - dropout)).detach()
-    ti = (i * t64(ki) / (1.0 - dropout)).detach()
+    tu = (u * torch.as_tensor(np.asarray(ku), dtype=u.dtype) / (1.0 - dropout)).detach()
+    ti = (i * torch.as_tensor(np.asarray(ki), dtype=i.dtype) / (1.0 - dropout)).detach()
     pu, pi = u @ W.T + b, i @ W.T + b
-    cos = -cosine(pu, ti).mean() / 2 - cosine(pi, tu).mean() / 2
+    if n_div is None:
+        cos = -cosine(pu, ti).mean() / 2 - cosine(pi, tu).mean() / 2
+    else:
+        cos = -cosine(pu, ti).sum() / n_div / 2 - cosine(pi, tu).sum() / n_div / 2
     regl = reg * 0.5 * ((u ** 2).sum() + (i ** 2).sum())
     return (cos, regl), Mu, Mi
 

@@ -455,3 +455,194 @@ def test_a_too_wide_feature_table_raises(tiny_dir, monkeypatch, tmp_path):
     np.savez(os.path.join(tiny_dir, "tiny.img.npz"), features=np.zeros((96, 4097), np.float32))
     with pytest.raises(NotImplementedError, match="feature width <= 4096"):
         _model(tiny_dir)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 10. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-4, 2e-5        # _check_grad's
+
+
+def _twin_run(c, m, rows, dtype, reg, n_div=None):
+    """the twin in ``dtype`` on the batch rows ``rows`` of ``c``, on the model's own adjacency values
+    -> ((graph, modal, reg part), {name: float64 gradient}, targets' norms (user table, item table))"""
+    import torch
+    d, I = c["d"], c["I"]
+    val = m.adj.val.cpu().numpy()[:len(c["items"])]
+    P = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in c["P"].items()}
+    R = torch.tensor(T.dense_block(c["rowptr"], c["items"], I, val), dtype=dtype)
+    keeps = {k: v[rows][:, :d] for k, v in c["keeps"].items()}
+    comps, Mu, Mi = T.losses_f64(P, R, c["users"][rows], c["its"][rows], keeps, c["L"], 0.3, reg, 2.0, n_div=n_div)
+    sum(comps).backward()
+    with torch.no_grad():
+        tn = ((Mu[c["users"][rows]] * torch.tensor(keeps["u"], dtype=dtype)).norm(dim=1).numpy() / 0.7,
+              (Mi[c["its"][rows]] * torch.tensor(keeps["i"], dtype=dtype)).norm(dim=1).numpy() / 0.7)
+    G = {k: np.zeros(v.shape) if v.grad is None else v.grad.numpy().astype(np.float64) for k, v in P.items()}
+    return [x.item() for x in comps], G, tn
+
+
+def _edge_compare(c, what, reg=0.1, ok=None, floor=None, widen=False, m=None):
+    """The device step on the batch of ``c`` against the float64 twin on the rows ``ok`` (all when None) with n as the divisor.
+    ``floor`` ({name: gradient}): each tensor's scale is max|want| or that tensor at a batch without the exact cancellation,
+    whichever is more.  ``widen``: allow max(ATOL * scale, 4 x the error of the same twin in float32 on the CPU), both printed"""
+    import torch
+    n = c["n"]
+    ok = np.ones(n, bool) if ok is None else ok
+    m = _detached(c, reg) if m is None else m
+    comps, G, _ = _twin_run(c, m, ok, torch.float64, reg, n_div=n)
+    comps32, G32, _ = _twin_run(c, m, ok, torch.float32, reg, n_div=n) if widen else (comps, None, None)
+    loss = m.gradient_step(c["users"], c["its"], target_keep=_target_keep(c)).cpu().numpy()
+    want, want32 = (np.array(x + [sum(x)], np.float64) for x in (comps, comps32))
+    print(what, "loss", loss, "twin", want, "abs err", np.abs(loss - want), "fp32-CPU err", np.abs(want32 - want))
+    assert np.isfinite(loss).all()
+    assert np.all(np.abs(loss - want) <= np.maximum(1e-5 * np.abs(want), 4 * np.abs(want32 - want)))
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    assert set(got) == set(G)
+    for k in G:                       # every tensor is measured before the assertion
+        scale = float(np.abs(G[k]).max())
+        if floor is not None:
+            scale = max(scale, float(np.abs(floor[k]).max()))
+        err = np.abs(got[k].astype(np.float64) - G[k])
+        atol = ATOL * scale
+        if widen:
+            err32 = float(np.abs(G32[k] - G[k]).max())
+            atol = max(atol, 4 * err32)
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}, fp32-CPU err {err32:.3e}")
+        else:
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}")
+        assert np.isfinite(got[k]).all(), k
+        assert np.all(err <= atol + RTOL * np.abs(G[k])), (what, k, float(err.max()), scale)
+    return loss, got, m
+
+
+@pytest.mark.parametrize("d", [64, 20])
+@pytest.mark.parametrize("n", [15, 16, 17, 63, 65])
+def test_batch_sizes_around_the_tiles(n, d):
+    """below, at and above a wavefront's 16 rows and a workgroup's 64 (n = 64 is in STEP_CASES)"""
+    c = _step_case(n, 2, d, 100, 37, 1000 + n + d)
+    assert len(np.unique(c["users"])) < n and len(np.unique(c["its"])) < n and (c["users"] == 47).any() and (c["its"] == 39).any()
+    _edge_compare(c, f"n = {n}, d = {d}")
+
+
+def test_full_batch_at_four_layers():
+    """n = 2048 at L = SKR_BM3_MAX_LAYERS = 4 on a 2100 x 2100 graph, both modalities: 32 batch workgroups, 128 MFMA trips of the
+    projections' weight gradient; then the same call again: the same bits"""
+    import time
+    import torch
+    from skrec import _hip
+    t0 = time.time()
+    assert _hip.SKR_BM3_MAX_LAYERS == 4 and _hip.SKR_BM3_MAX_BATCH == 2048
+    c = _step_case(2048, 4, 64, 100, 37, 2100, U=2100, I=2100)
+    loss, _, m = _edge_compare(c, "n = 2048", widen=True)
+    g1, M1 = m._grad.clone(), m.M.clone()
+    m._work.fill_(255)
+    loss2 = m.gradient_step(c["users"], c["its"], target_keep=_target_keep(c)).cpu().numpy()
+    assert np.array_equal(loss.view(np.uint32), loss2.view(np.uint32)) and torch.equal(g1, m._grad) and torch.equal(M1, m.M)
+    print("full batch: wall time", time.time() - t0)
+
+
+@pytest.mark.parametrize("n", [37, 300])
+@pytest.mark.parametrize("which", ["user", "item"])
+def test_one_id_in_every_row(which, n):
+    """the longest segment: all n ranks of one list name one id, so one wavefront of seg_add (and, for the item, of the
+    feature rows' seg_rows) walks them all and the rank kernel counts n equal keys; the node's flags are one row repeated.
+    The scales are floored by the same batch with its random ids"""
+    import torch
+    c = _step_case(n, 2, 64, 100, 37, 3000 + n)
+    m = _detached(c, 0.1)
+    floor = _twin_run(c, m, np.ones(n, bool), torch.float64, 0.1, n_div=n)[1]
+    if which == "user":
+        c["users"][:] = c["users"][n - 1]
+        c["keeps"]["u"][:] = c["keeps"]["u"][n - 1]
+    else:
+        c["its"][:] = c["its"][3]
+        for k in "itv":
+            c["keeps"][k][:] = c["keeps"][k][3]
+    _edge_compare(c, f"one {which}, n = {n}", floor=floor, m=m)
+
+
+def test_ids_out_of_range_contribute_nothing():
+    """the result is that of the batch without those rows with n = 70 as the divisor of every cosine mean; the regulariser is
+    that of the whole tables, as ever"""
+    U, I, n = 48, 40, 70
+    c = _step_case(n, 2, 64, 100, 37, 4000)
+    users, its = c["users"], c["its"]
+    users[3], its[17], users[40], its[40], users[69] = U, -1, -7, I, 2 ** 31 - 1
+    ok = (users >= 0) & (users < U) & (its >= 0) & (its < I)
+    assert ok.sum() == 66
+    _edge_compare(c, "ids out of range", ok=ok)
+    # the device's own result on the filtered batch: without the regulariser every gradient, and every sum of cosines
+    # (2 - graph, 4 cl_weight - modal), scales by 66 / 70; the losses are compared as they are, at their own rtol
+    m = _detached(c, 0.0)
+    loss = m.gradient_step(users, its, target_keep=_target_keep(c)).cpu().numpy()
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    loss2 = m.gradient_step(users[ok], its[ok], target_keep=tuple(k[ok] for k in _target_keep(c))).cpu().numpy()
+    got2 = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    assert loss[2] == 0 and loss2[2] == 0
+    np.testing.assert_allclose(loss[:2], np.array([2.0, 8.0]) * (4 / 70) + loss2[:2] * (66 / 70), rtol=1e-5)
+    for k in got:
+        np.testing.assert_allclose(got[k], got2[k] * np.float32(66 / 70), rtol=RTOL, atol=ATOL * np.abs(got[k]).max(), err_msg=k)
+
+
+def test_an_empty_batch_writes_nothing():
+    import ctypes
+    import torch
+    from skrec import _hip
+    c = _step_case(17, 2, 64, 100, 37, 5000)
+    m = _detached(c)
+    loss = torch.full((4,), 7.0, device="cuda")
+    ids = torch.zeros(4, dtype=torch.int32, device="cuda")
+    m._prev_items = ids               # rows that a step would clear first
+    a = m._step_args(ids, ids, None, loss)
+    assert a.n_clear == 4
+    a.n = 0
+    m._grad.fill_(3.0)
+    m._work.fill_(5)
+    tabs = [m.M, m._G, m._ping[0], m._ping[1]]
+    for t in tabs:
+        t.fill_(2.0)
+    before = [t.clone() for t in tabs] + [m._work.clone(), m._flat.clone()]
+    _hip.check(_hip.lib().skr_bm3_step(ctypes.byref(a), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and (m._grad == 3.0).all()
+    assert all(torch.equal(x, y) for x, y in zip(before, tabs + [m._work, m._flat]))
+    # through the class: a zero loss, a zero gradient whatever the last step left there, nothing left to clear
+    m._prev_items = None
+    m._grad.zero_()
+    m.gradient_step(c["users"], c["its"])
+    assert m._grad.any() and m._prev_items is not None
+    z, step = np.zeros(0, np.int32), m._step
+    loss = m.gradient_step(z, z)
+    assert loss.shape == (4,) and not loss.any() and not m._grad.any() and m._prev_items is None and m._step == step
+    # train_step: the zero gradient through Adam, as MGCN, LATTICE and SLMRec do it; with no moments yet nothing moves
+    m.gradient_step(c["users"], c["its"])
+    flat = m._flat.clone()
+    assert not m.train_step(z, z).any()
+    assert torch.equal(flat, m._flat)
+
+
+def test_a_predictor_output_of_exact_zeros():
+    """W = 0 and b = 0: every P row is zero, |P| takes the 1e-8 clamp, every cosine is 0 (graph = 2, modal = 4 cl_weight) and the
+    predictor's gradient is of the order 1e8 / n, finite"""
+    c = _step_case(70, 2, 64, 100, 37, 6000)
+    c["P"]["predictor.weight"][:] = 0
+    c["P"]["predictor.bias"][:] = 0
+    loss, got, _ = _edge_compare(c, "P = 0", widen=True)
+    assert loss[0] == 2 and loss[1] == 8 and np.abs(got["predictor.bias"]).max() > 1e4
+
+
+def test_target_rows_with_a_norm_under_the_clamp():
+    """the isolated user's and the isolated item's embedding rows scaled by 1e-9: their target rows (row 1 of the batch) have
+    0 < |t| < 1e-8, the max(|t|, 1e-8) branch of the cosine; the reference is the twin's own clamp"""
+    import torch
+    c = _step_case(70, 2, 64, 100, 37, 6001)
+    U, I = c["U"], c["I"]
+    assert c["users"][1] == U - 1 and c["its"][1] == I - 1 and (c["users"] == U - 1).sum() == 1 and (c["its"] == I - 1).sum() == 1
+    c["keeps"]["u"][1], c["keeps"]["i"][1] = 1, 1
+    c["P"]["user_embedding.weight"][U - 1] *= np.float32(1e-9)
+    c["P"]["item_id_embedding.weight"][I - 1] *= np.float32(1e-9)
+    m = _detached(c, 0.1)
+    tn = _twin_run(c, m, np.ones(70, bool), torch.float64, 0.1)[2]
+    print("target norms of row 1:", tn[0][1], tn[1][1])
+    assert 0 < tn[0][1] < 1e-8 and 0 < tn[1][1] < 1e-8
+    _edge_compare(c, "small targets", widen=True, m=m)

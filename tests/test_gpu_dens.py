@@ -295,3 +295,234 @@ def test_more_than_one_rank_raises(tiny_dir, monkeypatch, tmp_path):
     z = np.zeros(2049, np.int32)
     with pytest.raises(NotImplementedError, match="at most 2048"):
         m.gradient_step(z, z, np.zeros((2049, 6), np.int32), 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-4, 2e-5        # _check_grad's
+
+
+def _twin_run(c, rows, gamma, l2, dtype, choices=None, n_div=None):
+    """the twin (selection weight 0.75) in ``dtype`` on the batch rows ``rows`` -> (step_f64's dict, {name: float64 gradient})"""
+    import torch
+    P = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in c["P"].items()}
+    A = torch.tensor(T.dense_adjacency(c["rowptr"], c["items"], c["I"]), dtype=dtype)
+    r = T.step_f64(P, A, c["users"][rows], c["pos"][rows], c["cand"][rows], c["H"], 0.75, gamma, l2, choices=choices, n_div=n_div)
+    r["total"].backward()
+    return r, {k: np.zeros(v.shape) if v.grad is None else v.grad.numpy().astype(np.float64) for k, v in P.items()}
+
+
+def _edge_compare(c, what, gamma=0.3, l2=1e-2, ok=None, force=(), floor=None, widen=False, m=None):
+    """The device step on the batch of ``c`` against the float64 twin on the rows ``ok`` (all of them when None) with n as the
+    divisor, every choice forced to the twin's.  ``force``: (row, hop, the twin's choice, the device's sel_in entry) for entries
+    that are handed in differently.  ``floor`` ({name: gradient}): a batch at which exact cancellation leaves gradients of
+    rounding size takes each tensor's scale from max|want| or from that tensor at a batch without the cancellation, whichever is
+    more.  ``widen``: allow max(ATOL * scale, 4 x the error of the same twin in float32 on the CPU), both printed."""
+    import torch
+    n, H = c["n"], c["H"]
+    ok = np.ones(n, bool) if ok is None else ok
+    chosen = None
+    if force:
+        chosen = np.full((n, H + 1), -1, np.int64)
+        for b, h, k, _ in force:
+            chosen[b, h] = k
+        chosen = chosen[ok]
+    r, G = _twin_run(c, ok, gamma, l2, torch.float64, choices=chosen, n_div=n)
+    sel_in = np.zeros((n, H + 1), np.int32)
+    sel_in[ok] = r["choices"]
+    for b, h, k, dev_value in force:
+        assert ok[b] and sel_in[b, h] == k
+        sel_in[b, h] = dev_value
+    r32, G32 = _twin_run(c, ok, gamma, l2, torch.float32, choices=r["choices"], n_div=n) if widen else (r, None)
+    m = _detached(c, gamma, l2) if m is None else m
+    loss, sel = m.gradient_step(c["users"], c["pos"], c["cand"], 1, sel_in=sel_in)
+    loss, sel = loss.cpu().numpy(), sel.cpu().numpy()
+    want, want32 = (np.array([x["mf"].item(), x["emb"].item(), x["total"].item()], np.float64) for x in (r, r32))
+    print(what, "loss", loss, "twin", want, "abs err", np.abs(loss - want), "fp32-CPU err", np.abs(want32 - want))
+    assert np.isfinite(loss).all() and np.array_equal(sel[ok], r["choices"])
+    assert np.all(np.abs(loss - want) <= np.maximum(1e-5 * np.abs(want), 4 * np.abs(want32 - want)))
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    for k in T.NAMES:                 # every tensor is measured before the assertion
+        scale = float(np.abs(G[k]).max())
+        if floor is not None:
+            scale = max(scale, float(np.abs(floor[k]).max()))
+        err = np.abs(got[k].astype(np.float64) - G[k])
+        atol = ATOL * scale
+        if widen:
+            err32 = float(np.abs(G32[k] - G[k]).max())
+            atol = max(atol, 4 * err32)
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}, fp32-CPU err {err32:.3e}")
+        else:
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}")
+        assert np.isfinite(got[k]).all(), k
+        assert np.all(err <= atol + RTOL * np.abs(G[k])), (what, k, float(err.max()), scale)
+    return loss, got, r, G, m
+
+
+@pytest.mark.parametrize("d", [64, 32])
+@pytest.mark.parametrize("n", [15, 16, 17, 63, 64, 65])
+def test_batch_sizes_around_the_tiles(n, d):
+    """below, at and above a wavefront's 16 rows and a workgroup's 64; H = 2, K = 6: 3 n (row, hop) pairs in the back kernel"""
+    c = _step_case(64, 96, n, 2, 6, d, 1000 + n + d)
+    assert len(np.unique(c["users"])) < n and len(np.unique(c["pos"])) < n and (c["cand"] == 95).any()
+    _edge_compare(c, f"n = {n}, d = {d}")
+
+
+def test_full_batch_at_every_maximum():
+    """n = 2048, H = SKR_DENS_MAX_HOPS = 3, K = SKR_DENS_MAX_NEGS = 16 on a 2100 x 2100 graph: 128 back chunks = SKR_DENS_MAX_WG,
+    512 select tiles; then the same call again: the same bits"""
+    import time
+    from skrec import _hip
+    t0 = time.time()
+    assert (_hip.SKR_DENS_MAX_HOPS, _hip.SKR_DENS_MAX_NEGS, _hip.SKR_DENS_MAX_BATCH) == (3, 16, 2048)
+    c = _step_case(2100, 2100, 2048, 3, 16, 64, 2100)
+    assert (2048 * 4 + 63) // 64 == 128             # SKR_DENS_MAX_WG of include/skrec_hip.h
+    loss, got, r, _, m = _edge_compare(c, "n = 2048", widen=True)
+    g1 = m._grad.clone()
+    m._work.fill_(255)
+    m._grad.fill_(3.0)
+    loss2, sel2 = m.gradient_step(c["users"], c["pos"], c["cand"], 1, sel_in=r["choices"])
+    assert np.array_equal(loss.view(np.uint32), loss2.cpu().numpy().view(np.uint32))
+    assert np.array_equal(g1.cpu().numpy().view(np.uint32), m._grad.cpu().numpy().view(np.uint32))
+    assert np.array_equal(sel2.cpu().numpy(), r["choices"])
+    print("full batch: wall time", time.time() - t0)
+
+
+@pytest.mark.parametrize("n", [37, 300])
+@pytest.mark.parametrize("which", ["user", "pos", "cand", "pos and cand"])
+def test_one_id_in_every_row(which, n):
+    """the longest segment: every rank of the user list, or n or all 2 n ranks of a hop's item list, name one id, so one
+    wavefront of seg_add walks them all and rank counts n (2 n) equal keys.  With one item on a side terms cancel exactly
+    (pos = cand: x1 = 0 in every row), so the scales come from the same users with the case's random items (``floor``)"""
+    import torch
+    c = _step_case(64, 96, n, 2, 6, 64, 3000 + n)
+    floor = _twin_run(c, np.ones(n, bool), 0.3, 1e-2, torch.float64, n_div=n)[1]
+    if which == "user":
+        c["users"][:] = c["users"][0]
+    if "pos" in which:
+        c["pos"][:] = c["pos"][3]
+    if "cand" in which:
+        c["cand"][:] = c["pos"][3] if "pos" in which else c["cand"][3, 1]
+    _edge_compare(c, f"one {which}, n = {n}", floor=floor)
+
+
+def test_ids_out_of_range_contribute_nothing():
+    """the result is that of the batch without those rows, with n = 70 as the divisor of mf and of emb; the candidates of a
+    skipped row get no gradient either"""
+    U, I, n = 64, 96, 70
+    c = _step_case(U, I, n, 2, 6, 64, 4000)
+    users, pos = c["users"], c["pos"]
+    users[3], pos[17], users[40], pos[40], users[69] = U, -1, -7, I, 2 ** 31 - 1
+    ok = (users >= 0) & (users < U) & (pos >= 0) & (pos < I)
+    assert ok.sum() == 66
+    loss, got, r, _, m = _edge_compare(c, "ids out of range", ok=ok)
+    # the device's own result on the filtered batch, scaled by 66 / 70
+    loss2, _ = m.gradient_step(users[ok], pos[ok], c["cand"][ok], 1, sel_in=r["choices"])
+    got2 = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    np.testing.assert_allclose(loss, loss2.cpu().numpy() * 66 / 70, rtol=1e-5)
+    for k in T.NAMES:
+        np.testing.assert_allclose(got[k], got2[k] * np.float32(66 / 70), rtol=RTOL, atol=ATOL * np.abs(got[k]).max(), err_msg=k)
+
+
+def test_candidates_out_of_range_are_zero_rows_and_sel_in_is_clamped():
+    """on rows that are otherwise valid: one candidate at n_items, one at -1, each forced to be the chosen one at one hop (the
+    pool and back kernels then meet selitem = -1), and one sel_in entry of n_negs + 3, which selects candidate n_negs - 1"""
+    U, I, n, K = 64, 96, 70, 6
+    c = _step_case(U, I, n, 2, K, 64, 4001)
+    c["cand"][5, 2], c["cand"][66, 0] = I, -1
+    force = [(5, 1, 2, 2), (66, 0, 0, 0), (20, 2, K - 1, K + 3)]
+    _, _, r, _, m = _edge_compare(c, "candidates out of range", force=force)
+    assert r["choices"][20, 2] == K - 1              # (sel_out equals the twin's choices: the entry came back clamped)
+    # left to the kernel, a candidate out of range scores an exact 0 like the twin's zero row
+    _, own = m.gradient_step(c["users"], c["pos"], c["cand"], 1)
+    mg, best, second = T.margins(r["scores"], r["scale"], np.where((c["cand"] >= 0) & (c["cand"] < I), c["cand"], -1))
+    gotc = np.take_along_axis(np.where((c["cand"] >= 0) & (c["cand"] < I), c["cand"], -1), own.cpu().numpy().astype(np.int64), 1)
+    sure = mg >= MARGIN
+    print("groups under the margin:", int((~sure).sum()), "of", sure.size)
+    assert (~sure).sum() <= 0.005 * sure.size
+    assert np.array_equal(gotc[sure], best[sure]) and ((gotc == best) | (gotc == second))[~sure].all()
+
+
+def test_an_empty_batch_writes_nothing():
+    import ctypes
+    import torch
+    from skrec import _hip
+    c = _step_case(64, 96, 17, 2, 6, 64, 5000)
+    m = _detached(c, 0.3)
+    loss = torch.full((3,), 7.0, device="cuda")
+    ids = torch.zeros(4, dtype=torch.int32, device="cuda")
+    cand = torch.zeros(4 * 6, dtype=torch.int32, device="cuda")
+    sel = torch.full((4, 3), 9, dtype=torch.int32, device="cuda")
+    a = m._step_args(ids, ids, cand, None, sel, loss, 1)
+    a.n = 0
+    m._grad.fill_(3.0)
+    m._work.fill_(5)
+    tabs = m._hops + m._G + [m._ping]
+    for t in tabs:
+        t.fill_(2.0)
+    before = [t.clone() for t in tabs] + [m._work.clone(), m._flat.clone()]
+    _hip.check(_hip.lib().skr_dens_step(ctypes.byref(a), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and (m._grad == 3.0).all() and (sel == 9).all()
+    assert all(torch.equal(x, y) for x, y in zip(before, tabs + [m._work, m._flat]))
+    # through the class: a zero loss, a zero gradient whatever the last step left there
+    m.gradient_step(c["users"], c["pos"], c["cand"], 1)
+    assert m._grad.any()
+    z = np.zeros(0, np.int32)
+    loss, sel = m.gradient_step(z, z, np.zeros((0, 6), np.int32), 1)
+    assert loss.shape == (3,) and not loss.any() and not m._grad.any() and sel.shape == (0, 3)
+    # train_step: the zero gradient through Adam, as MGCN, LATTICE and SLMRec do it; with no moments yet nothing moves
+    m.gradient_step(c["users"], c["pos"], c["cand"], 1)
+    flat = m._flat.clone()
+    assert not m.train_step(z, z, np.zeros((0, 6), np.int32), 1).any()
+    assert torch.equal(flat, m._flat)
+
+
+def _scaled_to(c, names, values, target, sign):
+    """the parameters ``names`` of ``c`` scaled by one positive factor so that max(values) = target (sign > 0) or
+    min(values) = -target (sign < 0); ``values`` must be linear in that factor"""
+    s = target / (values.max() if sign > 0 else -values.min())
+    assert s > 0
+    for k in names:
+        c["P"][k] = (c["P"][k].astype(np.float64) * s).astype(np.float32)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5])
+def test_softplus_arguments_of_a_hundred(k, sign):
+    """the embeddings scaled until x_k, the argument of the k-th softplus term (x1 = u.N - u.P, x2 .. x5 the gated ones), reaches
+    +100 (softplus_f's exp(-|x|) underflows, sigmoid_f(x) = 1 in fp32) or -100 (expf(100) = inf inside sigmoid_f).  x_k is
+    quadratic in the factor up to what the gates and the choices move, so the factor is settled in a few rounds"""
+    import torch
+    c = _step_case(64, 96, 100, 2, 6, 64, 6000)
+    rows = np.ones(100, bool)
+    for _ in range(12):
+        x = _twin_run(c, rows, 0.3, 1e-2, torch.float64)[0]["x"][k - 1]
+        ext = x.max() if sign > 0 else -x.min()
+        assert ext > 0
+        if 99.5 < ext < 100.5:
+            break
+        _scaled_to(c, ("user_embed", "item_embed"), np.sqrt(np.abs(x)) * np.sign(x), 10.0, sign)
+    x = _twin_run(c, rows, 0.3, 1e-2, torch.float64)[0]["x"]
+    print("x1 .. x5: min", x.min(1), "max", x.max(1))
+    ext = x[k - 1].max() if sign > 0 else -x[k - 1].min()
+    assert 99 < ext < 101 and np.float32(1) + np.exp(np.float32(-ext)) == 1
+    _edge_compare(c, f"x{k} of {sign * 100}", widen=True)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_gate_pre_activations_of_a_hundred(sign):
+    """user_gate and item_gate scaled until a = item_gate(p) + user_gate(s) reaches +-100, then pos_gate and neg_gate until
+    z = neg_gate(c) + pos_gate(p gp) does (both are linear in their gates' factor): sigmoid_f at both ends, gp (1 - gp) = 0"""
+    import torch
+    c = _step_case(64, 96, 100, 2, 6, 64, 6001)
+    rows = np.ones(100, bool)
+    gates = lambda *g: tuple(f"{x}.{p}" for x in g for p in ("weight", "bias"))      # noqa: E731
+    _scaled_to(c, gates("user_gate", "item_gate"), _twin_run(c, rows, 0.3, 1e-2, torch.float64)[0]["a"][:, :, :64], 100.0, sign)
+    _scaled_to(c, gates("pos_gate", "neg_gate"), _twin_run(c, rows, 0.3, 1e-2, torch.float64)[0]["z"], 100.0, sign)
+    r = _twin_run(c, rows, 0.3, 1e-2, torch.float64)[0]
+    print("a: min", r["a"].min(), "max", r["a"].max(), "z: min", r["z"].min(), "max", r["z"].max())
+    for v in (r["a"], r["z"]):
+        assert 99 < (v.max() if sign > 0 else -v.min()) < 101
+    _edge_compare(c, f"gates of {sign * 100}", widen=True)

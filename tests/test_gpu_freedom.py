@@ -473,3 +473,190 @@ def test_limits_raise(golden, tiny_dir, monkeypatch, tmp_path):
     np.savez(os.path.join(tiny_dir, "tiny.txt.npz"), features=np.zeros((96, 4097), np.float32))
     with pytest.raises(NotImplementedError, match="feature width <= 4096.*text.*4097"):
         _model(tiny_dir)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-4, 2e-5        # _check_grad's
+EDGE = (2, 1, 64, 100, 37)     # Lu, Lm, d, F_image, F_text of the small edge cases
+
+
+def _pruned_model(c, reg):
+    m = _detached(c, reg)
+    m.prune(0, keep=c["keep"])
+    return m
+
+
+def _twin_run(c, m, rows, dtype, reg, n_div=None):
+    """the twin in ``dtype`` on the batch rows ``rows`` of ``c``, on the model's own item graph
+    -> ((graph, modal), {name: float64 gradient}, [x_g, x_text, x_image])"""
+    import torch
+    I = c["I"]
+    P = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in c["P"].items()}
+    R = torch.tensor(T.pruned_block(c["rowptr"], c["items"], I, c["keep"]), dtype=dtype)
+    S = torch.tensor(T.dense_graph(T.csr_rows(m.mm_adj.rowptr.cpu().numpy()), m.mm_adj.col.cpu().numpy()[:m.mm_adj.nnz],
+                                   m.mm_adj.val.cpu().numpy()[:m.mm_adj.nnz], I), dtype=dtype)
+    args = []
+    (g, mm), _, _ = T.losses_f64(P, R, S, c["users"][rows], c["pos"][rows], c["neg"][rows], c["Lu"], c["Lm"], reg, n_div=n_div, args=args)
+    (g + mm).backward()
+    return [g.item(), mm.item()], {k: np.zeros(v.shape) if v.grad is None else v.grad.numpy().astype(np.float64) for k, v in P.items()}, args
+
+
+def _edge_compare(c, what, reg=0.5, ok=None, floor=None, widen=False, m=None):
+    """The device step on the batch of ``c`` against the float64 twin on the rows ``ok`` (all when None) with n as the divisor.
+    ``floor`` ({name: gradient}): each tensor's scale is max|want| or that tensor at a batch without the exact cancellation,
+    whichever is more.  ``widen``: allow max(ATOL * scale, 4 x the error of the same twin in float32 on the CPU), both printed"""
+    import torch
+    n = c["n"]
+    ok = np.ones(n, bool) if ok is None else ok
+    m = _pruned_model(c, reg) if m is None else m
+    comps, G, _ = _twin_run(c, m, ok, torch.float64, reg, n_div=n)
+    comps32, G32, _ = _twin_run(c, m, ok, torch.float32, reg, n_div=n) if widen else (comps, None, None)
+    _dirty(m)
+    loss = m.gradient_step(c["users"], c["pos"], c["neg"]).cpu().numpy()
+    want, want32 = (np.array(x + [sum(x)], np.float64) for x in (comps, comps32))
+    print(what, "loss", loss, "twin", want, "abs err", np.abs(loss - want), "fp32-CPU err", np.abs(want32 - want))
+    assert np.isfinite(loss).all()
+    assert np.all(np.abs(loss - want) <= np.maximum(1e-5 * np.abs(want), 4 * np.abs(want32 - want)))
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    assert set(got) == set(G)
+    for k in G:                       # every tensor is measured before the assertion
+        scale = float(np.abs(G[k]).max())
+        if floor is not None:
+            scale = max(scale, float(np.abs(floor[k]).max()))
+        err = np.abs(got[k].astype(np.float64) - G[k])
+        atol = ATOL * scale
+        if widen:
+            err32 = float(np.abs(G32[k] - G[k]).max())
+            atol = max(atol, 4 * err32)
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}, fp32-CPU err {err32:.3e}")
+        else:
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}")
+        assert np.isfinite(got[k]).all(), k
+        assert np.all(err <= atol + RTOL * np.abs(G[k])), (what, k, float(err.max()), scale)
+    return loss, got, m
+
+
+@pytest.mark.parametrize("d", [64, 20])
+@pytest.mark.parametrize("n", [15, 16, 17, 64, 65])
+def test_batch_sizes_around_the_tiles(n, d):
+    """below, at and above 16 and 64 rows (n = 63 is in STEP_CASES): 4 rows per batch workgroup, 16 ranks per feature-gradient tile"""
+    c = _step_case(n, 2, 1, d, 100, 37, seed=1000 + n + d)
+    assert len(np.unique(c["users"])) < n and len(np.unique(c["pos"])) < n and np.isin(c["pos"], c["neg"]).any()
+    _edge_compare(c, f"n = {n}, d = {d}")
+
+
+def test_full_batch_at_four_layers_each():
+    """n = 2048 at n_ui_layers = n_mm_layers = SKR_FREEDOM_MAX_LAYERS = 4 on a 2100 x 2100 graph, both modalities: the 4096 ranks
+    of the item list, 128 trips of the float64 weight-gradient sum; then the same call again: the same bits"""
+    import time
+    import torch
+    from skrec import _hip
+    t0 = time.time()
+    assert _hip.SKR_FREEDOM_MAX_LAYERS == 4 and _hip.SKR_FREEDOM_MAX_BATCH == 2048
+    c = _step_case(2048, 4, 4, 64, 100, 37, seed=2100, U=2100, I=2100)
+    loss, _, m = _edge_compare(c, "n = 2048", widen=True)
+    g1, M1 = m._grad.clone(), m.M.clone()
+    m._work.fill_(255)
+    loss2 = m.gradient_step(c["users"], c["pos"], c["neg"]).cpu().numpy()
+    assert np.array_equal(loss.view(np.uint32), loss2.view(np.uint32)) and torch.equal(g1, m._grad) and torch.equal(M1, m.M)
+    print("full batch: wall time", time.time() - t0)
+
+
+@pytest.mark.parametrize("n", [37, 300])
+@pytest.mark.parametrize("which", ["user", "item"])
+def test_one_id_in_every_row(which, n):
+    """the longest segment: all n ranks of the user list, or all 2 n ranks of pos || neg, name one id, so one wavefront of
+    seg_add (and of the feature rows' seg_rows) walks them all and the rank kernel counts n (2 n) equal keys.  With pos = neg
+    every argument is 0 and every item-side gradient cancels exactly: the scales are floored by the same users with the case's
+    random items"""
+    import torch
+    c = _step_case(n, *EDGE, seed=3000 + n)
+    m = _pruned_model(c, 0.5)
+    floor = _twin_run(c, m, np.ones(n, bool), torch.float64, 0.5, n_div=n)[1]
+    if which == "user":
+        c["users"][:] = c["users"][n - 1]
+    else:
+        c["pos"][:] = c["pos"][3]
+        c["neg"][:] = c["pos"][3]
+    loss, _, _ = _edge_compare(c, f"one {which}, n = {n}", floor=floor, m=m)
+    if which == "item":
+        np.testing.assert_allclose(loss, np.log(2.0) * np.array([1.0, 1.0, 2.0]), rtol=1e-5)
+
+
+def test_ids_out_of_range_contribute_nothing():
+    """the result is that of the batch without those rows, with n = 70 as the divisor of the three means"""
+    U, I, n = 48, 40, 70
+    c = _step_case(n, *EDGE, seed=4000)
+    users, pos, neg = c["users"], c["pos"], c["neg"]
+    users[3], pos[17], users[40], neg[40], neg[69] = U, -1, -7, I, 2 ** 31 - 1
+    ok = (users >= 0) & (users < U) & (pos >= 0) & (pos < I) & (neg >= 0) & (neg < I)
+    assert ok.sum() == 66
+    loss, got, m = _edge_compare(c, "ids out of range", ok=ok)
+    # the device's own result on the filtered batch, scaled by 66 / 70
+    loss2 = m.gradient_step(users[ok], pos[ok], neg[ok]).cpu().numpy()
+    got2 = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    np.testing.assert_allclose(loss, loss2 * 66 / 70, rtol=1e-5)
+    for k in got:
+        np.testing.assert_allclose(got[k], got2[k] * np.float32(66 / 70), rtol=RTOL, atol=ATOL * np.abs(got[k]).max(), err_msg=k)
+
+
+def test_an_empty_batch_writes_nothing():
+    import ctypes
+    import torch
+    from skrec import _hip
+    c = _step_case(17, *EDGE, seed=5000)
+    m = _pruned_model(c, 0.5)
+    loss = torch.full((3,), 7.0, device="cuda")
+    ids = torch.zeros(4, dtype=torch.int32, device="cuda")
+    m._prev_items = ids               # rows that a step would clear first
+    a = m._step_args(ids, ids, ids, loss)
+    assert a.n_clear == 4
+    a.n = 0
+    m._grad.fill_(3.0)
+    m._work.fill_(5)
+    tabs = [m.M, m._G] + [p for p in m._ping if p is not None]
+    for t in tabs:
+        t.fill_(2.0)
+    before = [t.clone() for t in tabs] + [m._work.clone(), m._flat.clone()]
+    _hip.check(_hip.lib().skr_freedom_step(ctypes.byref(a), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and (m._grad == 3.0).all()
+    assert all(torch.equal(x, y) for x, y in zip(before, tabs + [m._work, m._flat]))
+    # through the class: a zero loss, a zero gradient whatever the last step left there, nothing left to clear
+    m._prev_items = None
+    m._grad.zero_()
+    m.gradient_step(c["users"], c["pos"], c["neg"])
+    assert m._grad.any() and m._prev_items is not None
+    z = np.zeros(0, np.int32)
+    loss = m.gradient_step(z, z, z)
+    assert loss.shape == (3,) and not loss.any() and not m._grad.any() and m._prev_items is None
+    # train_step: the zero gradient through Adam, as MGCN, LATTICE and SLMRec do it; with no moments yet nothing moves
+    m.gradient_step(c["users"], c["pos"], c["neg"])
+    flat = m._flat.clone()
+    assert not m.train_step(z, z, z).any()
+    assert torch.equal(flat, m._flat)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_bpr_arguments_of_a_hundred(sign):
+    """the embeddings scaled (x_g is quadratic in the factor) until x_g reaches +100 or -100, then each projection's weight (x_m
+    is linear in it) until x_m does: exp(-|x|) underflows inside log_sigmoid's log1p, sigmoid_neg gives 0 or 1"""
+    import torch
+    c = _step_case(100, *EDGE, seed=6000)
+    m = _pruned_model(c, 0.5)
+    rows = np.ones(100, bool)
+    ext = lambda x: x.max() if sign > 0 else -x.min()       # noqa: E731
+    xg = _twin_run(c, m, rows, torch.float64, 0.5)[2][0]
+    for k in T.BASE:
+        c["P"][k] = (c["P"][k] * np.sqrt(100.0 / ext(xg))).astype(np.float32)
+    xs = _twin_run(c, m, rows, torch.float64, 0.5)[2]
+    for k, x in (("text_trs.weight", xs[1]), ("image_trs.weight", xs[2])):
+        c["P"][k] = (c["P"][k] * (100.0 / ext(x))).astype(np.float32)
+    m.load_parameters({k: c["P"][k] for k in m.parameters()})
+    xs = _twin_run(c, m, rows, torch.float64, 0.5)[2]
+    print("x_g, x_text, x_image: min", [x.min() for x in xs], "max", [x.max() for x in xs])
+    for x in xs:
+        assert 99 < ext(x) < 101 and np.float32(1) + np.exp(np.float32(-ext(x))) == 1
+    _edge_compare(c, f"arguments of {sign * 100}", widen=True, m=m)

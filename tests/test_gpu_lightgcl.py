@@ -334,3 +334,194 @@ def test_run_skrec_cli(tiny_dir, tmp_path):
                        cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "epoch 0:" in r.stdout and "best:" in r.stdout and "Recall@5" in r.stdout
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-4, 2e-5        # _check_grad's
+TEMP, LAMBDA1, LAMBDA2 = 0.2, 0.2, 1e-4
+
+
+def _twin_run(c, dtype, valid=None):
+    """the twin in ``dtype`` -> ((bpr, cl, reg), gradient of bpr + cl with respect to E_0 [U + I, d] in float64, the user
+    side's and the item side's contrastive logits over temp)"""
+    import torch
+    U = c["U"]
+    A = torch.tensor(T.dense_adjacency(c["rowptr"], c["items"], c["I"]), dtype=dtype)
+    eu, ei = (torch.tensor(a, dtype=dtype, requires_grad=True) for a in (c["E0"][:U], c["E0"][U:]))
+    fac = tuple(torch.tensor(f, dtype=dtype) for f in c["fac"])
+    comps, Eu, Ei, _ = T.losses_f64(eu, ei, A, fac, c["uids"], c["pos"], c["neg"], c["L"], TEMP, LAMBDA1, LAMBDA2, valid=valid)
+    (comps[0] + comps[1]).backward()
+    with torch.no_grad():
+        _, _, Gu, Gi = T.forward_f64(eu, ei, A, fac, c["L"])
+        ok_u = np.ones(c["B"], bool) if valid is None else valid[0]
+        ok_i = np.ones(2 * c["B"], bool) if valid is None else np.concatenate(valid[1:])
+        iids = np.concatenate([c["pos"], c["neg"]])
+        logits = ((Gu[c["uids"][ok_u]] @ Eu.T / TEMP).numpy(), (Gi[iids[ok_i]] @ Ei.T / TEMP).numpy())
+    return [x.item() for x in comps], np.vstack([eu.grad.numpy(), ei.grad.numpy()]).astype(np.float64), logits
+
+
+def _edge_compare(c, what, valid=None, floor=None, widen=False, m=None):
+    """The device step on the batch of ``c`` against the float64 twin, which skips the ids that ``valid`` marks as out of range.
+    ``floor``: each side's scale is max|want| or that of a batch without the exact cancellation, whichever is more.  ``widen``:
+    allow max(ATOL * scale, 4 x the error of the same twin in float32 on the CPU), both printed"""
+    import torch
+    U, d = c["U"], c["d"]
+    comps, G, _ = _twin_run(c, torch.float64, valid)
+    comps32, G32, _ = _twin_run(c, torch.float32, valid) if widen else (comps, None, None)
+    m = _detached(c, TEMP, LAMBDA1, LAMBDA2) if m is None else m
+    loss = m.gradient_step(c["uids"], c["pos"], c["neg"]).cpu().numpy()
+    want, want32 = (np.array(x + [sum(x)], np.float64) for x in (comps, comps32))
+    print(what, "loss", loss, "twin", want, "abs err", np.abs(loss - want), "fp32-CPU err", np.abs(want32 - want))
+    assert np.isfinite(loss).all()
+    assert np.all(np.abs(loss - want) <= np.maximum(1e-5 * np.abs(want), 4 * np.abs(want32 - want)))
+    grad = m._grad.cpu().numpy()
+    assert np.isfinite(grad).all() and not grad[:, d:].any()
+    for name, rows in (("E_u_0", slice(0, U)), ("E_i_0", slice(U, None))):     # both tensors are measured before the assertion
+        w = G[rows]
+        scale = float(np.abs(w).max())
+        if floor is not None:
+            scale = max(scale, float(np.abs(floor[rows]).max()))
+        err = np.abs(grad[rows, :d].astype(np.float64) - w)
+        atol = ATOL * scale
+        if widen:
+            err32 = float(np.abs(G32[rows] - w).max())
+            atol = max(atol, 4 * err32)
+            print(f"{what}: {name}: max abs err {err.max():.3e}, scale {scale:.3e}, fp32-CPU err {err32:.3e}")
+        else:
+            print(f"{what}: {name}: max abs err {err.max():.3e}, scale {scale:.3e}")
+        assert np.all(err <= atol + RTOL * np.abs(w)), (what, name, float(err.max()), scale)
+    return loss, grad, m
+
+
+@pytest.mark.parametrize("d", [64, 40])
+@pytest.mark.parametrize("B", [15, 16, 17, 63, 64, 65])
+def test_batch_sizes_around_the_tiles(B, d):
+    """below, at and above 16 and 64 pairs: the item side's 2 B queries cross the 64-query chunk of the InfoNCE passes at B = 32
+    and again here at 2 B = 126, 128, 130"""
+    c = _step_case(150, 130, B, 2, 5, d, 1000 + B + d)
+    assert len(np.unique(c["uids"])) < B and (c["neg"] == 129).any()
+    _edge_compare(c, f"B = {B}, d = {d}")
+
+
+def test_full_batch_at_sixteen_factors():
+    """B = 2048 at q = SKR_LIGHTGCL_MAX_Q = 16 and L = 3 on a 2100 x 2100 graph: 4096 item-side queries =
+    SKR_LIGHTGCL_MAX_QUERIES; then the same call again: the same bits; one pair more is refused"""
+    import time
+    import torch
+    from skrec import _hip
+    t0 = time.time()
+    assert _hip.SKR_LIGHTGCL_MAX_Q == 16 and _hip.SKR_LIGHTGCL_MAX_QUERIES == 4096
+    c = _step_case(2100, 2100, 2048, 3, 16, 64, 2100)
+    loss, _, m = _edge_compare(c, "B = 2048", widen=True)
+    g1, s1 = m._grad.clone(), m.sums.clone()
+    m._work.fill_(255)
+    m._grad.fill_(3.0)
+    loss2 = m.gradient_step(c["uids"], c["pos"], c["neg"]).cpu().numpy()
+    assert np.array_equal(loss.view(np.uint32), loss2.view(np.uint32)) and torch.equal(g1, m._grad) and torch.equal(s1, m.sums)
+    z = np.zeros(2049, np.int32)
+    with pytest.raises(NotImplementedError, match="at most 2048"):
+        m.gradient_step(z, z, z)
+    print("full batch: wall time", time.time() - t0)
+
+
+def test_one_factor():
+    """q = 1: one column of the [N, 16] factor tables is in use"""
+    _edge_compare(_step_case(150, 130, 37, 2, 1, 64, 1100), "q = 1")
+
+
+@pytest.mark.parametrize("B", [37, 300])
+@pytest.mark.parametrize("which", ["user", "item"])
+def test_one_id_in_every_row(which, B):
+    """the longest segment: all B ranks of the user list, or all 2 B ranks of the item list (pos and neg together), name one id,
+    so one wavefront of seg_add walks them all and the prep kernel counts B (2 B) equal keys.  With pos = neg every BPR argument
+    is 0 and the term's gradients cancel exactly: the scales are floored by the same users with the case's random items"""
+    import torch
+    c = _step_case(150, 130, B, 2, 5, 64, 3000 + B)
+    floor = _twin_run(c, torch.float64)[1]
+    if which == "user":
+        c["uids"][:] = c["uids"][B - 1]
+    else:
+        c["pos"][:] = c["pos"][B - 1]
+        c["neg"][:] = c["pos"][B - 1]
+    loss, _, _ = _edge_compare(c, f"one {which}, B = {B}", floor=floor)
+    if which == "item":
+        np.testing.assert_allclose(loss[0], np.log(2.0), rtol=1e-5)
+
+
+def test_ids_out_of_range_are_skipped():
+    """each id on its own, as the header says: a pair's BPR term needs its three ids, a user's (an item's) log-sum-exp and
+    positive score that id alone, and 70 and 140 stay the divisors.  Then rows whose three ids are all out of range: the
+    device's own result on the batch without them, scaled by 65 / 70"""
+    U, I, B = 150, 130, 70
+    c = _step_case(U, I, B, 2, 5, 64, 4000)
+    uids, pos, neg = c["uids"], c["pos"], c["neg"]
+    keep = uids.copy(), pos.copy(), neg.copy()
+    uids[3], pos[17], uids[40], neg[40], neg[69] = U, -1, -7, I, 2 ** 31 - 1
+    valid = ((uids >= 0) & (uids < U), (pos >= 0) & (pos < I), (neg >= 0) & (neg < I))
+    assert [int(v.sum()) for v in valid] == [68, 69, 68] and (valid[0] & valid[1] & valid[2]).sum() == 66
+    _, _, m = _edge_compare(c, "ids out of range", valid=valid)
+    bad = np.array([3, 17, 40, 41, 69])
+    c["uids"], c["pos"], c["neg"] = keep
+    keep[0][bad], keep[1][bad], keep[2][bad] = (U, -1, -7, U + 5, 2 ** 31 - 1), (I, -1, -7, I + 5, 2 ** 31 - 1), (-3, I, I + 1, -1, 2 ** 31 - 1)
+    ok = np.ones(B, bool)
+    ok[bad] = False
+    loss = m.gradient_step(*keep).cpu().numpy()
+    g = m._grad.cpu().numpy().copy()
+    loss2 = m.gradient_step(*(a[ok] for a in keep)).cpu().numpy()
+    g2 = m._grad.cpu().numpy()
+    np.testing.assert_allclose(loss[:2], loss2[:2] * 65 / 70, rtol=1e-5)
+    np.testing.assert_allclose(g, g2 * np.float32(65 / 70), rtol=RTOL, atol=ATOL * np.abs(g).max())
+
+
+def test_an_empty_batch_writes_nothing():
+    import ctypes
+    import torch
+    from skrec import _hip
+    c = _step_case(150, 130, 17, 2, 5, 64, 5000)
+    m = _detached(c, TEMP, LAMBDA1, 0.0)
+    loss = torch.full((4,), 7.0, device="cuda")
+    ids = torch.zeros(4, dtype=torch.int32, device="cuda")
+    a = m._step_args(ids, ids, ids, loss)
+    a.n = 0
+    m._grad.fill_(3.0)
+    m._work.fill_(5)
+    tabs = [m.sums, m._below, m._ping[0], m._ping[1], m._gsum, m._addend]
+    for t in tabs:
+        t.fill_(2.0)
+    before = [t.clone() for t in tabs] + [m._work.clone(), m._flat.clone()]
+    _hip.check(_hip.lib().skr_lightgcl_step(ctypes.byref(a), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and (m._grad == 3.0).all()
+    assert all(torch.equal(x, y) for x, y in zip(before, tabs + [m._work, m._flat]))
+    # through the class: a zero loss, a zero gradient, and the sums are not claimed to be those of the parameters
+    z = np.zeros(0, np.int32)
+    loss = m.gradient_step(z, z, z)
+    assert loss.shape == (4,) and not loss.any() and not m._grad.any() and not m._sums_current
+    m.gradient_step(c["uids"], c["pos"], c["neg"])
+    assert m._grad.any() and m._sums_current
+    assert not m.gradient_step(z, z, z).any() and not m._grad.any()
+    # train_step: the zero gradient through Adam, as MGCN, LATTICE and SLMRec do it; with no moments yet and no weight decay
+    # (lambda2 = 0: the decay term does not depend on the batch) nothing moves
+    m.gradient_step(c["uids"], c["pos"], c["neg"])
+    flat = m._flat.clone()
+    assert not m.train_step(z, z, z).any()
+    assert torch.equal(flat, m._flat)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_contrastive_logits_of_two_hundred(sign):
+    """E_0 scaled (the logits are quadratic in the factor) until the user side's logits over temp reach +200 (exp overflows fp32:
+    a log-sum-exp that does not take the running maximum off first gives inf) or -200 (such an exp underflows to 0)"""
+    import torch
+    c = _step_case(150, 130, 100, 2, 5, 64, 6000)
+    lg = _twin_run(c, torch.float64)[2][0]
+    c["E0"] = (c["E0"] * np.sqrt(200.0 / (lg.max() if sign > 0 else -lg.min()))).astype(np.float32)
+    lu, li = _twin_run(c, torch.float64)[2]
+    print("logits over temp: users min", lu.min(), "max", lu.max(), "items min", li.min(), "max", li.max())
+    if sign > 0:
+        assert 199 < lu.max() < 201 and np.isinf(np.exp(np.float32(lu.max())))
+    else:
+        assert -201 < lu.min() < -199 and np.exp(np.float32(lu.min())) == 0
+    _edge_compare(c, f"logits of {sign * 200}", widen=True)

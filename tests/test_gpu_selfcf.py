@@ -415,3 +415,188 @@ def test_each_limit_raises(tiny_dir, monkeypatch, tmp_path, kw, msg):
     from skrec.recommender.SelfCF import SelfCFConfig, check_limits
     with pytest.raises(NotImplementedError, match="one GPU"):
         check_limits(SelfCFConfig(**CONFIG), world=2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+RTOL, ATOL = 1e-4, 2e-5        # _check_grad's
+
+
+def _twin_run(c, m, rows, dtype, reg, dropout=0.5, n_div=None):
+    """the twin in ``dtype`` on the batch rows ``rows`` of ``c``, on the model's own adjacency values
+    -> ((cosine, reg part), {name: float64 gradient}, targets' norms (user side, item side))"""
+    import torch
+    d, I = c["d"], c["I"]
+    val = m.adj.val.cpu().numpy()[:len(c["items"])]
+    scale = float(np.float32(1.0 / (1.0 - c["rate"])))
+    R1, R2t = (torch.tensor(a, dtype=dtype) for a in T.masked_blocks(c["rowptr"], c["items"], I, val, c["k1"], c["k2"], scale))
+    P = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in c["P"].items()}
+    (cos, regl), Mu, Mi = T.losses_f64(P["user_emb"], P["item_emb"], P["predictor.weight"], P["predictor.bias"], R1, R2t, c["users"][rows],
+                                       c["its"][rows], c["ku"][rows][:, :d], c["ki"][rows][:, :d], c["L"], dropout, reg, n_div=n_div)
+    (cos + regl).backward()
+    with torch.no_grad():
+        tn = ((Mu[c["users"][rows]] * torch.tensor(c["ku"][rows][:, :d], dtype=dtype) / (1 - dropout)).norm(dim=1).numpy(),
+              (Mi[c["its"][rows]] * torch.tensor(c["ki"][rows][:, :d], dtype=dtype) / (1 - dropout)).norm(dim=1).numpy())
+    return (cos.item(), regl.item()), {k: v.grad.numpy().astype(np.float64) for k, v in P.items()}, tn
+
+
+def _edge_compare(c, what, reg=1e-2, ok=None, floor=None, widen=False, m=None):
+    """The device step on the batch of ``c`` against the float64 twin on the rows ``ok`` (all when None) with n as the divisor.
+    ``floor`` ({name: gradient}): each tensor's scale is max|want| or that tensor at a batch without the exact cancellation,
+    whichever is more.  ``widen``: allow max(ATOL * scale, 4 x the error of the same twin in float32 on the CPU), both printed"""
+    import torch
+    n = c["n"]
+    ok = np.ones(n, bool) if ok is None else ok
+    m = _detached(c, reg) if m is None else m
+    (cos, regl), G, _ = _twin_run(c, m, ok, torch.float64, reg, n_div=n)
+    (cos32, regl32), G32, _ = _twin_run(c, m, ok, torch.float32, reg, n_div=n) if widen else ((cos, regl), None, None)
+    loss = m.gradient_step(c["users"], c["its"], rate=c["rate"], edge_keep=(c["k1"], c["k2"]), target_keep=(c["ku"], c["ki"])).cpu().numpy()
+    want, want32 = np.array([cos, regl, cos + regl]), np.array([cos32, regl32, cos32 + regl32])
+    print(what, "loss", loss, "twin", want, "abs err", np.abs(loss - want), "fp32-CPU err", np.abs(want32 - want))
+    assert np.isfinite(loss).all()
+    assert np.all(np.abs(loss - want) <= np.maximum(1e-5 * np.abs(want), 4 * np.abs(want32 - want)))
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    for k in T.PARAMS:                # every tensor is measured before the assertion
+        scale = float(np.abs(G[k]).max())
+        if floor is not None:
+            scale = max(scale, float(np.abs(floor[k]).max()))
+        err = np.abs(got[k].astype(np.float64) - G[k])
+        atol = ATOL * scale
+        if widen:
+            err32 = float(np.abs(G32[k] - G[k]).max())
+            atol = max(atol, 4 * err32)
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}, fp32-CPU err {err32:.3e}")
+        else:
+            print(f"{what}: {k}: max abs err {err.max():.3e}, scale {scale:.3e}")
+        assert np.isfinite(got[k]).all(), k
+        assert np.all(err <= atol + RTOL * np.abs(G[k])), (what, k, float(err.max()), scale)
+    return loss, got, m
+
+
+def _run(m, c, rows=None):
+    rows = slice(None) if rows is None else rows
+    return m.gradient_step(c["users"][rows], c["its"][rows], rate=c["rate"], edge_keep=(c["k1"], c["k2"]),
+                           target_keep=(c["ku"][rows], c["ki"][rows]))
+
+
+@pytest.mark.parametrize("d", [64, 20])
+@pytest.mark.parametrize("n", [15, 16, 17, 63, 65])
+def test_batch_sizes_around_the_tiles(n, d):
+    """below, at and above a wavefront's 16 rows and a workgroup's 64 (n = 64 is in test_step_matches_float64_autograd)"""
+    c = _step_case(n, 2, d, 1000 + n + d)
+    assert len(np.unique(c["users"])) < n and len(np.unique(c["its"])) < n and (c["users"] == 47).any() and (c["its"] == 39).any()
+    _edge_compare(c, f"n = {n}, d = {d}")
+
+
+def test_full_batch_at_four_layers():
+    """n = 2048 at L = SKR_SELFCF_MAX_LAYERS = 4 on a 2100 x 2100 graph: 32 batch workgroups, eight dropped plan runs each way;
+    then the same call again: the same bits"""
+    import time
+    import torch
+    from skrec import _hip
+    t0 = time.time()
+    assert _hip.SKR_SELFCF_MAX_LAYERS == 4 and _hip.SKR_SELFCF_MAX_BATCH == 2048
+    c = _step_case(2048, 4, 64, 2100, U=2100, I=2100)
+    loss, _, m = _edge_compare(c, "n = 2048", widen=True)
+    g1, M1 = m._grad.clone(), m.M.clone()
+    m._work.fill_(255)
+    m._grad.fill_(3.0)
+    loss2 = _run(m, c).cpu().numpy()
+    assert np.array_equal(loss.view(np.uint32), loss2.view(np.uint32)) and torch.equal(g1, m._grad) and torch.equal(M1, m.M)
+    print("full batch: wall time", time.time() - t0)
+
+
+@pytest.mark.parametrize("n", [37, 300])
+@pytest.mark.parametrize("which", ["user", "item"])
+def test_one_id_in_every_row(which, n):
+    """the longest segment: all n ranks of one list name one id, so one wavefront of seg_add walks them all and the rank
+    kernel counts n equal keys; the scales are floored by the same batch with its random ids"""
+    import torch
+    c = _step_case(n, 2, 64, 3000 + n)
+    m = _detached(c, 1e-2)
+    floor = _twin_run(c, m, np.ones(n, bool), torch.float64, 1e-2, n_div=n)[1]
+    key = "users" if which == "user" else "its"
+    c[key][:] = c[key][n - 1]
+    _edge_compare(c, f"one {which}, n = {n}", floor=floor, m=m)
+
+
+def test_ids_out_of_range_contribute_nothing():
+    """the result is that of the batch without those rows with n = 70 as the divisor of the two cosine means; the regulariser
+    is a sum over the remaining rows"""
+    U, I, n = 48, 40, 70
+    c = _step_case(n, 2, 64, 4000)
+    users, its = c["users"], c["its"]
+    users[3], its[17], users[40], its[40], users[69] = U, -1, -7, I, 2 ** 31 - 1
+    ok = (users >= 0) & (users < U) & (its >= 0) & (its < I)
+    assert ok.sum() == 66
+    _edge_compare(c, "ids out of range", ok=ok)
+    # the device's own result on the filtered batch, scaled by 66 / 70 (without the regulariser, which does not scale)
+    m = _detached(c, 0.0)
+    loss = _run(m, c).cpu().numpy()
+    got = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    loss2 = _run(m, c, ok).cpu().numpy()
+    got2 = {k: v.cpu().numpy() for k, v in m.gradients().items()}
+    assert loss[1] == 0 and loss2[1] == 0
+    np.testing.assert_allclose(loss, loss2 * 66 / 70, rtol=1e-5)
+    for k in T.PARAMS:
+        np.testing.assert_allclose(got[k], got2[k] * np.float32(66 / 70), rtol=RTOL, atol=ATOL * np.abs(got[k]).max(), err_msg=k)
+
+
+def test_an_empty_batch_writes_nothing():
+    import torch
+    from skrec import _hip
+    c = _step_case(17, 2, 64, 5000)
+    m = _detached(c)
+    loss = torch.full((3,), 7.0, device="cuda")
+    ids = torch.zeros(4, dtype=torch.int32, device="cuda")
+    a = m._step_args(ids, ids, 0.3, None, None, None, loss)
+    a.n = 0
+    m._grad.fill_(3.0)
+    m._work.fill_(5)
+    tabs = [m.M, m._G, m._ping[0], m._ping[1]]
+    for t in tabs:
+        t.fill_(2.0)
+    before = [t.clone() for t in tabs] + [m._work.clone(), m._flat.clone()]
+    _hip.check(_hip.lib().skr_selfcf_step(C.byref(a), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and (m._grad == 3.0).all()
+    assert all(torch.equal(x, y) for x, y in zip(before, tabs + [m._work, m._flat]))
+    # through the class: a zero loss, a zero gradient whatever the last step left there; the draws' step counter stays
+    _run(m, c)
+    assert m._grad.any()
+    z, step = np.zeros(0, np.int32), m._step
+    loss = m.gradient_step(z, z)
+    assert loss.shape == (3,) and not loss.any() and not m._grad.any() and m._step == step
+    # train_step: the zero gradient through Adam, as MGCN, LATTICE and SLMRec do it; with no moments yet nothing moves
+    _run(m, c)
+    flat = m._flat.clone()
+    assert not m.train_step(z, z).any()
+    assert torch.equal(flat, m._flat)
+
+
+def test_a_predictor_output_of_exact_zeros():
+    """W = 0 and b = 0: every P row is zero, |P| takes the 1e-8 clamp, every cosine is 0 and the predictor's gradient is
+    -t / (1e-8 max(|t|, 1e-8)) / (2 n): of the order 1e8 / n, finite"""
+    c = _step_case(70, 2, 64, 6000)
+    c["P"]["predictor.weight"][:] = 0
+    c["P"]["predictor.bias"][:] = 0
+    loss, got, _ = _edge_compare(c, "P = 0", widen=True)
+    assert loss[0] == 0 and np.abs(got["predictor.bias"]).max() > 1e4
+
+
+def test_target_rows_with_a_norm_under_the_clamp():
+    """the isolated user's and the isolated item's embedding rows scaled by 1e-9: their target rows (rows 1 of the batch) have
+    0 < |t| < 1e-8, the max(|t|, 1e-8) branch of the cosine; the reference is the twin's own clamp"""
+    import torch
+    c = _step_case(70, 2, 64, 6001)
+    U, I = c["U"], c["I"]
+    assert c["users"][1] == U - 1 and c["its"][1] == I - 1
+    c["ku"][1], c["ki"][1] = 1, 1
+    c["P"]["user_emb"][U - 1] *= np.float32(1e-9)
+    c["P"]["item_emb"][I - 1] *= np.float32(1e-9)
+    m = _detached(c, 1e-2)
+    tn = _twin_run(c, m, np.ones(70, bool), torch.float64, 1e-2)[2]
+    print("target norms of row 1:", tn[0][1], tn[1][1])
+    assert 0 < tn[0][1] < 1e-8 and 0 < tn[1][1] < 1e-8
+    _edge_compare(c, "small targets", widen=True, m=m)
