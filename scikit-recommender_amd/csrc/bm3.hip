@@ -172,53 +172,6 @@ __global__ __launch_bounds__(HW * 64) void bm_seg_rows_kernel(const int32_t* __r
     if (lane == 0) head[rk] = first ? id : -1;
 }
 
-// dX[head[rk]][f] = sum_o Gseg[rk][o] W[o][f]: a wavefront owns 16 ranks and 64 columns; rows that are no head are not written
-__global__ __launch_bounds__(HW * 64) void bm_feat_grad_kernel(const float* __restrict__ Gseg, const int32_t* __restrict__ head, int n, int ld,
-                                                               const float* __restrict__ W, float* __restrict__ dX) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    const int rk0 = blockIdx.x * 16;
-    const int f0 = (blockIdx.y * HW + wv) * 64;
-    if (f0 >= ld) return;
-    float a[16];
-    load_row_a(a, Gseg, rk0 + r < n ? rk0 + r : -1, g);
-    f32x4 acc[4];
-    zero_acc(acc);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-        const float* __restrict__ wrow = W + static_cast<int64_t>(16 * g + kk) * ld + f0 + r;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const float b = f0 + nb * 16 + r < ld ? wrow[nb * 16] : 0.0f;
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b, acc[nb], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int rk = rk0 + 4 * g + rr;
-        const int64_t id = rk < n ? head[rk] : -1;
-        if (id < 0) continue;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const int f = f0 + nb * 16 + r;
-            if (f < ld) dX[id * ld + f] = acc[nb][rr];
-        }
-    }
-}
-
-// the feature-gradient rows of the listed items := 0 (blockIdx.y: the modality)
-struct ClearParams {
-    float* table[2];
-    int ld[2];
-};
-__global__ __launch_bounds__(256) void bm_clear_rows_kernel(ClearParams p, const int32_t* __restrict__ ids, int I) {
-    float* t = p.table[blockIdx.y];
-    if (t == nullptr) return;
-    const int id = ids[blockIdx.x], ld = p.ld[blockIdx.y];
-    if (id < 0 || id >= I) return;
-    float4* row = reinterpret_cast<float4*>(t + static_cast<int64_t>(id) * ld);
-    for (int k = threadIdx.x; k < ld / 4; k += 256) row[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
 // ------------------------------------------------------------------------------------------------
 // + h and the sums of squares
 // ------------------------------------------------------------------------------------------------
@@ -617,7 +570,7 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
     SKR_HIP(mk.mark());
     if (a->n_clear > 0 && (a->feat_dim[0] || a->feat_dim[1])) {
         ClearParams cp = {{a->feat_dim[0] ? a->feat_grad[0] : nullptr, a->feat_dim[1] ? a->feat_grad[1] : nullptr}, {a->feat_ld[0], a->feat_ld[1]}};
-        hipLaunchKernelGGL(bm_clear_rows_kernel, dim3(a->n_clear, 2), dim3(256), 0, st, cp, a->clear_items, I);
+        hipLaunchKernelGGL(clear_rows_kernel<256>, dim3(a->n_clear, 2), dim3(256), 0, st, cp, a->clear_items, I);
         SKR_LAUNCH_CHECK();
     }
     // ---- forward (BM3.py:145-151): the layer means of X_k = A-hat X_(k-1)
@@ -663,7 +616,7 @@ int run_step(const skr_bm3_step_args* a, void* stream, float* h_ms) {
         hipLaunchKernelGGL(bm_trs_bgrad_kernel, dim3(1), dim3(D), 0, st, dY, n, a->trs_grad[m] + static_cast<int64_t>(D) * ld);
         hipLaunchKernelGGL(bm_trs_wgrad_kernel, dim3((ld + 63) / 64), dim3(HW * 64), 0, st, a->feat[m], I, ld, a->items, n, dY, a->trs_grad[m]);
         hipLaunchKernelGGL(bm_seg_rows_kernel, dim3(blocks), dim3(HW * 64), 0, st, a->items, ordi, n, I, dY, w + W.Gseg, head);
-        hipLaunchKernelGGL(bm_feat_grad_kernel, dim3((n + 15) / 16, (ld + 64 * HW - 1) / (64 * HW)), dim3(HW * 64), 0, st, w + W.Gseg, head, n, ld,
+        hipLaunchKernelGGL(feat_grad_kernel<HW>, dim3((n + 15) / 16, (ld + 64 * HW - 1) / (64 * HW)), dim3(HW * 64), 0, st, w + W.Gseg, head, n, ld,
                            a->trs[m], a->feat_grad[m]);
     }
     SKR_LAUNCH_CHECK();

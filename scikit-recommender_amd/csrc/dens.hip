@@ -447,10 +447,7 @@ __global__ __launch_bounds__(HW * 64) void dn_back_kernel(Tables T, const float*
 // ------------------------------------------------------------------------------------------------
 // the gradient rows into the hop's table
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int item_at(const int32_t* __restrict__ pos, const int32_t* __restrict__ sel, int n, int k) {
-    return k < n ? pos[k] : sel[k - n];
-}
-
+// item_at (step_common.h): position k < n of a hop's item list is pos[k], position n + b the hop's chosen item sel[b]
 // order_u [n]: the positions of the user list sorted by (id, position); order_i [H + 1][2 n]: those of hop h's item list
 // cat(pos, the hop's chosen items) -- a rank by counting.  blockIdx.y = hop; the user list is ranked by hop 0's blocks.
 __global__ __launch_bounds__(256) void dn_rank_kernel(const int32_t* __restrict__ uids, const int32_t* __restrict__ pos,

@@ -24,8 +24,8 @@
 //   2 Lu plan runs   acc = G; acc = A'^T acc + G; the last writes acc / (Lu + 1) into the gradient (Lu == 0: grad = G)
 //   Lm plan runs     t_k = S^T t_(k-1) on G's item rows; the last adds into the gradient's item rows (Lm == 0: grad_i += G_i)
 //
-// The kernels of the projection backward are bm3.hip's, restated for the difference of two feature rows and the 2 n long
-// item list.  Determinism: no floating-point atomic anywhere; the select's histograms are integer atomics, whose result does
+// trs_wgrad and seg_rows are bm3.hip's, restated for the difference of two feature rows and the 2 n long item list; the
+// kernels that are the same text -- rank_triples, add, feat_grad, clear_rows -- are step_common.h's.  Determinism: no floating-point atomic anywhere; the select's histograms are integer atomics, whose result does
 // not depend on their order.
 #include "skr_common.h"
 #include "fast_rng.h"
@@ -290,13 +290,6 @@ inline PruneLayout prune_layout(int64_t N, int64_t nnz) {
 // ------------------------------------------------------------------------------------------------
 // the step: batch kernel, loss, ordered adds
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
-// sigmoid(-x) without overflow
-__device__ __forceinline__ float sigmoid_neg(float x) {
-    const float e = expf(-fabsf(x));
-    return x >= 0.0f ? e / (1.0f + e) : 1.0f / (1.0f + e);
-}
-
 // Item list: position o < n is pos[o], position n + b is neg[b]; its rows of Gi lie at o resp. n4 + b.
 struct BatchParams {
     const float* M;
@@ -370,38 +363,9 @@ __global__ __launch_bounds__(64) void fd_loss_kernel(const float* __restrict__ s
     loss[2] = g + modal;
 }
 
-__device__ __forceinline__ int item_at(const int32_t* __restrict__ pos, const int32_t* __restrict__ neg, int n, int o) {
-    return o < n ? pos[o] : neg[o - n];
-}
-
-// order_u [n] / order_i [2 n]: the positions of the user list and of pos || neg sorted by (id, position) -- the rank by
-// counting of step_common.h's rank_lists_kernel, written out for an item list twice as long as the user list
-__global__ __launch_bounds__(256) void fd_rank_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ pos,
-                                                      const int32_t* __restrict__ neg, int n, int32_t* __restrict__ order_u,
-                                                      int32_t* __restrict__ order_i) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= 3 * n) return;
-    int rank = 0;
-    if (k < n) {
-        const int id = users[k];
-        for (int j = 0; j < n; ++j) {
-            const int o = users[j];
-            rank += (o < id || (o == id && j < k)) ? 1 : 0;
-        }
-        order_u[rank] = k;
-    } else {
-        const int kk = k - n;
-        const int id = item_at(pos, neg, n, kk);
-        for (int j = 0; j < 2 * n; ++j) {
-            const int o = item_at(pos, neg, n, j);
-            rank += (o < id || (o == id && j < kk)) ? 1 : 0;
-        }
-        order_i[rank] = kk;
-    }
-}
-
 // G[id] = the sum of the rows whose list entry is id, in rank order, by the wavefront of the id's first rank: one writer
-// per distinct id (G is cleared first).  Blocks [0, blocks_u) walk the user list, the others the item list.
+// per distinct id (G is cleared first).  Blocks [0, blocks_u) walk the user list, the others the item list.  (lattice.hip's
+// la_seg_add_kernel sums a second table beside it, mgcn.hip's three slot tables, bm3.hip's adds onto G over one item list.)
 __global__ __launch_bounds__(HW * 64) void fd_seg_add_kernel(float* __restrict__ G, const int32_t* __restrict__ users,
                                                              const int32_t* __restrict__ pos, const int32_t* __restrict__ neg,
                                                              const int32_t* __restrict__ order_u, const int32_t* __restrict__ order_i, int n,
@@ -427,19 +391,12 @@ __global__ __launch_bounds__(HW * 64) void fd_seg_add_kernel(float* __restrict__
     G[(static_cast<int64_t>(user ? 0 : U) + id) * D + lane] = acc;
 }
 
-// the item rows' + h path without an item-graph layer: dst += src
-__global__ __launch_bounds__(256) void fd_add_kernel(float* dst, const float* src, int64_t n) {
-    for (int64_t e = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * 256) {
-        const float v = dst[e], w = src[e];
-        dst[e] = v + w;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// the projection backward (bm3.hip's kernels on f[pos] - f[neg] and on the 2 n long item list)
+// the projection backward (bm3.hip's kernels on f[pos] - f[neg] and on the 2 n long item list; feat_grad: step_common.h)
 // ------------------------------------------------------------------------------------------------
 // dW[o][f] = sum_b g[b][o] (X[pos_b][f] - X[neg_b][f]): a wavefront owns 16 columns f and walks the batch in order, four rows
 // per MFMA (A = g^T, B = the differences of the gathered rows); acc[mb][rr] = dW[16 mb + g + 4 rr][f0 + r].
+// (bm_trs_wgrad_kernel: one gathered row, not a difference, summed in fp32.)
 // The sum runs on v_mfma_f64_16x16x4_f64 (A and B as the fp32 instruction of that shape, the result's row g + 4 rr): it is the one long sum
 // of the step -- up to 2 048 terms of either sign that nearly cancel -- and an element that starts with a gradient beside
 // Adam's eps has its fp32 rounding magnified by up to lr / eps in the first update.  In float64 only the terms' own
@@ -480,6 +437,7 @@ __global__ __launch_bounds__(HW * 64) void fd_trs_wgrad_kernel(const float* __re
 
 // Gseg[rk] = the signed sum (+ at pos, - at neg) of the g rows whose item is the one at rank rk, in rank order, head[rk] =
 // that item -- at the first rank of every distinct valid item; zeros and -1 at every other rank.  len = 2 n ranks.
+// (bm_seg_rows_kernel: one list of n items, no sign.)
 __global__ __launch_bounds__(HW * 64) void fd_seg_rows_kernel(const int32_t* __restrict__ pos, const int32_t* __restrict__ neg,
                                                               const int32_t* __restrict__ order, int n, int I, const float* __restrict__ dY,
                                                               float* __restrict__ Gseg, int32_t* __restrict__ head) {
@@ -499,53 +457,6 @@ __global__ __launch_bounds__(HW * 64) void fd_seg_rows_kernel(const int32_t* __r
     }
     Gseg[static_cast<int64_t>(rk) * D + lane] = acc;
     if (lane == 0) head[rk] = first ? id : -1;
-}
-
-// dX[head[rk]][f] = sum_o Gseg[rk][o] W[o][f]: a wavefront owns 16 ranks and 64 columns; rows that are no head are not written
-__global__ __launch_bounds__(HW * 64) void fd_feat_grad_kernel(const float* __restrict__ Gseg, const int32_t* __restrict__ head, int n, int ld,
-                                                               const float* __restrict__ W, float* __restrict__ dX) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    const int rk0 = blockIdx.x * 16;
-    const int f0 = (blockIdx.y * HW + wv) * 64;
-    if (f0 >= ld) return;
-    float a[16];
-    load_row_a(a, Gseg, rk0 + r < n ? rk0 + r : -1, g);
-    f32x4 acc[4];
-    zero_acc(acc);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-        const float* __restrict__ wrow = W + static_cast<int64_t>(16 * g + kk) * ld + f0 + r;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const float b = f0 + nb * 16 + r < ld ? wrow[nb * 16] : 0.0f;
-            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b, acc[nb], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int rk = rk0 + 4 * g + rr;
-        const int64_t id = rk < n ? head[rk] : -1;
-        if (id < 0) continue;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const int f = f0 + nb * 16 + r;
-            if (f < ld) dX[id * ld + f] = acc[nb][rr];
-        }
-    }
-}
-
-// the feature-gradient rows of the listed items := 0 (blockIdx.y: the modality)
-struct ClearParams {
-    float* table[2];
-    int ld[2];
-};
-__global__ __launch_bounds__(256) void fd_clear_rows_kernel(ClearParams p, const int32_t* __restrict__ ids, int I) {
-    float* t = p.table[blockIdx.y];
-    if (t == nullptr) return;
-    const int id = ids[blockIdx.x], ld = p.ld[blockIdx.y];
-    if (id < 0 || id >= I) return;
-    float4* row = reinterpret_cast<float4*>(t + static_cast<int64_t>(id) * ld);
-    for (int k = threadIdx.x; k < ld / 4; k += 256) row[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -629,7 +540,7 @@ int run_step(const skr_freedom_step_args* a, void* stream, float* h_ms) {
     // ---- h = S^Lm X0_items (FREEDOM.py:212-214), added to M's item rows (:225); the ping tables are free again
     if (Lm == 0) {
         const unsigned wgs = static_cast<unsigned>(std::min<int64_t>((IO + 255) / 256, 8192));
-        hipLaunchKernelGGL(fd_add_kernel, dim3(wgs), dim3(256), 0, st, a->M + UO, a->params + UO, IO);
+        hipLaunchKernelGGL(add_kernel<256>, dim3(wgs), dim3(256), 0, st, a->M + UO, a->params + UO, IO);
         SKR_LAUNCH_CHECK();
     }
     {
@@ -649,7 +560,7 @@ int run_step(const skr_freedom_step_args* a, void* stream, float* h_ms) {
     float* Gm[2] = {nullptr, nullptr};
     if (modal && a->n_clear > 0 && (has[0] || has[1])) {
         ClearParams cp = {{has[0] ? a->feat_grad[0] : nullptr, has[1] ? a->feat_grad[1] : nullptr}, {a->feat_ld[0], a->feat_ld[1]}};
-        hipLaunchKernelGGL(fd_clear_rows_kernel, dim3(a->n_clear, 2), dim3(256), 0, st, cp, a->clear_items, I);
+        hipLaunchKernelGGL(clear_rows_kernel<256>, dim3(a->n_clear, 2), dim3(256), 0, st, cp, a->clear_items, I);
         SKR_LAUNCH_CHECK();
     }
     for (int m = 0; m < 2; ++m) {
@@ -678,7 +589,7 @@ int run_step(const skr_freedom_step_args* a, void* stream, float* h_ms) {
     SKR_HIP(mk.mark());
     // ---- the gradient with respect to M: one ordered sum per distinct node into the cleared G
     SKR_HIP(hipMemsetAsync(a->G, 0, static_cast<size_t>(N) * D * sizeof(float), st));
-    hipLaunchKernelGGL(fd_rank_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
+    hipLaunchKernelGGL(rank_triples_kernel<256>, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
     const int blocks_u = (n + HW - 1) / HW, blocks_i = (2 * n + HW - 1) / HW;
     hipLaunchKernelGGL(fd_seg_add_kernel, dim3(blocks_u + blocks_i), dim3(HW * 64), 0, st, a->G, a->users, a->pos, a->neg, ordu, ordi, n, n4, U, I,
                        blocks_u, w + W.Gu, w + W.Gi);
@@ -692,7 +603,7 @@ int run_step(const skr_freedom_step_args* a, void* stream, float* h_ms) {
         hipLaunchKernelGGL(fd_trs_wgrad_kernel, dim3((ld + 63) / 64), dim3(HW * 64), 0, st, a->feat[m], I, ld, a->pos, a->neg, n, Gm[m],
                            a->trs_grad[m]);
         hipLaunchKernelGGL(fd_seg_rows_kernel, dim3(blocks_i), dim3(HW * 64), 0, st, a->pos, a->neg, ordi, n, I, Gm[m], w + W.Gseg, head);
-        hipLaunchKernelGGL(fd_feat_grad_kernel, dim3((2 * n + 15) / 16, (ld + 64 * HW - 1) / (64 * HW)), dim3(HW * 64), 0, st, w + W.Gseg, head,
+        hipLaunchKernelGGL(feat_grad_kernel<HW>, dim3((2 * n + 15) / 16, (ld + 64 * HW - 1) / (64 * HW)), dim3(HW * 64), 0, st, w + W.Gseg, head,
                            2 * n, ld, a->trs[m], a->feat_grad[m]);
         SKR_LAUNCH_CHECK();
     }
@@ -704,7 +615,7 @@ int run_step(const skr_freedom_step_args* a, void* stream, float* h_ms) {
     if (rc != SKR_OK) return rc;
     if (Lm == 0) {
         const unsigned wgs = static_cast<unsigned>(std::min<int64_t>((IO + 255) / 256, 8192));
-        hipLaunchKernelGGL(fd_add_kernel, dim3(wgs), dim3(256), 0, st, a->grad + UO, a->G + UO, IO);
+        hipLaunchKernelGGL(add_kernel<256>, dim3(wgs), dim3(256), 0, st, a->grad + UO, a->G + UO, IO);
         SKR_LAUNCH_CHECK();
     }
     {

@@ -403,13 +403,6 @@ inline BwdLayout bwd_layout(int64_t I, int64_t nnz) {
 // ------------------------------------------------------------------------------------------------
 // the step: batch kernel, loss, ordered adds
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
-// sigmoid(-x) without overflow
-__device__ __forceinline__ float sigmoid_neg(float x) {
-    const float e = expf(-fabsf(x));
-    return x >= 0.0f ? e / (1.0f + e) : 1.0f / (1.0f + e);
-}
-
 // Item list: position o < n is pos[o], position n + b is neg[b]; its rows of Gi and Hi lie at o resp. n4 + b.
 struct BatchParams {
     const float* M;                // [N][64]: the user-item part
@@ -484,36 +477,9 @@ __global__ __launch_bounds__(64) void la_loss_kernel(const float* __restrict__ s
     loss[2] = b + r;
 }
 
-__device__ __forceinline__ int item_at(const int32_t* __restrict__ pos, const int32_t* __restrict__ neg, int n, int o) {
-    return o < n ? pos[o] : neg[o - n];
-}
-
-// order_u [n] / order_i [2 n]: the positions of the user list and of pos || neg sorted by (id, position), by counting: the
-// loop of freedom.hip's fd_rank_kernel, written out here as step_common.h asks (behind a shared helper it compiled slower)
-__global__ __launch_bounds__(256) void la_rank_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ pos,
-                                                      const int32_t* __restrict__ neg, int n, int32_t* __restrict__ order_u,
-                                                      int32_t* __restrict__ order_i) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= 3 * n) return;
-    int rank = 0;
-    if (k < n) {
-        const int id = users[k];
-        for (int j = 0; j < n; ++j) {
-            const int o = users[j];
-            rank += (o < id || (o == id && j < k)) ? 1 : 0;
-        }
-        order_u[rank] = k;
-    } else {
-        const int kk = k - n;
-        const int id = item_at(pos, neg, n, kk);
-        for (int j = 0; j < 2 * n; ++j) {
-            const int o = item_at(pos, neg, n, j);
-            rank += (o < id || (o == id && j < kk)) ? 1 : 0;
-        }
-        order_i[rank] = kk;
-    }
-}
-
+// The BPR scalars, the pos || neg item list, the rank by counting (rank_triples_kernel) and dst += src (add_kernel) are
+// step_common.h's: one text with freedom.hip and mgcn.hip.
+//
 // G[id] (users, items) and DHn[id] (items) = the sums of the rows whose list entry is id, in rank order, by the wavefront of
 // the id's first rank: one writer per distinct id (both tables are cleared first).  Blocks [0, blocks_u) walk the user list.
 __global__ __launch_bounds__(HW * 64) void la_seg_add_kernel(float* __restrict__ G, float* __restrict__ DHn, const int32_t* __restrict__ users,
@@ -560,14 +526,6 @@ __global__ __launch_bounds__(256) void la_mark_kernel(const int32_t* __restrict_
     if (k >= 2 * n) return;
     const int id = item_at(pos, neg, n, k);
     if (id >= 0 && id < I) mask[id] = 1;
-}
-
-// dst += src
-__global__ __launch_bounds__(256) void la_add_kernel(float* dst, const float* src, int64_t n) {
-    for (int64_t e = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * 256) {
-        const float v = dst[e], w = src[e];
-        dst[e] = v + w;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -691,7 +649,7 @@ int run_step(const skr_lattice_step_args* a, void* stream, float* h_ms) {
     float* DHn = a->DH + static_cast<int64_t>(Ln > 0 ? Ln - 1 : 0) * IO;
     SKR_HIP(hipMemsetAsync(a->G, 0, static_cast<size_t>(N) * D * sizeof(float), st));
     SKR_HIP(hipMemsetAsync(DHn, 0, static_cast<size_t>(IO) * sizeof(float), st));
-    hipLaunchKernelGGL(la_rank_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
+    hipLaunchKernelGGL(rank_triples_kernel<256>, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
     const int blocks_u = (n + HW - 1) / HW, blocks_i = (2 * n + HW - 1) / HW;
     hipLaunchKernelGGL(la_seg_add_kernel, dim3(blocks_u + blocks_i), dim3(HW * 64), 0, st, a->G, DHn, a->users, a->pos, a->neg, ordu, ordi, n, n4,
                        U, I, blocks_u, w + W.Gu, w + W.Gi, w + W.Hi);
@@ -718,7 +676,7 @@ int run_step(const skr_lattice_step_args* a, void* stream, float* h_ms) {
     // ---- backward through h: dh_(l-1) = S^T dh_l; the last adds into the gradient's item rows
     if (Ln == 0) {
         const unsigned wgs = static_cast<unsigned>(std::min<int64_t>((IO + 255) / 256, 8192));
-        hipLaunchKernelGGL(la_add_kernel, dim3(wgs), dim3(256), 0, st, a->grad + UO, DHn, IO);
+        hipLaunchKernelGGL(add_kernel<256>, dim3(wgs), dim3(256), 0, st, a->grad + UO, DHn, IO);
         SKR_LAUNCH_CHECK();
     }
     for (int l = Ln; l >= 1; --l) {

@@ -51,11 +51,6 @@ constexpr int XTY_BLOCKS = 64; // ... and the most row blocks above XTY_ROWS * X
 constexpr float INV_TAU = 5.0f;    // the reference's literal temperature 0.2 (MGCN.py:350)
 constexpr float NORM_EPS = 1e-12f; // F.normalize
 
-__device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoid_neg(float x) {
-    const float e = expf(-fabsf(x));
-    return x >= 0.0f ? e / (1.0f + e) : 1.0f / (1.0f + e);
-}
 __device__ __forceinline__ float sigmoid(float x) { return sigmoid_neg(-x); }
 
 // ---- the products' accumulators (mfma_tile.h: zero_acc64, mfma64, tile_product64, logits_tile64).  The operands are fp32
@@ -628,35 +623,6 @@ __global__ __launch_bounds__(HW * 64) void mg_fuse_bwd_kernel(FuseBwdParams p) {
     p.dq[e] = dq;
 }
 
-__device__ __forceinline__ int item_at(const int32_t* __restrict__ pos, const int32_t* __restrict__ neg, int n, int o) {
-    return o < n ? pos[o] : neg[o - n];
-}
-
-// order_u [n] / order_i [2 n]: the positions of the user list and of pos || neg sorted by (id, position), a rank by counting
-__global__ __launch_bounds__(256) void mg_rank_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ pos,
-                                                      const int32_t* __restrict__ neg, int n, int32_t* __restrict__ order_u,
-                                                      int32_t* __restrict__ order_i) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= 3 * n) return;
-    int rank = 0;
-    if (k < n) {
-        const int id = users[k];
-        for (int j = 0; j < n; ++j) {
-            const int o = users[j];
-            rank += (o < id || (o == id && j < k)) ? 1 : 0;
-        }
-        order_u[rank] = k;
-    } else {
-        const int kk = k - n;
-        const int id = item_at(pos, neg, n, kk);
-        for (int j = 0; j < 2 * n; ++j) {
-            const int o = item_at(pos, neg, n, j);
-            rank += (o < id || (o == id && j < kk)) ? 1 : 0;
-        }
-        order_i[rank] = kk;
-    }
-}
-
 // G_k[id] = the sum of the slot rows of S_k whose list entry is id, in rank order, by the wavefront of the id's first rank: one
 // writer per distinct id (the three tables are cleared first)
 struct SegParams {
@@ -899,7 +865,7 @@ int run_step(const skr_mgcn_step_args* a, void* stream, float* h_ms) {
     if ((rc = launch_xty(w + W.dpp, w + W.zg + 2 * S * D, S, D, w + W.part, a->prefer_grad[0], st)) != SKR_OK) return rc;
     if ((rc = launch_xty(w + W.dpp + S * D, w + W.zg + 2 * S * D, S, D, w + W.part, a->prefer_grad[1], st)) != SKR_OK) return rc;
     for (int t = 0; t < 3; ++t) SKR_HIP(hipMemsetAsync(a->G[t], 0, static_cast<size_t>(N) * D * sizeof(float), st));
-    hipLaunchKernelGGL(mg_rank_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
+    hipLaunchKernelGGL(rank_triples_kernel<256>, dim3((3 * n + 255) / 256), dim3(256), 0, st, a->users, a->pos, a->neg, n, ordu, ordi);
     const int blocks_u = (n + HW - 1) / HW, blocks_i = (2 * n + HW - 1) / HW;
     SegParams sp = {{a->G[0], a->G[1], a->G[2]}, {w + W.dm, w + W.dz, w + W.dz + S * D}};
     hipLaunchKernelGGL(mg_seg_add_kernel, dim3(blocks_u + blocks_i), dim3(HW * 64), 0, st, sp, a->users, a->pos, a->neg, ordu, ordi, n, n16, U, I,

@@ -1,16 +1,32 @@
-// step_common.h -- what the models' step drivers share: the two small kernels that bm3.hip and selfcf.hip (and, for the
-// reduction, dens.hip) launch alike, the host-side plan runs of the four graph models, and the timer of the profiling entries.
+// step_common.h -- what the models' step drivers share: the small kernels that several of bm3.hip, selfcf.hip, dens.hip,
+// freedom.hip, mgcn.hip and lattice.hip launch alike, the BPR scalars and the pos || neg item list of the triple models, the
+// host-side plan runs of the graph models, and the timer of the profiling entries.
 #pragma once
 #include "skr_common.h"
+#include "mfma_tile.h"
 
 namespace skr {
+
+// log(sigmoid(x)) as torch's log_sigmoid forward writes it
+__device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
+// sigmoid(-x) without overflow
+__device__ __forceinline__ float sigmoid_neg(float x) {
+    const float e = expf(-fabsf(x));
+    return x >= 0.0f ? e / (1.0f + e) : 1.0f / (1.0f + e);
+}
+
+// the item list of a batch of triples (dens.hip: pos and a hop's chosen items): position o < n is pos[o], position n + b is neg[b]
+__device__ __forceinline__ int item_at(const int32_t* __restrict__ pos, const int32_t* __restrict__ neg, int n, int o) {
+    return o < n ? pos[o] : neg[o - n];
+}
 
 namespace {   // kernels: templates, so that only a translation unit that launches one holds a copy; none is exported
 
 // order_u [n] / order_i [n]: the positions of the user / item list sorted by (id, position) -- a rank by counting, which
-// gives a batch's duplicate ids a fixed order; THREADS per workgroup.  The loop is written out here, in dn_rank_kernel and
-// in bk_prep_kernel: behind a helper that takes the list as an accessor it compiles to other code, and the launch groups
-// measured 1 - 5 us slower (profiles/tile_helpers_timing.json).
+// gives a batch's duplicate ids a fixed order; THREADS per workgroup.  The loop is written out here, in rank_triples_kernel,
+// in dn_rank_kernel and in bk_prep_kernel: behind a helper that takes the list as an accessor it compiles to other code, and
+// the launch groups measured 1 - 5 us slower (profiles/tile_helpers_timing.json).  rank_triples_kernel is one text for the
+// three models that launch it, not such a helper: its two loops stay written out.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void rank_lists_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ items, int n,
                                                              int32_t* __restrict__ order_u, int32_t* __restrict__ order_i) {
@@ -25,6 +41,92 @@ __global__ __launch_bounds__(THREADS) void rank_lists_kernel(const int32_t* __re
         rank += (o < id || (o == id && j < kk)) ? 1 : 0;
     }
     (k < n ? order_u : order_i)[rank] = kk;
+}
+
+// order_u [n] / order_i [2 n]: the positions of the user list and of pos || neg sorted by (id, position) -- the same rank
+// by counting for an item list twice as long as the user list (freedom.hip, mgcn.hip, lattice.hip)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void rank_triples_kernel(const int32_t* __restrict__ users, const int32_t* __restrict__ pos,
+                                                               const int32_t* __restrict__ neg, int n, int32_t* __restrict__ order_u,
+                                                               int32_t* __restrict__ order_i) {
+    const int k = blockIdx.x * THREADS + threadIdx.x;
+    if (k >= 3 * n) return;
+    int rank = 0;
+    if (k < n) {
+        const int id = users[k];
+        for (int j = 0; j < n; ++j) {
+            const int o = users[j];
+            rank += (o < id || (o == id && j < k)) ? 1 : 0;
+        }
+        order_u[rank] = k;
+    } else {
+        const int kk = k - n;
+        const int id = item_at(pos, neg, n, kk);
+        for (int j = 0; j < 2 * n; ++j) {
+            const int o = item_at(pos, neg, n, j);
+            rank += (o < id || (o == id && j < kk)) ? 1 : 0;
+        }
+        order_i[rank] = kk;
+    }
+}
+
+// dst += src (freedom.hip, lattice.hip: the item rows' + h path)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void add_kernel(float* dst, const float* src, int64_t n) {
+    for (int64_t e = blockIdx.x * static_cast<int64_t>(THREADS) + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * THREADS) {
+        const float v = dst[e], w = src[e];
+        dst[e] = v + w;
+    }
+}
+
+// dX[head[rk]][f] = sum_o Gseg[rk][o] W[o][f]: a wavefront owns 16 ranks and 64 columns; rows that are no head are not written
+// (bm3.hip, freedom.hip: the feature tables' gradient, one writer per distinct item); HW wavefronts per workgroup
+template <int HW>
+__global__ __launch_bounds__(HW * 64) void feat_grad_kernel(const float* __restrict__ Gseg, const int32_t* __restrict__ head, int n, int ld,
+                                                            const float* __restrict__ W, float* __restrict__ dX) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const int rk0 = blockIdx.x * 16;
+    const int f0 = (blockIdx.y * HW + wv) * 64;
+    if (f0 >= ld) return;
+    float a[16];
+    load_row_a(a, Gseg, rk0 + r < n ? rk0 + r : -1, g);
+    f32x4 acc[4];
+    zero_acc(acc);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+        const float* __restrict__ wrow = W + static_cast<int64_t>(16 * g + kk) * ld + f0 + r;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            const float b = f0 + nb * 16 + r < ld ? wrow[nb * 16] : 0.0f;
+            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b, acc[nb], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        const int rk = rk0 + 4 * g + rr;
+        const int64_t id = rk < n ? head[rk] : -1;
+        if (id < 0) continue;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            const int f = f0 + nb * 16 + r;
+            if (f < ld) dX[id * ld + f] = acc[nb][rr];
+        }
+    }
+}
+
+// the feature-gradient rows of the listed items := 0 (blockIdx.y: the modality; bm3.hip, freedom.hip)
+struct ClearParams {
+    float* table[2];
+    int ld[2];
+};
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void clear_rows_kernel(ClearParams p, const int32_t* __restrict__ ids, int I) {
+    float* t = p.table[blockIdx.y];
+    if (t == nullptr) return;
+    const int id = ids[blockIdx.x], ld = p.ld[blockIdx.y];
+    if (id < 0 || id >= I) return;
+    float4* row = reinterpret_cast<float4*>(t + static_cast<int64_t>(id) * ld);
+    for (int k = threadIdx.x; k < ld / 4; k += THREADS) row[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // out [LEN] = the workgroups' partial sums part [n_wg][LEN] in workgroup order

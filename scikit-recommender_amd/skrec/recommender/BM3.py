@@ -29,23 +29,19 @@ top-K path: the two factor tables come from ``skr_bm3_queries``.
 
 Limits (NotImplementedError): embed_dim <= 64, n_layers <= 4, batch_size <= 2048, 1 <= F <= 4096 per modality, one GPU.
 """
-import ctypes
-
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
 from ..utils.py import ModelConfig
-from ._graph import GraphRecommender, linear_block, propagate_mean, selfcf_adjacency, upload_csr
-from .base import DenseAdam, on_compute_stream
+from ._graph import linear_block, propagate_mean, selfcf_adjacency, upload_csr
+from ._multimodal import MODALITIES, ModalLayout, MultimodalRecommender, limit_batch, limit_features, limit_world
+from .base import DenseAdam
 
 __all__ = ["BM3", "BM3Config"]
 
 MAX_BATCH, MAX_LAYERS, MAX_FEAT = _hip.SKR_BM3_MAX_BATCH, _hip.SKR_BM3_MAX_LAYERS, _hip.SKR_BM3_MAX_FEAT
 PRED_FLOATS = _hip.SKR_BM3_PRED_FLOATS
-# (key, the reference's prefix, index of the kernel's modality slot): the reference registers the image block first
-MODALITIES = (("img", "image", 0), ("txt", "text", 1))
 
 
 class BM3Config(ModelConfig):
@@ -89,13 +85,9 @@ def check_limits(config, world=1, img_dim=None, txt_dim=None):
         raise NotImplementedError(f"BM3: embed_dim <= 64 (got {config.embed_dim}): rows are 64 floats and the predictor 64 x 64")
     if config.n_layers > MAX_LAYERS:
         raise NotImplementedError(f"BM3: n_layers <= {MAX_LAYERS} (got {config.n_layers})")
-    if config.batch_size > MAX_BATCH:
-        raise NotImplementedError(f"BM3: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_bm3_step takes {MAX_BATCH} rows")
-    for name, F in (("image", img_dim), ("text", txt_dim)):
-        if F is not None and not 1 <= F <= MAX_FEAT:
-            raise NotImplementedError(f"BM3: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
-    if world > 1:
-        raise NotImplementedError("BM3 runs on one GPU (one rank): there is no sharded engine for it")
+    limit_batch("BM3", config, MAX_BATCH)
+    limit_features("BM3", MAX_FEAT, img_dim, txt_dim)
+    limit_world("BM3", world)
 
 
 def _linear_xavier(fan_in, d):
@@ -120,29 +112,12 @@ def init_parameters(num_users, num_items, d, img_dim=None, txt_dim=None):
     return P
 
 
-def _features(a, num_items, name):
-    if a is None:
-        return None
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 2 or a.shape[0] != num_items:
-        raise ValueError(f"BM3: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
-    return a.to(torch.float32)
-
-
-class BM3(GraphRecommender):
+class BM3(MultimodalRecommender):
     """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables
     or None; ``seed`` (the run's): the key of the device draws"""
     config_class = BM3Config
-
-    def _check_limits(self, world):
-        check_limits(self.config, world)
-
-    def _build_args(self, run_config):
-        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features, "seed": getattr(run_config, "seed", 0) or 0}
-
-    def _check_data(self, img=None, txt=None, seed=0):
-        check_limits(self.config, 1, None if img is None else int(img.shape[1]), None if txt is None else int(txt.shape[1]))
+    check_limits = staticmethod(check_limits)
+    MAX_BATCH, LOSS_LEN, seeded = MAX_BATCH, 4, True
 
     def _build(self, rowptr, items, img=None, txt=None, seed=0):
         cfg, dev = self.config, self.device
@@ -151,25 +126,18 @@ class BM3(GraphRecommender):
         rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t, _ = selfcf_adjacency(rp, col, nu, ni)      # BM3.py:116-140 normalises as SelfCF does
-        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
-        self.feat_dim = {k: 0 if v is None else int(v.shape[1]) for k, v in feats.items()}
-        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
+        feats = self._features(img, txt)
         P = init_parameters(nu, ni, d, self.feat_dim["img"] or None, self.feat_dim["txt"] or None)
-        # float offsets of the blocks of the flat buffer
-        self._off = {"pred": N * 64}
-        o = N * 64 + PRED_FLOATS
-        for key, _, _ in MODALITIES:
-            if self.feat_dim[key]:
-                ld = self.feat_ld[key]
-                self._off[key + "_trs"], self._off[key + "_tab"] = o, o + 64 * ld + 64
-                o += 64 * ld + 64 + ni * ld
-        self._total = o
-        self._flat = torch.zeros(o, dtype=torch.float32, device=dev)
+        # float offsets of the blocks of the flat buffer: the predictor, then the modal blocks (key: (projection, table))
+        self._modal = ModalLayout(ni, self.feat_dim, N * 64 + PRED_FLOATS)
+        self._off = {"pred": N * 64, **self._modal.off}
+        self._total = self._modal.total
+        self._flat = torch.zeros(self._total, dtype=torch.float32, device=dev)
         self.optimizer = DenseAdam(self._flat, lr=cfg.lr)         # Adam(weight_decay=0), a constant learning rate (BM3.py:221-225)
         self._grad = self.optimizer.grad
         self.X0 = self._flat[:N * 64].view(N, 64)
         self._pred = self._flat[N * 64:N * 64 + PRED_FLOATS]
-        for key, prefix, _ in MODALITIES:
+        for key, prefix in MODALITIES:
             if feats[key] is not None:
                 P[prefix + "_embedding.weight"] = feats[key]
         self.load_parameters(P)
@@ -180,44 +148,25 @@ class BM3(GraphRecommender):
         self._G = z() if L > 0 else None
         self._Qu = torch.zeros((nu, 64), dtype=torch.float32, device=dev)
         self._Qi = torch.zeros((ni, 64), dtype=torch.float32, device=dev)
-        self._work = torch.empty(int(_hip.lib().skr_bm3_workspace(min(cfg.batch_size, MAX_BATCH))), dtype=torch.uint8, device=dev)
+        self._work = self._new_work()
         self._seed, self._step = int(seed), 0
-        self._prev_items = None        # the item ids whose feature-gradient rows the previous step wrote
         self.step_losses = []          # (graph cosines, modal cosines, reg, total) per training step, device tensors [4]
 
     # ---- the flat buffer's blocks ----------------------------------------------------------------
-    def _views(self, flat):
-        """{name: view} of ``flat`` in the reference's names and shapes"""
+    def _views(self, flat=False):
+        """{name: view} of ``flat`` (a buffer; False / True: the parameter / gradient buffer) in the reference's names and
+        shapes: user_embedding.weight, item_id_embedding.weight, predictor.weight, predictor.bias and, per present modality,
+        image_ / text_embedding.weight, _trs.weight, _trs.bias"""
         d, nu, ni = self.config.embed_dim, self.num_users, self.num_items
         N = nu + ni
+        flat = self._buffer(flat) if isinstance(flat, bool) else flat
         rows = flat[:N * 64].view(N, 64)
         W, b = linear_block(flat[N * 64:N * 64 + PRED_FLOATS], d)
         out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d], "predictor.weight": W, "predictor.bias": b}
-        for key, prefix, _ in MODALITIES:
-            F, ld = self.feat_dim[key], self.feat_ld[key]
-            if F:
-                t, e = self._off[key + "_trs"], self._off[key + "_tab"]
-                out[prefix + "_embedding.weight"] = flat[e:e + ni * ld].view(ni, ld)[:, :F]
-                out[prefix + "_trs.weight"] = flat[t:t + 64 * ld].view(64, ld)[:d, :F]
-                out[prefix + "_trs.bias"] = flat[t + 64 * ld:t + 64 * ld + d]
+        for key, prefix in MODALITIES:
+            if key in self._modal.off:
+                out.update(self._modal.views(flat, key, prefix, d))
         return out
-
-    def parameters(self):
-        """{name: tensor} in the reference's names and shapes (copies): user_embedding.weight, item_id_embedding.weight,
-        predictor.weight, predictor.bias and, per present modality, image_ / text_embedding.weight, _trs.weight, _trs.bias"""
-        return {k: v.contiguous().clone() for k, v in self._views(self._flat).items()}
-
-    def gradients(self):
-        """the gradient buffer in the shapes of ``parameters()`` (copies)"""
-        return {k: v.contiguous().clone() for k, v in self._views(self._grad).items()}
-
-    def load_parameters(self, named):
-        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
-        views = self._views(self._flat)
-        assert set(named) == set(views), sorted(set(named) ^ set(views))
-        for k, v in named.items():
-            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            views[k].copy_(t.detach().to(self.device, torch.float32))
 
     # ---- training --------------------------------------------------------------------------------
     def target_draws(self, ids, table, step=None):
@@ -228,6 +177,22 @@ class BM3(GraphRecommender):
         _hip.check(_hip.lib().skr_bm3_draws(_hip.ptr(d_ids), int(d_ids.numel()), int(table), self.config.dropout, self._seed,
                                             self._step if step is None else int(step), _hip.ptr(out), _hip.stream()))
         return out
+
+    def _workspace(self, n):
+        return int(_hip.lib().skr_bm3_workspace(n))
+
+    def _make_args(self, ids, loss, target_keep=None):
+        n, keeps = int(ids[0].numel()), None
+        if target_keep is not None:
+            ones = None
+            keeps = []
+            for k in target_keep:
+                if k is None:      # an absent modality: the kernel wants all four or none, and does not read this one
+                    ones = torch.ones((n, 64), dtype=torch.uint8, device=self.device) if ones is None else ones
+                    k = ones
+                keeps.append(self._flags(k, (n, 64)))
+        self._keeps = keeps            # alive across the launches
+        return self._step_args(*ids, keeps, loss)
 
     def _step_args(self, du, di, keeps, loss):
         """``keeps``: None or the four [n, 64] uint8 device tensors of SKR_BM3_DRAW_*"""
@@ -241,16 +206,13 @@ class BM3(GraphRecommender):
         a.n_users, a.n_items, a.dim, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, L, int(du.numel())
         a.params, a.users, a.items = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(di)
         a.grad = _hip.ptr(self._grad)
-        for key, _, m in MODALITIES:
+        for m, (key, _) in enumerate(MODALITIES):
             if not self.feat_dim[key]:
                 continue
-            t, e = self._off[key + "_trs"], self._off[key + "_tab"]
+            (trs, tab), (gtrs, gtab) = self._blocks(key), self._blocks(key, True)
             a.feat_dim[m], a.feat_ld[m] = self.feat_dim[key], self.feat_ld[key]
-            a.trs[m], a.feat[m] = _hip.ptr(self._flat[t:]), _hip.ptr(self._flat[e:])
-            a.trs_grad[m], a.feat_grad[m] = _hip.ptr(self._grad[t:]), _hip.ptr(self._grad[e:])
-        prev = self._prev_items
-        if prev is not None:
-            a.clear_items, a.n_clear = _hip.ptr(prev), int(prev.numel())
+            a.trs[m], a.feat[m], a.trs_grad[m], a.feat_grad[m] = _hip.ptr(trs), _hip.ptr(tab), _hip.ptr(gtrs), _hip.ptr(gtab)
+        self._clear_args(a)
         a.dropout, a.reg, a.cl_weight, a.seed, a.step = cfg.dropout, cfg.reg, cfg.cl_weight, self._seed, self._step
         a.M, a.G, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(loss)
         a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
@@ -263,45 +225,11 @@ class BM3(GraphRecommender):
         ``target_keep`` = (ku, ki, kt, kv), [n, 64] each -- the flags of the user, item, text and image targets at the
         batch's rows (the entries of an absent modality may be None) -- instead of the device draws;
         ``h_ms``: a ctypes float array of SKR_BM3_GROUPS entries that receives the milliseconds of each launch group"""
-        cfg = self.config
-        du, di = self._ids(users), self._ids(items)
-        n, L = int(du.numel()), cfg.n_layers
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"BM3: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert di.numel() == n
-        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
-        if n == 0:                     # skr_bm3_step launches nothing for an empty batch: a zero loss, a zero gradient
-            self._grad.zero_()
-            self._prev_items = None    # no feature-gradient row is left to clear
-            return loss
-        self._grow_work(int(_hip.lib().skr_bm3_workspace(n)))
-        keeps = None
-        if target_keep is not None:
-            ones = None
-            keeps = []
-            for k in target_keep:
-                if k is None:      # an absent modality: the kernel wants all four or none, and does not read this one
-                    ones = torch.ones((n, 64), dtype=torch.uint8, device=self.device) if ones is None else ones
-                    k = ones
-                keeps.append(self._flags(k, (n, 64)))
-        a = self._step_args(du, di, keeps, loss)
-        if h_ms is None:
-            _hip.check(_hip.lib().skr_bm3_step(ctypes.byref(a), _hip.stream()))
-        else:
-            _hip.check(_hip.lib().skr_bm3_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        self._prev_items = di
-        self._step += 1
-        return loss
+        return self._gradient_step((users, items), h_ms, target_keep=target_keep)
 
-    @on_compute_stream
-    def train_step(self, users, items, target_keep=None):
-        """one step on the pairs (users [n], items [n]) (sequences or int32 device tensors) -> device tensor of the loss
-        components (graph cosines, modal cosines, reg, their sum)"""
-        loss = self.gradient_step(users, items, target_keep=target_keep)
-        self.optimizer.step()
-        self._prev_items = None        # the Adam launch zeroes the gradient it has read: nothing is left to clear
-        self.step_losses.append(loss)
-        return loss
+    def _after_step(self, ids):
+        self._prev_items = ids[1]
+        self._step += 1
 
     # ---- ranking: the base class's, on the two factor tables (BM3.py:206-210) -----------------------
     def propagate(self):

@@ -32,26 +32,21 @@ Limits (NotImplementedError): embed_dim <= 64, n_ui_layers <= 4, n_mm_layers <= 
 1 <= F <= 4096 per modality, one GPU.  ValueError: no modality at all; a modality with feat_dim != embed_dim (the reference
 fails there on a shape mismatch).
 """
-import ctypes
-
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import PairwiseIterator
 from ..utils.item_graph import build_item_graph, knn_topk
 from ..utils.py import ModelConfig
-from ._graph import GraphRecommender, propagate_mean, run_plan, selfcf_adjacency, upload_csr
+from ._graph import propagate_mean, run_plan, selfcf_adjacency, upload_csr
+from ._multimodal import MODALITIES, ModalLayout, MultimodalRecommender, limit_batch, limit_features, limit_world
 from ._sparse import DeviceCSR
-from .base import DenseAdam, on_compute_stream
+from .base import DenseAdam
 
 __all__ = ["FREEDOM", "FREEDOMConfig"]
 
 MAX_BATCH, MAX_LAYERS, MAX_FEAT = _hip.SKR_FREEDOM_MAX_BATCH, _hip.SKR_FREEDOM_MAX_LAYERS, _hip.SKR_FREEDOM_MAX_FEAT
 MAX_KNN = _hip.SKR_KNN_MAX_K
-# (key, the reference's prefix, index of the kernel's modality slot): the reference registers the image block first
-MODALITIES = (("img", "image", 0), ("txt", "text", 1))
 
 
 class FREEDOMConfig(ModelConfig):
@@ -103,15 +98,11 @@ def check_limits(config, world=1, img_dim=None, txt_dim=None):
         raise NotImplementedError(f"FREEDOM: n_ui_layers <= {MAX_LAYERS} (got {config.n_ui_layers})")
     if config.n_mm_layers > MAX_LAYERS:
         raise NotImplementedError(f"FREEDOM: n_mm_layers <= {MAX_LAYERS} (got {config.n_mm_layers})")
-    if config.batch_size > MAX_BATCH:
-        raise NotImplementedError(f"FREEDOM: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_freedom_step takes {MAX_BATCH} rows")
+    limit_batch("FREEDOM", config, MAX_BATCH)
     if config.knn_k > MAX_KNN:
         raise NotImplementedError(f"FREEDOM: knn_k <= {MAX_KNN} (got {config.knn_k}): skr_knn_topk keeps {MAX_KNN} neighbours per row")
-    for name, F in (("image", img_dim), ("text", txt_dim)):
-        if F is not None and not 1 <= F <= MAX_FEAT:
-            raise NotImplementedError(f"FREEDOM: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
-    if world > 1:
-        raise NotImplementedError("FREEDOM runs on one GPU (one rank): there is no sharded engine for it")
+    limit_features("FREEDOM", MAX_FEAT, img_dim, txt_dim)
+    limit_world("FREEDOM", world)
 
 
 def init_parameters(num_users, num_items, d, feat_dim, img_dim=None, txt_dim=None):
@@ -130,16 +121,6 @@ def init_parameters(num_users, num_items, d, feat_dim, img_dim=None, txt_dim=Non
     return P
 
 
-def _features(a, num_items, name):
-    if a is None:
-        return None
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 2 or a.shape[0] != num_items:
-        raise ValueError(f"FREEDOM: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
-    return a.to(torch.float32)
-
-
 def edge_weights(rowptr, col, num_items):
     """w [nnz] in R's CSR order, the reference's ``_normalize_adj_m`` on the full graph in fp32 (FREEDOM.py:192-209):
     pow(1e-7 + rowcount, -0.5) * pow(1e-7 + colcount, -0.5)"""
@@ -152,20 +133,15 @@ def edge_weights(rowptr, col, num_items):
     return (r[rows] * c[cols]).contiguous()
 
 
-class FREEDOM(GraphRecommender):
+class FREEDOM(MultimodalRecommender):
     """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables
     or None; ``seed`` (the run's): the key of the device draws"""
     config_class = FREEDOMConfig
+    check_limits = staticmethod(check_limits)
+    MAX_BATCH, LOSS_LEN, seeded, pairwise = MAX_BATCH, 3, True, True
 
-    def _check_limits(self, world):
-        check_limits(self.config, world)
-
-    def _build_args(self, run_config):
-        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features, "seed": getattr(run_config, "seed", 0) or 0}
-
-    def _check_data(self, img=None, txt=None, seed=0):
+    def _check_modalities(self, img, txt):
         cfg = self.config
-        check_limits(cfg, 1, None if img is None else int(img.shape[1]), None if txt is None else int(txt.shape[1]))
         if img is None and txt is None:
             raise ValueError("FREEDOM: no modality at all -- the item graph needs an image or a text feature table")
         if cfg.feat_dim != cfg.embed_dim:
@@ -185,35 +161,24 @@ class FREEDOM(GraphRecommender):
         self.edge_w = edge_weights(rp, col, ni)
         self.adj_train, self.adj_train_t = self.adj, self.adj_t
         self._retired = []             # (event, the matrices of an earlier epoch): kept until the stream has passed the event
-        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
-        self.feat_dim = {k: 0 if v is None else int(v.shape[1]) for k, v in feats.items()}
-        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
+        feats = self._features(img, txt)
         P = init_parameters(nu, ni, d, cfg.feat_dim, self.feat_dim["img"] or None, self.feat_dim["txt"] or None)
         # the flat buffer: the rows and, at reg > 0, the modal blocks; at reg == 0 those are constants of their own
         self._modal_trained = cfg.reg > 0
-        self._off, o = {}, N * 64
-        for key, _, _ in MODALITIES:
-            if self.feat_dim[key] and self._modal_trained:
-                ld = self.feat_ld[key]
-                self._off[key] = (o, o + 64 * ld + 64)
-                o += 64 * ld + 64 + ni * ld
-        self._flat = torch.zeros(o, dtype=torch.float32, device=dev)
+        self._modal = ModalLayout(ni, self.feat_dim, N * 64 if self._modal_trained else 0)
+        self._off = self._modal.off if self._modal_trained else {}
+        self._flat = torch.zeros(self._modal.total if self._modal_trained else N * 64, dtype=torch.float32, device=dev)
         self.optimizer = DenseAdam(self._flat, lr=cfg.lr)         # Adam(weight_decay=0), a constant learning rate (FREEDOM.py:271-275)
         self._grad = self.optimizer.grad
         self.X0 = self._flat[:N * 64].view(N, 64)
-        self._const = {}
-        for key, _, _ in MODALITIES:
-            if self.feat_dim[key] and not self._modal_trained:
-                ld = self.feat_ld[key]
-                self._const[key] = (torch.zeros(64 * ld + 64, dtype=torch.float32, device=dev),
-                                    torch.zeros(ni * ld, dtype=torch.float32, device=dev))
-        for key, prefix, _ in MODALITIES:
+        self._const = None if self._modal_trained else torch.zeros(self._modal.total, dtype=torch.float32, device=dev)
+        for key, prefix in MODALITIES:
             if feats[key] is not None:
                 P[prefix + "_embedding.weight"] = feats[key]
         self.load_parameters(P)
         # the frozen item graph, from the initial feature tables (FREEDOM.py:111-124)
         knn = {}
-        for key, _, _ in MODALITIES:
+        for key, _ in MODALITIES:
             F = self.feat_dim[key]
             knn[key] = knn_topk(self._blocks(key)[1].view(ni, self.feat_ld[key]), cfg.knn_k, feat_dim=F) if F else None
         S, St = build_item_graph(knn["img"], knn["txt"], cfg.knn_k, cfg.mm_image_weight)
@@ -223,56 +188,30 @@ class FREEDOM(GraphRecommender):
         self.pooled = z()                                         # the layer means (+ h) of the last propagate()
         self._ping = (z(), z()) if max(Lu, Lm) > 1 else (None, None)
         self._G = z()
-        self._work = torch.empty(int(_hip.lib().skr_freedom_workspace(min(cfg.batch_size, MAX_BATCH))), dtype=torch.uint8, device=dev)
+        self._work = self._new_work()
         self._seed = int(seed)
-        self._prev_items = None        # the item ids whose feature-gradient rows the previous step wrote
         self.step_losses = []          # (graph term, reg * modal terms, total) per training step, device tensors [3]
 
     # ---- the blocks ------------------------------------------------------------------------------
+    def _modal_buffer(self, grad=False):
+        """the buffer of the modal blocks: the flat (``grad``: gradient) buffer at reg > 0, the constants otherwise (``grad``:
+        None)"""
+        if self._modal_trained:
+            return self._buffer(grad)
+        return None if grad else self._const
+
     def _blocks(self, key, grad=False):
-        """(projection block W [64, ld] | b [64], feature table [I, ld]) of a present modality as flat tensors: slices of the
-        flat buffer (``grad``: of the gradient buffer) at reg > 0, the constants otherwise (``grad``: None)"""
-        if not self._modal_trained:
-            return (None, None) if grad else self._const[key]
-        t, e = self._off[key]
-        ld, src = self.feat_ld[key], self._grad if grad else self._flat
-        return src[t:e], src[e:e + self.num_items * ld]
+        """(projection block W [64, ld] | b [64], feature table [I, ld]) of a present modality as flat slices of
+        ``_modal_buffer(grad)``; (None, None) where that is None"""
+        return (None, None) if self._modal_buffer(grad) is None else MultimodalRecommender._blocks(self, key, grad)
 
     def _views(self, grad=False):
-        """{name: view} in the reference's names, order and shapes; the gradient of a constant block is None"""
+        """{name: view} in the reference's names, order and shapes: user_embedding.weight, item_id_embedding.weight and, per
+        present modality, image_ / text_embedding.weight, _trs.weight, _trs.bias; the gradient of a constant block is None,
+        which ``gradients()`` reports as exact zeros"""
         d, nu, ni = self.config.embed_dim, self.num_users, self.num_items
-        rows = (self._grad if grad else self._flat)[:(nu + ni) * 64].view(nu + ni, 64)
-        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d]}
-        for key, prefix, _ in MODALITIES:
-            F, ld = self.feat_dim[key], self.feat_ld[key]
-            if not F:
-                continue
-            trs, tab = self._blocks(key, grad)
-            if trs is None:
-                out[prefix + "_embedding.weight"] = out[prefix + "_trs.weight"] = out[prefix + "_trs.bias"] = None
-                continue
-            out[prefix + "_embedding.weight"] = tab.view(ni, ld)[:, :F]
-            out[prefix + "_trs.weight"] = trs[:64 * ld].view(64, ld)[:d, :F]
-            out[prefix + "_trs.bias"] = trs[64 * ld:64 * ld + d]
-        return out
-
-    def parameters(self):
-        """{name: tensor} in the reference's names, order and shapes (copies): user_embedding.weight, item_id_embedding.weight
-        and, per present modality, image_ / text_embedding.weight, _trs.weight, _trs.bias"""
-        return {k: v.contiguous().clone() for k, v in self._views().items()}
-
-    def gradients(self):
-        """the gradient in the shapes of ``parameters()`` (copies); exact zeros for the constant blocks of reg == 0"""
-        P = self._views()
-        return {k: torch.zeros_like(P[k]).contiguous() if v is None else v.contiguous().clone() for k, v in self._views(True).items()}
-
-    def load_parameters(self, named):
-        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
-        views = self._views()
-        assert set(named) == set(views), sorted(set(named) ^ set(views))
-        for k, v in named.items():
-            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            views[k].copy_(t.detach().to(self.device, torch.float32))
+        rows = self._buffer(grad)[:(nu + ni) * 64].view(nu + ni, 64)
+        return {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d], **self._modal_views(grad, d)}
 
     # ---- the epoch's graph -----------------------------------------------------------------------
     def prune(self, epoch, keep=None):
@@ -323,6 +262,9 @@ class FREEDOM(GraphRecommender):
         return DeviceCSR.from_arrays((nu, ni), rp, col[:k], val[:k]), DeviceCSR.from_arrays((ni, nu), rpt, colt[:k], valt[:k])
 
     # ---- training --------------------------------------------------------------------------------
+    def _workspace(self, n):
+        return int(_hip.lib().skr_freedom_workspace(n))
+
     def _step_args(self, du, dp, dn, loss):
         cfg = self.config
         Lu, Lm = cfg.n_ui_layers, cfg.n_mm_layers
@@ -335,15 +277,13 @@ class FREEDOM(GraphRecommender):
         a.params, a.users, a.pos, a.neg = _hip.ptr(self._flat), _hip.ptr(du), _hip.ptr(dp), _hip.ptr(dn)
         a.grad, a.reg = _hip.ptr(self._grad), cfg.reg
         if self._modal_trained:
-            for key, _, m in MODALITIES:
+            for m, (key, _) in enumerate(MODALITIES):
                 if not self.feat_dim[key]:
                     continue
                 (trs, tab), (gtrs, gtab) = self._blocks(key), self._blocks(key, True)
                 a.feat_dim[m], a.feat_ld[m] = self.feat_dim[key], self.feat_ld[key]
                 a.trs[m], a.feat[m], a.trs_grad[m], a.feat_grad[m] = _hip.ptr(trs), _hip.ptr(tab), _hip.ptr(gtrs), _hip.ptr(gtab)
-            prev = self._prev_items
-            if prev is not None:
-                a.clear_items, a.n_clear = _hip.ptr(prev), int(prev.numel())
+            self._clear_args(a)
         a.M, a.G, a.loss = _hip.ptr(self.M), _hip.ptr(self._G), _hip.ptr(loss)
         a.ping[0], a.ping[1] = _hip.ptr(self._ping[0]), _hip.ptr(self._ping[1])
         a.work, a.work_bytes = _hip.ptr(self._work), self._work.numel()
@@ -353,48 +293,14 @@ class FREEDOM(GraphRecommender):
         """forward and backward of one batch on the installed graph without the optimiser: the gradient is left in the
         optimiser's gradient buffer, the layer means (+ h) in ``self.M`` -> device tensor (graph term, reg * modal terms,
         total).  ``h_ms``: a ctypes float array of SKR_FREEDOM_GROUPS entries that receives the milliseconds of each launch group"""
-        cfg = self.config
-        du, dp, dn = self._ids(users), self._ids(pos), self._ids(neg)
-        n, Lu, Lm = int(du.numel()), cfg.n_ui_layers, cfg.n_mm_layers
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"FREEDOM: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert dp.numel() == n and dn.numel() == n
-        loss = torch.zeros(3, dtype=torch.float32, device=self.device)
-        if n == 0:                     # skr_freedom_step launches nothing for an empty batch: a zero loss, a zero gradient
-            self._grad.zero_()
-            self._prev_items = None    # no feature-gradient row is left to clear
-            return loss
-        self._grow_work(int(_hip.lib().skr_freedom_workspace(n)))
-        a = self._step_args(du, dp, dn, loss)
-        items = torch.cat([dp, dn]) if self._modal_trained else None
-        if h_ms is None:
-            _hip.check(_hip.lib().skr_freedom_step(ctypes.byref(a), _hip.stream()))
-        else:
-            _hip.check(_hip.lib().skr_freedom_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        if items is not None:
-            self._prev_items = items
-        return loss
+        return self._gradient_step((users, pos, neg), h_ms)
 
-    @on_compute_stream
-    def train_step(self, users, pos, neg):
-        """one step on the triples (users [n], pos [n], neg [n]) (sequences or int32 device tensors) -> device tensor of the
-        loss components (graph term, reg * modal terms, their sum)"""
-        loss = self.gradient_step(users, pos, neg)
-        self.optimizer.step()
-        self._prev_items = None        # the Adam launch zeroes the gradient it has read: nothing is left to clear
-        self.step_losses.append(loss)
-        return loss
+    def _after_step(self, ids):
+        if self._modal_trained:
+            self._prev_items = torch.cat(ids[1:])
 
-    def _make_iterator(self):
-        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True, drop_last=False,
-                                sampler_mode=self.sampler_mode)
-
-    def _batches(self, data_iter, epoch):
-        return data_iter.iter_device()
-
-    def _run_epoch(self, data_iter, epoch):
+    def _begin_epoch(self, epoch):
         self.prune(epoch)              # FREEDOM.py:285 pre_epoch_processing
-        GraphRecommender._run_epoch(self, data_iter, epoch)
 
     # ---- ranking: the base class's, on the two factor tables (FREEDOM.py:254-260) ------------------
     def propagate(self):

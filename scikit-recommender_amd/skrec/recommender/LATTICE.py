@@ -37,27 +37,22 @@ knn_k <= 32, 1 <= F <= 4096 per modality, one GPU, cf_model in {"lightgcn", "mf"
 different model).  ``mess_dropout`` is accepted and unused outside ngcf, as in the reference.  ValueError: no modality at all
 (the reference fails there on an unbound name).
 """
-import ctypes
-
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import PairwiseIterator
 from ..utils.item_graph import build_weighted_item_graph, knn_topk
 from ..utils.py import ModelConfig
-from ._graph import GraphRecommender, run_plan, upload_csr
+from ._graph import run_plan, upload_csr
+from ._multimodal import MODALITIES, ModalLayout, MultimodalRecommender, lambda_lr, limit_batch, limit_features, limit_world
 from ._sparse import DeviceCSR
-from .base import DenseAdam, on_compute_stream
+from .base import DenseAdam
 
 __all__ = ["LATTICE", "LATTICEConfig"]
 
 MAX_BATCH, MAX_LAYERS, MAX_FEAT = _hip.SKR_LATTICE_MAX_BATCH, _hip.SKR_LATTICE_MAX_LAYERS, _hip.SKR_MGCN_MAX_FEAT
 MAX_KNN = _hip.SKR_KNN_MAX_K
 CF_MODELS = {"lightgcn": _hip.SKR_LATTICE_CF_LIGHTGCN, "mf": _hip.SKR_LATTICE_CF_MF}
-# (key, the reference's prefix): the reference registers the image block first
-MODALITIES = (("img", "image"), ("txt", "text"))
 NAMES = ("modal_weight", "user_embedding.weight", "item_id_embedding.weight", "image_embedding.weight", "text_embedding.weight",
          "image_trs.weight", "image_trs.bias", "text_trs.weight", "text_trs.bias")
 
@@ -115,22 +110,17 @@ def check_limits(config, world=1, img_dim=None, txt_dim=None):
         raise NotImplementedError(f"LATTICE: len(weight_size) <= {MAX_LAYERS} (got {len(config.weight_size)})")
     if config.n_layers > MAX_LAYERS:
         raise NotImplementedError(f"LATTICE: n_layers <= {MAX_LAYERS} (got {config.n_layers})")
-    if config.batch_size > MAX_BATCH:
-        raise NotImplementedError(f"LATTICE: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_lattice_step takes {MAX_BATCH} rows")
+    limit_batch("LATTICE", config, MAX_BATCH)
     if config.knn_k > MAX_KNN:
         raise NotImplementedError(f"LATTICE: knn_k <= {MAX_KNN} (got {config.knn_k}): skr_knn_topk keeps {MAX_KNN} neighbours per row")
-    for name, F in (("image", img_dim), ("text", txt_dim)):
-        if F is not None and not 1 <= F <= MAX_FEAT:
-            raise NotImplementedError(f"LATTICE: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
-    if world > 1:
-        raise NotImplementedError("LATTICE runs on one GPU (one rank): there is no sharded engine for it")
+    limit_features("LATTICE", MAX_FEAT, img_dim, txt_dim)
+    limit_world("LATTICE", world)
 
 
 def learning_rate(config, epoch):
     """the learning rate of epoch ``epoch``: LambdaLR's lr * lr_scheduler[0] ** (epoch / lr_scheduler[1]) (LATTICE.py:314-316),
     the reference's Python-float expression"""
-    g, s = config.lr_scheduler
-    return config.lr * g ** (epoch / s)
+    return lambda_lr(config.lr, config.lr_scheduler, epoch)
 
 
 def init_parameters(num_users, num_items, d, feat_embed_dim, img_dim=None, txt_dim=None):
@@ -148,16 +138,6 @@ def init_parameters(num_users, num_items, d, feat_embed_dim, img_dim=None, txt_d
             lin = nn.Linear(F, feat_embed_dim)
             P[prefix + "_trs.weight"], P[prefix + "_trs.bias"] = lin.weight.detach().clone(), lin.bias.detach().clone()
     return P
-
-
-def _features(a, num_items, name):
-    if a is None:
-        return None
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 2 or a.shape[0] != num_items:
-        raise ValueError(f"LATTICE: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
-    return a.to(torch.float32)
 
 
 def square_adjacency(rowptr, col, num_users, num_items):
@@ -187,19 +167,14 @@ def transpose_pattern(rowptr, col, n):
     return rowptr_t, rows[order].to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
 
 
-class LATTICE(GraphRecommender):
+class LATTICE(MultimodalRecommender):
     """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables
     or None"""
     config_class = LATTICEConfig
+    check_limits = staticmethod(check_limits)
+    MAX_BATCH, LOSS_LEN, pairwise = MAX_BATCH, 3, True
 
-    def _check_limits(self, world):
-        check_limits(self.config, world)
-
-    def _build_args(self, run_config):
-        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features}
-
-    def _check_data(self, img=None, txt=None):
-        check_limits(self.config, 1, None if img is None else int(img.shape[1]), None if txt is None else int(txt.shape[1]))
+    def _check_modalities(self, img, txt):
         if img is None and txt is None:
             raise ValueError("LATTICE: no modality at all -- the item graph needs an image or a text feature table")
 
@@ -213,23 +188,16 @@ class LATTICE(GraphRecommender):
         rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t = square_adjacency(rp, col, nu, ni)
-        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
-        self.feat_dim = {k: 0 if v is None else int(v.shape[1]) for k, v in feats.items()}
-        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
-        self.present = [bool(self.feat_dim[key]) for key, _ in MODALITIES]
+        feats = self._features(img, txt)
         P = init_parameters(nu, ni, d, cfg.feat_embed_dim, self.feat_dim["img"] or None, self.feat_dim["txt"] or None)
         # the two flat buffers
         self._flat = torch.zeros(N * 64, dtype=torch.float32, device=dev)
         self.optimizer = DenseAdam(self._flat, lr=cfg.lr)
         self._grad = self.optimizer.grad
         self.X0 = self._flat.view(N, 64)
-        self._off, o = {}, 4
-        for key, _ in MODALITIES:
-            if self.feat_dim[key]:
-                ld = self.feat_ld[key]
-                self._off[key] = (o, o + 64 * ld + 64)
-                o += 64 * ld + 64 + ni * ld
-        self._mflat = torch.zeros(o, dtype=torch.float32, device=dev)
+        self._modal = ModalLayout(ni, self.feat_dim, 4)          # behind modal_weight and its padding
+        self._off = self._modal.off
+        self._mflat = torch.zeros(self._modal.total, dtype=torch.float32, device=dev)
         self.modal_optimizer = DenseAdam(self._mflat, lr=cfg.lr)     # one Adam in the reference; see the module's docstring
         self._mgrad = self.modal_optimizer.grad
         self._modal_grad_dirty = False
@@ -256,7 +224,7 @@ class LATTICE(GraphRecommender):
         cap = 4 * cfg.knn_k * ni
         self._g = torch.zeros(cap, dtype=torch.float32, device=dev)
         self._dw = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._work = torch.empty(int(_hip.lib().skr_lattice_workspace(min(cfg.batch_size, MAX_BATCH), ni)), dtype=torch.uint8, device=dev)
+        self._work = self._new_work()
         self._bwd_work = torch.empty(0, dtype=torch.uint8, device=dev)
         self.graph = None              # the installed item graph: see rebuild_graph
         self._graph_version = None
@@ -264,45 +232,20 @@ class LATTICE(GraphRecommender):
         self.step_losses = []          # (BPR, regulariser, total) per training step, device tensors [3]
 
     # ---- the blocks ------------------------------------------------------------------------------
-    def _blocks(self, key, grad=False):
-        """(projection block W [64, ld] | b [64], feature table [I, ld]) of a present modality as flat slices of the modal
-        parameter (``grad``: gradient) buffer"""
-        t, e = self._off[key]
-        src = self._mgrad if grad else self._mflat
-        return src[t:e], src[e:e + self.num_items * self.feat_ld[key]]
+    def _modal_buffer(self, grad=False):
+        """the modal blocks lie in the second buffer"""
+        return self._mgrad if grad else self._mflat
 
     def _views(self, grad=False):
-        """{name: view} in the reference's names, order and shapes"""
+        """{name: view} in the reference's ``named_parameters()`` names, order and shapes; in the gradient, a modal tensor the
+        last ``gradient_step`` did not reach reads as zeros"""
         d, fd, nu, ni = self.config.embed_dim, self.config.feat_embed_dim, self.num_users, self.num_items
-        rows = (self._grad if grad else self._flat).view(nu + ni, 64)
-        out = {"modal_weight": (self._mgrad if grad else self._mflat)[:2], "user_embedding.weight": rows[:nu, :d],
-               "item_id_embedding.weight": rows[nu:, :d]}
-        for key, prefix in MODALITIES:
-            F, ld = self.feat_dim[key], self.feat_ld[key]
-            if not F:
-                continue
-            trs, tab = self._blocks(key, grad)
-            out[prefix + "_embedding.weight"] = tab.view(ni, ld)[:, :F]
-            out[prefix + "_trs.weight"] = trs[:64 * ld].view(64, ld)[:fd, :F]
-            out[prefix + "_trs.bias"] = trs[64 * ld:64 * ld + fd]
+        rows = self._buffer(grad).view(nu + ni, 64)
+        out = {"modal_weight": self._modal_buffer(grad)[:2], "user_embedding.weight": rows[:nu, :d],
+               "item_id_embedding.weight": rows[nu:, :d], **self._modal_views(grad, fd)}
         return {k: out[k] for k in NAMES if k in out}
 
-    def parameters(self):
-        """{name: tensor} in the reference's ``named_parameters()`` names, order and shapes (copies)"""
-        return {k: v.contiguous().clone() for k, v in self._views().items()}
-
-    def gradients(self):
-        """the gradient of the last ``gradient_step`` in the shapes of ``parameters()`` (copies); the gradient of a modal
-        tensor the step did not reach reads as zeros"""
-        return {k: v.contiguous().clone() for k, v in self._views(True).items()}
-
-    def load_parameters(self, named):
-        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
-        views = self._views()
-        assert set(named) == set(views), sorted(set(named) ^ set(views))
-        for k, v in named.items():
-            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            views[k].copy_(t.detach().to(self.device, torch.float32))
+    def _loaded(self):
         self._version += 1
 
     # ---- the learned graph -----------------------------------------------------------------------
@@ -395,24 +338,24 @@ class LATTICE(GraphRecommender):
         constant and that buffer reads as zeros -> device tensor (BPR, regulariser, total).  ``h_ms``: a ctypes float array of
         SKR_LATTICE_GROUPS entries that receives the milliseconds of each launch group of the step; ``knn_in`` / ``knn_out``
         (build steps): see ``rebuild_graph``"""
-        cfg, L, st, p = self.config, _hip.lib(), _hip.stream(), _hip.ptr
-        du, dp, dn = self._ids(users), self._ids(pos), self._ids(neg)
-        n, Ln, ni = int(du.numel()), cfg.n_layers, self.num_items
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"LATTICE: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert dp.numel() == n and dn.numel() == n
-        build = bool(build) and Ln > 0
+        return self._gradient_step((users, pos, neg), h_ms, build=build, knn_in=knn_in, knn_out=knn_out)
+
+    def _before_step(self):
         if self._modal_grad_dirty:
             self._mgrad.zero_()
             self._modal_grad_dirty = False
-        loss = torch.zeros(3, dtype=torch.float32, device=self.device)
-        if n == 0:
-            self._grad.zero_()
-            return loss
+
+    def _workspace(self, n):
+        return int(_hip.lib().skr_lattice_workspace(n, self.num_items))
+
+    def _make_args(self, ids, loss, build=False, knn_in=None, knn_out=None):
+        cfg, p, (du, dp, dn) = self.config, _hip.ptr, ids
+        n, Ln, ni = int(du.numel()), cfg.n_layers, self.num_items
+        build = bool(build) and Ln > 0
         G = None
         if Ln > 0:
             G = self._current_graph(knn_in, knn_out) if build or self.graph is None else self.graph
-        self._grow_work(int(L.skr_lattice_workspace(n, ni)))
+        self._built = G if build else None         # the graph that ``_after_step`` carries the gradient through
         a = _hip.LatticeStepArgs()
         if self.n_ui_layers > 0 and cfg.cf_model == "lightgcn":
             a.plan_p, a.plan_pt = self.adj._plan_handle(), self.adj_t._plan_handle()
@@ -426,14 +369,11 @@ class LATTICE(GraphRecommender):
         if build:
             a.H, a.g_out, a.s_rowptr, a.s_col = p(self._H), p(self._g), p(G["S"].rowptr), p(G["S"].col)
         a.work, a.work_bytes = p(self._work), self._work.numel()
-        if h_ms is None:
-            _hip.check(L.skr_lattice_step(ctypes.byref(a), st))
-        else:
-            _hip.check(L.skr_lattice_step_timed(ctypes.byref(a), st, h_ms))
-        self._keep = (du, dp, dn)      # alive across the launches
-        if build:
-            self.graph_backward(G)
-        return loss
+        return a
+
+    def _after_step(self, ids):
+        if self._built is not None:
+            self.graph_backward(self._built)
 
     def graph_backward(self, G):
         """from ``dLoss/dS`` (left in ``_g`` by a build step) to the modal gradient buffer: ``skr_lattice_graph_bwd`` to the
@@ -466,32 +406,15 @@ class LATTICE(GraphRecommender):
                                               p(self._bwd_work), self._bwd_work.numel(), st))
         self._modal_grad_dirty = True
 
-    @on_compute_stream
-    def train_step(self, users, pos, neg, build=False, knn_in=None, knn_out=None):
-        """one step on the triples (users [n], pos [n], neg [n]) (sequences or int32 device tensors) -> device tensor of the
-        loss components (BPR, regulariser, their sum).  ``build``: the first step of an epoch (LATTICE.py:168-169, 285-286)"""
-        build = bool(build) and self.config.n_layers > 0
-        loss = self.gradient_step(users, pos, neg, build=build, knn_in=knn_in, knn_out=knn_out)
-        self.optimizer.step()
-        if build:                      # torch's Adam skips a tensor without a gradient: the modal block moves on build steps only
+    def _after_optimizer(self, build=False, **kw):
+        """``train_step(..., build=True)``: the first step of an epoch (LATTICE.py:168-169, 285-286)"""
+        if build and self.config.n_layers > 0:     # torch's Adam skips a tensor without a gradient: the modal block moves on build steps only
             self.modal_optimizer.step()
             self._modal_grad_dirty = False     # the Adam launch zeroes the gradient it has read
         self._version += 1
-        self.step_losses.append(loss)
-        return loss
 
-    def _make_iterator(self):
-        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True, drop_last=False,
-                                sampler_mode=self.sampler_mode)
-
-    def _batches(self, data_iter, epoch):
-        return data_iter.iter_device()
-
-    def set_epoch(self, epoch):
-        """installs the learning rate of epoch ``epoch`` in both optimisers (the reference steps its LambdaLR after each epoch,
-        LATTICE.py:338)"""
-        self.optimizer.lr = self.modal_optimizer.lr = float(learning_rate(self.config, epoch))
-        return self.optimizer.lr
+    def _optimizers(self):
+        return self.optimizer, self.modal_optimizer
 
     def _run_epoch(self, data_iter, epoch):
         self.set_epoch(epoch)

@@ -22,19 +22,16 @@ Ranking: ``<out_u, out_i>`` of a full forward -- two plain factor tables for the
 Limits (NotImplementedError): embed_dim <= 64, n_ui_layers <= 4, n_layers <= 4, batch_size <= 2048, knn_k <= 32,
 1 <= F <= 4096 per modality, one GPU.  ValueError: a missing modality (the reference's forward uses both unconditionally).
 """
-import ctypes
-
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from ..io import PairwiseIterator
 from ..utils.item_graph import build_weighted_item_graph, knn_topk
 from ..utils.py import ModelConfig
-from ._graph import GraphRecommender, _adjacency, propagate_mean, run_plan, upload_csr
+from ._graph import _adjacency, propagate_mean, run_plan, upload_csr
+from ._multimodal import ModalLayout, MultimodalRecommender, lambda_lr, limit_batch, limit_features, limit_world
 from ._sparse import DeviceCSR
-from .base import DenseAdam, on_compute_stream
+from .base import DenseAdam
 
 __all__ = ["MGCN", "MGCNConfig"]
 
@@ -94,22 +91,17 @@ def check_limits(config, world=1, img_dim=None, txt_dim=None):
         raise NotImplementedError(f"MGCN: n_ui_layers <= {MAX_LAYERS} (got {config.n_ui_layers})")
     if config.n_layers > MAX_LAYERS:
         raise NotImplementedError(f"MGCN: n_layers <= {MAX_LAYERS} (got {config.n_layers})")
-    if config.batch_size > MAX_BATCH:
-        raise NotImplementedError(f"MGCN: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_mgcn_step takes {MAX_BATCH} rows")
+    limit_batch("MGCN", config, MAX_BATCH)
     if config.knn_k > MAX_KNN:
         raise NotImplementedError(f"MGCN: knn_k <= {MAX_KNN} (got {config.knn_k}): skr_knn_topk keeps {MAX_KNN} neighbours per row")
-    for name, F in (("image", img_dim), ("text", txt_dim)):
-        if F is not None and not 1 <= F <= MAX_FEAT:
-            raise NotImplementedError(f"MGCN: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
-    if world > 1:
-        raise NotImplementedError("MGCN runs on one GPU (one rank): there is no sharded engine for it")
+    limit_features("MGCN", MAX_FEAT, img_dim, txt_dim)
+    limit_world("MGCN", world)
 
 
 def learning_rate(config, epoch):
     """the learning rate of epoch ``epoch``: LambdaLR's lr * lr_scheduler[0] ** (epoch / lr_scheduler[1]) (MGCN.py:373-375), the
     reference's Python-float expression"""
-    g, s = config.lr_scheduler
-    return config.lr * g ** (epoch / s)
+    return lambda_lr(config.lr, config.lr_scheduler, epoch)
 
 
 def init_parameters(num_users, num_items, d, img_dim, txt_dim):
@@ -132,16 +124,6 @@ def init_parameters(num_users, num_items, d, img_dim, txt_dim):
     return {k: v.detach().clone() for k, v in P.items()}
 
 
-def _features(a, num_items, name):
-    if a is None:
-        raise ValueError(f"MGCN: the {name} feature table is missing -- the model's forward uses both modalities")
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 2 or a.shape[0] != num_items:
-        raise ValueError(f"MGCN: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
-    return a.to(torch.float32)
-
-
 def mgcn_adjacency(rowptr, col, num_users, num_items):
     """(R, R^T) as DeviceCSR from the binary train CSR in HBM: rowdeg^-0.5 * coldeg^-0.5 in fp32, no self loops, no epsilon
     (MGCN.py:213-240; an entry's row and column have a degree of at least 1, so the reference's inf -> 0 never applies to one)"""
@@ -150,22 +132,12 @@ def mgcn_adjacency(rowptr, col, num_users, num_items):
     return _adjacency(rowptr, col, num_users, num_items, value, False)[:2]
 
 
-class MGCN(GraphRecommender):
+class MGCN(MultimodalRecommender):
     """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables,
     both required"""
     config_class = MGCNConfig
-
-    def _check_limits(self, world):
-        check_limits(self.config, world)
-
-    def _build_args(self, run_config):
-        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features}
-
-    def _check_data(self, img=None, txt=None):
-        for name, a in (("image", img), ("text", txt)):
-            if a is None:
-                raise ValueError(f"MGCN: the {name} feature table is missing -- the model's forward uses both modalities")
-        check_limits(self.config, 1, int(img.shape[1]), int(txt.shape[1]))
+    check_limits = staticmethod(check_limits)
+    MAX_BATCH, LOSS_LEN, required, pairwise = MAX_BATCH, 4, True, True
 
     def _build(self, rowptr, items, img=None, txt=None):
         cfg, dev = self.config, self.device
@@ -174,16 +146,11 @@ class MGCN(GraphRecommender):
         rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t = mgcn_adjacency(rp, col, nu, ni)
-        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
-        self.feat_dim = {k: int(v.shape[1]) for k, v in feats.items()}
-        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
+        feats = self._features(img, txt)
         P = init_parameters(nu, ni, d, self.feat_dim["img"], self.feat_dim["txt"])
         # the flat buffer
-        self._off, o = {}, N * 64
-        for key, _, _, _ in MODALITIES:
-            ld = self.feat_ld[key]
-            self._off[key] = (o, o + 64 * ld + 64)        # the projection block, the table
-            o += 64 * ld + 64 + ni * ld
+        self._modal = ModalLayout(ni, self.feat_dim, N * 64)
+        self._off, o = dict(self._modal.off), self._modal.total        # key: (the projection block, the table)
         for name, size in (("gate_v.0", GATE), ("gate_t.0", GATE), ("query", QUERY), ("gate_image_prefer.0", GATE),
                            ("gate_text_prefer.0", GATE)):
             self._off[name] = o
@@ -207,33 +174,19 @@ class MGCN(GraphRecommender):
         self._F, self._gout = (z(ni), z(ni)), (z(ni), z(ni))
         self._Z, self._G, self._ping = (z(N), z(N)), (z(N), z(N), z(N)), (z(N), z(N))
         self._ld_max = max(self.feat_ld.values())
-        self._work = torch.empty(int(_hip.lib().skr_mgcn_workspace(min(cfg.batch_size, MAX_BATCH), ni, self._ld_max)), dtype=torch.uint8,
-                                 device=dev)
+        self._work = self._new_work()
         self.step_losses = []          # (BPR, regulariser, cl_loss * InfoNCE, total) per training step, device tensors [4]
 
     # ---- the blocks ------------------------------------------------------------------------------
-    def _blocks(self, key, grad=False):
-        """(projection block W [64, ld] | b [64], feature table [I, ld]) of a modality as flat slices of the parameter (``grad``:
-        gradient) buffer"""
-        t, e = self._off[key]
-        src = self._grad if grad else self._flat
-        return src[t:e], src[e:e + self.num_items * self.feat_ld[key]]
-
     def _block(self, name, grad=False):
         o = self._off[name]
-        return (self._grad if grad else self._flat)[o:o + (QUERY if name == "query" else GATE)]
+        return self._buffer(grad)[o:o + (QUERY if name == "query" else GATE)]
 
     def _views(self, grad=False):
-        """{name: view} in the reference's names, order and shapes"""
+        """{name: view} in the reference's ``named_parameters()`` names, order and shapes"""
         d, nu, ni = self.config.embed_dim, self.num_users, self.num_items
-        rows = (self._grad if grad else self._flat)[:(nu + ni) * 64].view(nu + ni, 64)
-        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d]}
-        for key, prefix, _, _ in MODALITIES:
-            F, ld = self.feat_dim[key], self.feat_ld[key]
-            trs, tab = self._blocks(key, grad)
-            out[prefix + "_embedding.weight"] = tab.view(ni, ld)[:, :F]
-            out[prefix + "_trs.weight"] = trs[:64 * ld].view(64, ld)[:d, :F]
-            out[prefix + "_trs.bias"] = trs[64 * ld:64 * ld + d]
+        rows = self._buffer(grad)[:(nu + ni) * 64].view(nu + ni, 64)
+        out = {"user_embedding.weight": rows[:nu, :d], "item_id_embedding.weight": rows[nu:, :d], **self._modal_views(grad, d)}
         q = self._block("query", grad)
         out["query_common.0.weight"], out["query_common.0.bias"] = q[:4096].view(64, 64)[:d, :d], q[4096:4096 + d]
         out["query_common.2.weight"] = q[GATE:GATE + d].view(1, d)
@@ -242,39 +195,18 @@ class MGCN(GraphRecommender):
             out[name + ".weight"], out[name + ".bias"] = b[:4096].view(64, 64)[:d, :d], b[4096:4096 + d]
         return {k: out[k] for k in NAMES}
 
-    def parameters(self):
-        """{name: tensor} in the reference's ``named_parameters()`` names, order and shapes (copies)"""
-        return {k: v.contiguous().clone() for k, v in self._views().items()}
-
-    def gradients(self):
-        """the gradient in the shapes of ``parameters()`` (copies)"""
-        return {k: v.contiguous().clone() for k, v in self._views(True).items()}
-
-    def load_parameters(self, named):
-        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
-        views = self._views()
-        assert set(named) == set(views), sorted(set(named) ^ set(views))
-        for k, v in named.items():
-            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            views[k].copy_(t.detach().to(self.device, torch.float32))
-
     # ---- training --------------------------------------------------------------------------------
     def gradient_step(self, users, pos, neg, h_ms=None):
         """forward and backward of one batch without the optimiser: the gradient is left in the optimiser's gradient buffer,
         every element written -> device tensor (BPR, regulariser, cl_loss * InfoNCE, total).  ``h_ms``: a ctypes float array of
         SKR_MGCN_GROUPS entries that receives the milliseconds of each launch group"""
-        cfg = self.config
-        du, dp, dn = self._ids(users), self._ids(pos), self._ids(neg)
-        n = int(du.numel())
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"MGCN: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert dp.numel() == n and dn.numel() == n
-        if n > 0:
-            self._grow_work(int(_hip.lib().skr_mgcn_workspace(n, self.num_items, self._ld_max)))
-        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
-        if n == 0:
-            self._grad.zero_()
-            return loss
+        return self._gradient_step((users, pos, neg), h_ms)
+
+    def _workspace(self, n):
+        return int(_hip.lib().skr_mgcn_workspace(n, self.num_items, self._ld_max))
+
+    def _step_args(self, du, dp, dn, loss):
+        cfg, n = self.config, int(du.numel())
         a, p = _hip.MGCNStepArgs(), _hip.ptr
         a.plan_a, a.plan_at = self.adj._plan_handle(), self.adj_t._plan_handle()
         a.n_users, a.n_items, a.dim, a.n_ui_layers, a.n_layers, a.n = self.num_users, self.num_items, cfg.embed_dim, cfg.n_ui_layers, cfg.n_layers, n
@@ -295,37 +227,7 @@ class MGCN(GraphRecommender):
         for t in range(3):
             a.G[t] = p(self._G[t])
         a.work, a.work_bytes = p(self._work), self._work.numel()
-        if h_ms is None:
-            _hip.check(_hip.lib().skr_mgcn_step(ctypes.byref(a), _hip.stream()))
-        else:
-            _hip.check(_hip.lib().skr_mgcn_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        self._keep = (du, dp, dn)      # alive across the launches
-        return loss
-
-    @on_compute_stream
-    def train_step(self, users, pos, neg):
-        """one step on the triples (users [n], pos [n], neg [n]) (sequences or int32 device tensors) -> device tensor of the
-        loss components (BPR, regulariser, cl_loss * InfoNCE, their sum)"""
-        loss = self.gradient_step(users, pos, neg)
-        self.optimizer.step()
-        self.step_losses.append(loss)
-        return loss
-
-    def _make_iterator(self):
-        return PairwiseIterator(self.dataset.train_data, batch_size=self.config.batch_size, shuffle=True, drop_last=False,
-                                sampler_mode=self.sampler_mode)
-
-    def _batches(self, data_iter, epoch):
-        return data_iter.iter_device()
-
-    def set_epoch(self, epoch):
-        """installs the learning rate of epoch ``epoch`` (the reference steps its LambdaLR after each epoch, MGCN.py:397)"""
-        self.optimizer.lr = float(learning_rate(self.config, epoch))
-        return self.optimizer.lr
-
-    def _run_epoch(self, data_iter, epoch):
-        self.set_epoch(epoch)
-        GraphRecommender._run_epoch(self, data_iter, epoch)
+        return a
 
     # ---- ranking: the base class's, on the two factor tables (MGCN.py:355-361) ----------------------
     def propagate(self):

@@ -29,16 +29,15 @@ parameters.  ``predict()`` returns the sigmoid of the scores, as the reference d
 Limits (NotImplementedError): the branches the reference itself cannot run (``check_limits`` names each), rec_dim <= 64,
 layer_num <= 4, batch_size <= 2048, 1 <= F <= 4096 per modality, one GPU.  ValueError: a missing modality.
 """
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
 from ..utils.py import ModelConfig
-from ._graph import GraphRecommender, _adjacency, run_plan, upload_csr
-from .base import DenseAdam, on_compute_stream
+from ._graph import _adjacency, run_plan, upload_csr
+from ._multimodal import ModalLayout, MultimodalRecommender, lambda_lr, limit_batch, limit_features, limit_world
+from .base import DenseAdam
 
 __all__ = ["SLMRec", "SLMRecConfig"]
 
@@ -116,19 +115,15 @@ def check_limits(config, world=1, img_dim=None, txt_dim=None, data_name=None):
         raise NotImplementedError(f"SLMRec: rec_dim <= 64 (got {config.rec_dim}): rows are 64 floats")
     if config.layer_num > MAX_LAYERS:
         raise NotImplementedError(f"SLMRec: layer_num <= {MAX_LAYERS} (got {config.layer_num})")
-    if config.batch_size > MAX_BATCH:
-        raise NotImplementedError(f"SLMRec: batch_size <= {MAX_BATCH} (got {config.batch_size}): skr_slmrec_step takes {MAX_BATCH} rows")
-    for name, F in (("image", img_dim), ("text", txt_dim)):
-        if F is not None and not 1 <= F <= MAX_FEAT:
-            raise NotImplementedError(f"SLMRec: 1 <= feature width <= {MAX_FEAT} (the {name} table has {F} columns)")
-    if world > 1:
-        raise NotImplementedError("SLMRec runs on one GPU (one rank): there is no sharded engine for it")
+    limit_batch("SLMRec", config, MAX_BATCH)
+    limit_features("SLMRec", MAX_FEAT, img_dim, txt_dim)
+    limit_world("SLMRec", world)
 
 
 def learning_rate(config, epoch):
     """the learning rate of epoch ``epoch``: LambdaLR's lr * lr_scheduler[0] ** (epoch / lr_scheduler[1]) with the reference's
     fixed lr_scheduler = [1.0, 50] (SLMRec.py:545-547) -- constant; the reference's Python-float expression"""
-    return config.lr * LR_SCHEDULER[0] ** (epoch / LR_SCHEDULER[1])
+    return lambda_lr(config.lr, LR_SCHEDULER, epoch)
 
 
 def init_parameters(num_users, num_items, d, img_dim, txt_dim):
@@ -181,33 +176,16 @@ def slmrec_adjacency(rowptr, col, num_users, num_items):
     return _adjacency(rowptr, col, num_users, num_items, value, False)[:2]
 
 
-def _features(a, num_items, name):
-    if a is None:
-        raise ValueError(f"SLMRec: the {name} feature table is missing -- the model's forward uses both modalities")
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dim() != 2 or a.shape[0] != num_items:
-        raise ValueError(f"SLMRec: the {name} feature table has shape {tuple(a.shape)}, the data set has {num_items} items")
-    return torch.nn.functional.normalize(a.to(torch.float32), dim=1)          # SLMRec.py:448, 453: eps 1e-12, once
-
-
-class SLMRec(GraphRecommender):
+class SLMRec(MultimodalRecommender):
     """limits: see ``check_limits``; ``img`` / ``txt`` (``detached``; the data set's otherwise): [num_items, F] feature tables,
     both required, normalised here"""
     config_class = SLMRecConfig
-
-    def _check_limits(self, world):
-        check_limits(self.config, world)
+    check_limits = staticmethod(check_limits)
+    MAX_BATCH, LOSS_LEN, required, lr_scheduler = MAX_BATCH, 4, True, LR_SCHEDULER
 
     def _build_args(self, run_config):
         check_limits(self.config, 1, data_name=getattr(self.dataset, "data_name", None))
-        return {"img": self.dataset.img_features, "txt": self.dataset.txt_features}
-
-    def _check_data(self, img=None, txt=None):
-        for name, a in (("image", img), ("text", txt)):
-            if a is None:
-                raise ValueError(f"SLMRec: the {name} feature table is missing -- the model's forward uses both modalities")
-        check_limits(self.config, 1, int(img.shape[1]), int(txt.shape[1]))
+        return MultimodalRecommender._build_args(self, run_config)
 
     def _build(self, rowptr, items, img=None, txt=None):
         cfg, dev = self.config, self.device
@@ -216,19 +194,15 @@ class SLMRec(GraphRecommender):
         rp, col = upload_csr(rowptr, items, dev)
         assert rp.numel() == nu + 1
         self.adj, self.adj_t = slmrec_adjacency(rp, col, nu, ni)
-        feats = {"img": _features(img, ni, "image"), "txt": _features(txt, ni, "text")}
-        self.feat_dim = {k: int(v.shape[1]) for k, v in feats.items()}
-        self.feat_ld = {k: (F + 3) // 4 * 4 for k, F in self.feat_dim.items()}
+        feats = self._features(img, txt)
         self.feat = {}
-        for key, v in feats.items():           # the constant tables [I, ld], zero beyond F
+        for key, v in feats.items():           # the constant tables [I, ld], row-normalised once (SLMRec.py:448, 453: eps 1e-12), zero beyond F
             tab = torch.zeros((ni, self.feat_ld[key]), dtype=torch.float32, device=dev)
-            tab[:, :self.feat_dim[key]] = v.to(dev)
+            tab[:, :self.feat_dim[key]] = torch.nn.functional.normalize(v, dim=1).to(dev)
             self.feat[key] = tab
         # the flat buffer: the trained part, then g_a_iva
-        self._off, o = {}, N * 64
-        for key, name, _ in MODALITIES:
-            self._off[name] = (o, 64 * self.feat_ld[key] + 64)
-            o += 64 * self.feat_ld[key] + 64
+        self._modal = ModalLayout(ni, self.feat_dim, N * 64, tables=False)
+        self._off, o = {name: (self._modal.off[key][0], 64 * self.feat_ld[key] + 64) for key, name, _ in MODALITIES}, self._modal.total
         for name in FUSIONS:
             self._off[name] = (o, FUSION)
             o += FUSION
@@ -250,24 +224,22 @@ class SLMRec(GraphRecommender):
         self._D, self._dD = (z(ni), z(ni)), z(ni)
         self._G, self._ping = (z(N), z(N), z(N)), (z(N), z(N))
         self._ld_max = max(self.feat_ld.values())
-        self._work = torch.empty(int(_hip.lib().skr_slmrec_workspace(min(cfg.batch_size, MAX_BATCH), ni, self._ld_max)), dtype=torch.uint8,
-                                 device=dev)
+        self._work = self._new_work()
         self.step_losses = []          # (main, ssl_alpha v_loss, ssl_alpha t_loss, total) per training step, device tensors [4]
 
     # ---- the blocks ------------------------------------------------------------------------------
     def _block(self, name, grad=False):
         o, size = self._off[name]
         assert not (grad and name == "g_a_iva"), "g_a_iva has no gradient"
-        return (self._grad if grad else self._flat)[o:o + size]
+        return self._buffer(grad)[o:o + size]
 
     def _views(self, grad=False):
         """{name: view}: the reference's names and order; a fusion weight as [d, 3, d] (the reference's [d, 3 d] split by table)"""
         d, nu, ni = self.config.rec_dim, self.num_users, self.num_items
-        rows = (self._grad if grad else self._flat)[:(nu + ni) * 64].view(nu + ni, 64)
+        rows = self._buffer(grad)[:(nu + ni) * 64].view(nu + ni, 64)
         out = {"embedding_user.weight": rows[:nu, :d], "embedding_item.weight": rows[nu:, :d]}
         for key, name, _ in MODALITIES:
-            F, ld, b = self.feat_dim[key], self.feat_ld[key], self._block(name, grad)
-            out[name + ".weight"], out[name + ".bias"] = b[:64 * ld].view(64, ld)[:d, :F], b[64 * ld:64 * ld + d]
+            out[name + ".weight"], out[name + ".bias"] = self._modal.linear(self._block(name, grad), key, d)
         for name in FUSIONS:
             b = self._block(name, grad)
             out[name + ".weight"], out[name + ".bias"] = b[:64 * 192].view(64, 3, 64)[:d, :, :d], b[64 * 192:64 * 192 + d]
@@ -276,28 +248,21 @@ class SLMRec(GraphRecommender):
             out[name + ".weight"], out[name + ".bias"] = b[:4096].view(64, 64)[:do, :d], b[4096:4096 + do]
         return {k: out[k] for k in NAMES if k in out}
 
-    def _copies(self, grad):
+    def _to_reference(self, v):
+        """a fusion weight as the reference's [d, 3 d]; ``gradients()`` has no g_a_iva"""
         d = self.config.rec_dim
-        return {k: (v.reshape(d, 3 * d) if v.dim() == 3 else v.contiguous()).clone() for k, v in self._views(grad).items()}
+        return (v.reshape(d, 3 * d) if v.dim() == 3 else v.contiguous()).clone()
 
-    def parameters(self):
-        """{name: tensor} in the reference's ``named_parameters()`` names, order and shapes (copies)"""
-        return self._copies(False)
+    def _from_reference(self, t, view):
+        return t.reshape(view.shape)
 
-    def gradients(self):
-        """the gradient in the shapes of ``parameters()`` (copies); g_a_iva has none"""
-        return self._copies(True)
-
-    def load_parameters(self, named):
-        """sets the parameters from a dict in the names and shapes of ``parameters()`` (padding stays zero)"""
-        views = self._views()
-        assert set(named) == set(views), sorted(set(named) ^ set(views))
-        for k, v in named.items():
-            t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-            views[k].copy_(t.detach().to(self.device, torch.float32).reshape(views[k].shape))
+    def _loaded(self):
         self._forward_current = False
 
     # ---- training --------------------------------------------------------------------------------
+    def _workspace(self, n):
+        return int(_hip.lib().skr_slmrec_workspace(n, self.num_items, self._ld_max))
+
     def _step_args(self, du, dp, loss):
         """skr_slmrec_step_args of one batch (int32 device tensors) on this model's buffers"""
         cfg = self.config
@@ -326,44 +291,12 @@ class SLMRec(GraphRecommender):
         every element written, the three propagated tables in ``self.M`` -> device tensor (main, ssl_alpha v_loss, ssl_alpha
         t_loss, total).  ``h_ms``: a ctypes float array of SKR_SLMREC_GROUPS entries that receives the milliseconds of each
         launch group"""
-        du, dp = self._ids(users), self._ids(pos)
-        n = int(du.numel())
-        if n > MAX_BATCH:
-            raise NotImplementedError(f"SLMRec: a batch holds at most {MAX_BATCH} rows (got {n})")
-        assert dp.numel() == n
-        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
-        if n == 0:
-            self._grad.zero_()
-            return loss
-        self._grow_work(int(_hip.lib().skr_slmrec_workspace(n, self.num_items, self._ld_max)))
-        a = self._step_args(du, dp, loss)
-        if h_ms is None:
-            _hip.check(_hip.lib().skr_slmrec_step(ctypes.byref(a), _hip.stream()))
-        else:
-            _hip.check(_hip.lib().skr_slmrec_step_timed(ctypes.byref(a), _hip.stream(), h_ms))
-        self._keep = (du, dp)          # alive across the launches
+        return self._gradient_step((users, pos), h_ms)
+
+    def _after_step(self, ids):
+        """the fusion blocks are copied to the snapshot before the Adam launch of ``train_step``"""
         self._fusion_snapshot.copy_(self._fusion)          # M and the snapshot: the forward the reference ranks on
         self._forward_current = True
-        return loss
-
-    @on_compute_stream
-    def train_step(self, users, pos):
-        """one step on the pairs (users [n], pos [n]) (sequences or int32 device tensors) -> device tensor of the loss components
-        (main, ssl_alpha v_loss, ssl_alpha t_loss, their sum).  The fusion blocks are copied to the snapshot before the Adam
-        launch"""
-        loss = self.gradient_step(users, pos)
-        self.optimizer.step()
-        self.step_losses.append(loss)
-        return loss
-
-    def set_epoch(self, epoch):
-        """installs the learning rate of epoch ``epoch`` (the reference steps its LambdaLR after each epoch, SLMRec.py:567)"""
-        self.optimizer.lr = float(learning_rate(self.config, epoch))
-        return self.optimizer.lr
-
-    def _run_epoch(self, data_iter, epoch):
-        self.set_epoch(epoch)
-        GraphRecommender._run_epoch(self, data_iter, epoch)
 
     # ---- ranking (SLMRec.py:366-376) ----------------------------------------------------------------
     def _mean(self, Xi0, M):

@@ -3,6 +3,10 @@ adjacency pair (A, A^T) built in HBM, the plain run of a SpMM plan, the layer-me
 linear block of the flat parameter buffer, and ``GraphRecommender`` -- the epoch of steps and the propagate-then-rank
 half on ``DeviceRecommender`` (base.py).  A model keeps its config, its limits, its draws, ``_build``, ``gradient_step``,
 ``train_step`` and what is its own in ``propagate``.
+
+Which model sits on which base: LightGCL, DENS and SelfCF on ``GraphRecommender`` directly; BM3, FREEDOM, MGCN, LATTICE and
+SLMRec on ``MultimodalRecommender`` (_multimodal.py), which adds the feature tables, the modal blocks' layout, the parameter
+dictionaries and the frame of the step; LightGCN and LayerGCN on ``FullGraphBPR`` (_fullgraph.py), beside this module.
 """
 import numpy as np
 import torch

@@ -142,7 +142,7 @@ def run_layers(args, ds, img, txt, L, dev):
     res["project_ms"] = {}
     for key in ("img", "txt"):
         if m.feat_dim[key]:
-            t, e = m._off[key + "_trs"], m._off[key + "_tab"]
+            t, e = m._off[key]
 
             def project():
                 _hip.check(Lb.skr_bm3_project(_hip.ptr(m._flat[e:]), nI, m.feat_dim[key], m.feat_ld[key], _hip.ptr(m._flat[t:]),
@@ -156,7 +156,7 @@ def run_layers(args, ds, img, txt, L, dev):
     n_feat, ms_feat = 0, 0.0
     for key in ("img", "txt"):
         if m.feat_dim[key]:
-            e, cnt = m._off[key + "_tab"], nI * m.feat_ld[key]
+            e, cnt = m._off[key][1], nI * m.feat_ld[key]
 
             def table():
                 _hip.check(Lb.skr_adam_step(_hip.ptr(opt.flat[e:]), _hip.ptr(opt.grad[e:]), _hip.ptr(opt.m[e:]), _hip.ptr(opt.v[e:]), cnt, opt.lr,
