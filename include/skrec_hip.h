@@ -1590,6 +1590,79 @@ int skr_slmrec_step(const skr_slmrec_step_args* args, void* stream);
 #define SKR_SLMREC_GROUPS 8
 int skr_slmrec_step_timed(const skr_slmrec_step_args* args, void* stream, float* h_ms);
 
+/* ============================================================================================
+ * Caser -- convolutional sequence embedding (csrc/caser.hip)
+ * replaces: _Caser._forward_user / forward / predict and Caser.fit's step (recommender/Caser.py:118-162,191-207).
+ * Rows are 64 floats (dim must be 64; `width` <= 64 is the model's embed_size: narrower embeddings are zero-padded by the
+ * caller, and the vertical filters' outputs beyond `width` are held at zero).  Tables: d_U [n_users, 64]; d_E
+ * (item_embeddings) [n_rows, 64]; d_W2 [n_rows, 128], a row being the z half then the p half, each zero beyond width;
+ * d_b2 [n_rows]; n_rows = items + 1.  pad_idx names a padding row that reads as zeros in a window and never receives a
+ * gradient, in d_E, d_W2 and d_b2 alike; -1: no such row (the reference builds its tables without padding_idx,
+ * Caser.py:179, so its padding item is an ordinary row: skrec/recommender/Caser.py passes -1).
+ * d_shared: the shared parameters, SKR_CASER_SHARED_FLOATS(L, nv, nh) floats, 16-byte aligned, every part on a 64-float
+ * boundary and zero where padded:
+ *   conv_v.weight [nv][L] (64 floats) | conv_v.bias [nv] (64 floats) |
+ *   the horizontal filters, SKR_CASER_ROWS(L, nh) rows of 64 floats: for h = 1..L, for k < nh, for r < h the row
+ *     conv_h[h-1].weight[k, 0, r, :] -- row nh h (h - 1) / 2 + k h + r |
+ *   conv_h[h-1].bias[k] at (h - 1) nh + k, L nh floats rounded up to a multiple of 64 |
+ *   fc1.weight [64][Fp]: row j (an output), column c 64 + col for the vertical filter c's column col, column nv 64 + (h - 1) nh + k
+ *     for the horizontal filter (h, k); Fp = SKR_CASER_FP(L, nv, nh), the nv 64 + nh L columns rounded up to a multiple of 64 |
+ *   fc1.bias [64]
+ * Per instance (u, window s_1..s_L, positives t_1..t_T, negatives t_T+1..t_2T), with E_l = E[s_l] and p = U[u]:
+ *   out_v[c] = bv[c] + sum_l wv[c][l] E_l,   a[h,k,t] = bh[h,k] + sum_{r<h} <Wh[h,k,r], E_(t+r)>,   out_h[h,k] = max_t relu(a[h,k,t]),
+ *   out = dropout([out_v, out_h]),   z = relu(W1 out + b1),   x = [z, p],   y_j = <W2[t_j], x> + b2[t_j].
+ * max takes the lowest position among exact ties and relu'(0) = 0, as torch's max_pool1d and relu do.
+ * Limits (refused with a message): width <= 64, 1 <= seq_L <= SKR_CASER_MAX_L, 1 <= seq_T <= SKR_CASER_MAX_T,
+ * 1 <= nv <= SKR_CASER_MAX_NV, 1 <= nh <= SKR_CASER_MAX_NH, n <= SKR_CASER_MAX_BATCH.
+ * ========================================================================================== */
+#define SKR_CASER_MAX_L 8
+#define SKR_CASER_MAX_T 16
+#define SKR_CASER_MAX_NV 8
+#define SKR_CASER_MAX_NH 32
+#define SKR_CASER_MAX_BATCH 2048
+#define SKR_CASER_ROWS(L, nh) ((nh) * (L) * ((L) + 1) / 2)
+#define SKR_CASER_FP(L, nv, nh) (64 * (((nv) * 64 + (nh) * (L) + 63) / 64))
+#define SKR_CASER_SHARED_FLOATS(L, nv, nh) \
+    (128 + 64 * SKR_CASER_ROWS(L, nh) + 64 * (((L) * (nh) + 63) / 64) + 64 * SKR_CASER_FP(L, nv, nh) + 64)
+/* bytes of d_work for a batch of n instances (and for skr_caser_queries, which walks its users through it in chunks); 0 for
+ * arguments out of range */
+size_t skr_caser_workspace(int n, int seq_L, int nv, int nh);
+/* One training batch, forward and backward of mean over n seq_T of (bce(y_pos, 1) + bce(y_neg, 0)): d_u int32[n], d_seq
+ * int32[n][seq_L], d_pos / d_neg int32[n][seq_T].  The batch's two cross-entropy SUMS are WRITTEN to words 0 and 1 of d_loss
+ * (float [2 * loss_slots], loss_slots 1 or SKR_LOSS_SLOTS; the other slots' words are written as zeros).  The gradients are
+ * ADDED to d_gU, d_gE, d_gW2, d_gb2 and d_gshared, in the tables' layouts (the caller's optimiser zeroes them).  Dropout at
+ * rate `dropout` (0: keeps everything and draws nothing): d_keep holds one byte per [n, nv width + nh seq_L] element in the
+ * reference's column order (c width + col, then (h - 1) nh + k); NULL: the step draws on the device, keyed by (seed, step,
+ * user, column) -- a user's draws do not depend on the rest of the batch; equal to torch's draws in law only.  d_keep_out
+ * (optional, same shape) records the flags that were used.  An instance with an id outside [0, n_users) / [0, n_rows) is
+ * skipped: it adds nothing to the sums or the gradients (the mean still divides by n seq_T) and its ids are not
+ * dereferenced.  No floating-point atomic: row gradients are added once per distinct id in rank order, the shared
+ * parameters' in a fixed order, so two calls on the same inputs give the same bits.  d_work: skr_caser_workspace(n, ...)
+ * bytes, 16-byte aligned, no initial contents, not to be shared by calls that may run at the same time. */
+int skr_caser_step(const float* d_U, const float* d_E, const float* d_W2, const float* d_b2, const float* d_shared, const int32_t* d_u,
+                   const int32_t* d_seq, const int32_t* d_pos, const int32_t* d_neg, int n, int n_users, int n_rows, int pad_idx, int dim,
+                   int width, int seq_L, int seq_T, int nv, int nh, float dropout, const uint8_t* d_keep, uint8_t* d_keep_out,
+                   uint64_t seed, uint64_t step, float* d_gU, float* d_gE, float* d_gW2, float* d_gb2, float* d_gshared, void* d_work,
+                   size_t work_bytes, float* d_loss, int loss_slots, void* stream);
+/* The same step with an event after each of its SKR_CASER_LAUNCHES launch groups (conv; fc1; scores and loss terms; d_out = dz W1;
+ * dW1 | db1; conv backward; filter gradients; rank; ordered adds; loss sums): h_ms[k] (host) = milliseconds of group k;
+ * synchronises the stream (timing tools). */
+#define SKR_CASER_LAUNCHES 10
+int skr_caser_step_timed(const float* d_U, const float* d_E, const float* d_W2, const float* d_b2, const float* d_shared,
+                         const int32_t* d_u, const int32_t* d_seq, const int32_t* d_pos, const int32_t* d_neg, int n, int n_users,
+                         int n_rows, int pad_idx, int dim, int width, int seq_L, int seq_T, int nv, int nh, float dropout,
+                         const uint8_t* d_keep, uint8_t* d_keep_out, uint64_t seed, uint64_t step, float* d_gU, float* d_gE, float* d_gW2,
+                         float* d_gb2, float* d_gshared, void* d_work, size_t work_bytes, float* d_loss, int loss_slots, void* stream,
+                         float* h_ms);
+/* Query rows: d_Q[u][0..127] = x = [z, p] of user u = d_users[i] (d_users NULL: u = i) in eval mode (no dropout) from the
+ * window d_windows[i][0..seq_L), so that the model's score of item t is <d_Q[u], W2[t]> + b2[t] (skr_score_matrix at
+ * dim = 128).  A window with an entry outside [0, n_rows) -- by convention a negative first entry marks a user without training
+ * history -- gives a row of NaN (callers raise before they ask: the reference raises KeyError, Caser.py:223).  Users out of
+ * range are skipped.  d_work: at least 64 (4 SKR_CASER_FP + 4) + 16 bytes; skr_caser_workspace of any batch is enough. */
+int skr_caser_queries(const float* d_U, const float* d_E, const float* d_shared, const int32_t* d_users, int n, const int32_t* d_windows,
+                      int n_users, int n_rows, int pad_idx, int dim, int width, int seq_L, int nv, int nh, void* d_work,
+                      size_t work_bytes, float* d_Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

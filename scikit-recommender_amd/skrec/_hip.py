@@ -193,6 +193,10 @@ SIGNATURES = {
     "skr_slmrec_workspace": (sz, [i32, i32, i32]),
     "skr_slmrec_step": (i32, [vp, vp]),
     "skr_slmrec_step_timed": (i32, [vp, vp, vp]),
+    "skr_caser_workspace": (sz, [i32, i32, i32, i32]),
+    "skr_caser_step": (i32, [vp] * 9 + [i32] * 10 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp]),
+    "skr_caser_step_timed": (i32, [vp] * 9 + [i32] * 10 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp]),
+    "skr_caser_queries": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
 }
 
 
@@ -312,11 +316,28 @@ SKR_LATTICE_CF_LIGHTGCN, SKR_LATTICE_CF_MF = 0, 1                               
 SKR_SLMREC_MAX_BATCH, SKR_SLMREC_MAX_LAYERS, SKR_SLMREC_MAX_FEAT, SKR_SLMREC_GROUPS = 2048, 4, 4096, 8   # skr_slmrec_step limits
 SKR_SLMREC_GATE_FLOATS, SKR_SLMREC_FUSION_FLOATS = 64 * 64 + 64, 64 * 192 + 64   # a chain layer's block; a fusion layer's W [64][192] | b
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
+SKR_CASER_MAX_L, SKR_CASER_MAX_T, SKR_CASER_MAX_NV, SKR_CASER_MAX_NH, SKR_CASER_MAX_BATCH = 8, 16, 8, 32, 2048   # skr_caser_step limits
+SKR_CASER_LAUNCHES = 10                  # skr_caser_step_timed: launch groups
 
 
 def hgn_gate_floats(L):
     """SKR_HGN_GATE_FLOATS(L): floats of HGN's shared gate parameters (and of one partial of their gradient)"""
     return 2 * 64 * 64 + 3 * 64 + 64 * int(L)
+
+
+def caser_rows(L, nh):
+    """SKR_CASER_ROWS(L, nh): 64-float rows of Caser's horizontal filters, ordered (h, k, r)"""
+    return int(nh) * int(L) * (int(L) + 1) // 2
+
+
+def caser_fp(L, nv, nh):
+    """SKR_CASER_FP(L, nv, nh): the row stride of Caser's fc1.weight, its nv 64 + nh L columns rounded up to 64"""
+    return 64 * ((int(nv) * 64 + int(nh) * int(L) + 63) // 64)
+
+
+def caser_shared_floats(L, nv, nh):
+    """SKR_CASER_SHARED_FLOATS(L, nv, nh): floats of Caser's shared parameters (include/skrec_hip.h names the parts)"""
+    return 128 + 64 * caser_rows(L, nh) + 64 * ((int(L) * int(nh) + 63) // 64) + 64 * caser_fp(L, nv, nh) + 64
 
 
 class HipError(RuntimeError):
