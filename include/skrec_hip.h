@@ -818,7 +818,8 @@ int skr_seq_scores(int mode, const float* d_user_table, const float* d_last_tabl
  * atomic scatter-adds; the padding row gets none.  The gate parameters' gradients are named by every instance and are
  * summed in a FIXED order (per wavefront, per workgroup, then the workgroups in order in a second launch) and ADDED to
  * d_ggates (layout of d_gates): two calls on the same inputs give the same bits for them.  An instance with an id
- * outside [0, n_users) / [0, n_rows) is skipped.  d_work: float[SKR_HGN_MAX_BLOCKS * SKR_HGN_GATE_FLOATS(seq_L)] scratch,
+ * outside [0, n_users) / [0, n_rows) is skipped: it adds nothing to the loss or to any gradient (with pad_idx = -1 a -1 in
+ * a window is such an id, not padding).  The loss is a sum, so n == 0 returns at once and touches nothing.  d_work: float[SKR_HGN_MAX_BLOCKS * SKR_HGN_GATE_FLOATS(seq_L)] scratch,
  * no initial contents, not to be shared by calls that may run at the same time. */
 int skr_hgn_step(const float* d_U, const float* d_E, const float* d_W2, const float* d_b2, const float* d_gates,
                  const int32_t* d_u, const int32_t* d_seq, const int32_t* d_pos, const int32_t* d_neg, int n, int n_users,
@@ -839,7 +840,9 @@ int skr_hgn_queries(const float* d_U, const float* d_E, const float* d_gates, co
  * Tables: d_WqT [n_items, 128], the encoder weight transposed: an item's row is 64 mu columns then 64 logvar columns,
  * each half zero beyond dim; d_bq [128] likewise; d_Wp [n_items, 64] (16-byte aligned) and d_bp [n_items], the decoder.
  * A user's input is its row of the train CSR (d_rowptr int64 [n_users + 1], d_items int32, ASCENDING inside a row).
- * Per user u of the batch (n users, n <= SKR_MULTVAE_MAX_BATCH; a user outside [0, n_users) counts as an empty row):
+ * Per user u of the batch (n users, n <= SKR_MULTVAE_MAX_BATCH; a user outside [0, n_users) counts as an empty row, and
+ * an empty row is a row of the batch: n stays the divisor of both means, the row's h is zero, so it adds nothing to
+ * neg_ll and the KL of bq to kl, with that term's gradient going to d_gbq alone; the same user twice is two rows):
  *   h = x_u / ||x_u|| * keep / keep_prob,  e = h Wq^T + bq,  mu = e[:dim], logvar = e[64:64 + dim],
  *   z = mu + eps * exp(logvar / 2),  logits = z Wp^T + bp,
  *   neg_ll = -mean_u sum_{i in x_u} log_softmax(logits)_ui,  kl = mean_u sum 0.5 (-logvar + exp(logvar) + mu^2 - 1).
@@ -856,6 +859,7 @@ size_t skr_multvae_workspace(int n, int n_items);
  * the device, keyed by (seed, step, user, item) and (seed, step, user, column) -- a user's draws do not depend on the
  * rest of the batch; equal to the reference's torch draws in law only.  Nothing on the decoder side is a float atomic:
  * d_gWp, d_gbp, d_loss of two calls on the same inputs are bit-equal; d_gWqT rows are atomic scatter-adds.
+ * n == 0 WRITES d_loss = (0, 0) and touches no gradient and no workspace.
  * d_work: skr_multvae_workspace(n, n_items) bytes, 16-byte aligned, no initial contents, not to be shared by calls that
  * may run at the same time. */
 int skr_multvae_step(const float* d_WqT, const float* d_bq, const float* d_Wp, const float* d_bp, const int64_t* d_rowptr,
@@ -893,7 +897,17 @@ int skr_multvae_draws(const int64_t* d_rowptr, const int32_t* d_items, const int
  * the three pair arrays and d_puser may belong to a longer list (a block of batches prepared at once) and are indexed by
  * the values of d_uptr as they are; n_pairs = d_uptr[n] - d_uptr[0].  d_puser[p] is the batch position of pair p.
  * The item-major view: distinct item d_ditems[j] (j < n_distinct) owns d_ipair[d_iptr[j] .. d_iptr[j + 1]), pair numbers
- * RELATIVE to d_uptr[0]; every pair is listed once.  Entries out of range are skipped, never followed.
+ * RELATIVE to d_uptr[0]; every pair is listed once.  Entries out of range are skipped, never followed, and what is
+ * skipped contributes nothing to either loss word or to any gradient:
+ *   - a user outside [0, n_users), and a user whose d_uptr pair is broken (below d_uptr[0], descending, or past n_pairs),
+ *     owns no pairs: none of them is scored, counted in the BCE sum or followed from the item-major view; the user outside
+ *     the range has no U row either (no l2 term, no d_gU row).  The BCE is a sum, so no divisor changes.
+ *   - a pair whose d_pitem is outside [0, n_items) is skipped alone: nothing goes into its user's h, its dr is 0.
+ *   - the item-major view follows a d_ipair entry only if it is inside [0, n_pairs), its d_puser is inside [0, n), the pair
+ *     lies inside that user's d_uptr range (so its dr was written: d_work needs no initial contents whatever the pointers
+ *     say) and the pair's d_pitem is the item that lists it; a broken d_iptr pair is an empty list.  A distinct item none
+ *     of whose pairs is followed, or which is itself outside [0, n_items), is not named by the batch: no l2 term, no
+ *     gradient row.
  *   h_u = act(sum_{kept i} E_en[i] / keep_prob + U[u] + offset),   r = <h_u, E_de[i]> + bias[i] for every pair,
  *   loss = sum_pairs bce_with_logits(r, label) + reg * l2,
  *   l2 = 0.5 (|E_en[J]|^2 + |offset|^2 + |U[users]|^2 + |E_de[J]|^2 + |bias[J]|^2), J the distinct items.
@@ -907,6 +921,8 @@ size_t skr_cdae_workspace(int n, int64_t n_pairs);
  * gradient of the whole loss is WRITTEN into the rows the batch names -- d_gU[users], d_gE_en[J], d_gE_de[J], d_gbias[J]
  * and d_goffset [64] (layouts of the tables) -- and nothing else is touched: the caller's optimiser leaves the other
  * rows at zero.  No floating-point atomic: two calls on the same inputs give bit-equal results.
+ * n == 0 WRITES d_loss = (0, 0) and touches no gradient and no workspace: the offset's batch-independent terms, its
+ * 0.5 |offset|^2 in l2 and the reg * offset in d_goffset, are not produced for an empty batch.
  * d_work: skr_cdae_workspace(n, n_pairs) bytes, 16-byte aligned, no initial contents. */
 int skr_cdae_step(const float* d_E_en, const float* d_E_de, const float* d_bias, const float* d_offset, const float* d_U,
                   const int32_t* d_users, const int32_t* d_uptr, const int32_t* d_pitem, const uint8_t* d_plabel,

@@ -10,6 +10,9 @@
 //   item side   one wavefront per distinct item walks its pairs: dE_de[i] = sum dr h_u + reg E_de[i],
 //               db[i] = sum dr + reg b[i], dE_en[i] = sum_kept dpre_u / keep_prob + reg E_en[i]; 0.5 of the three squares
 //   finish      one workgroup: d offset = sum_u dpre_u + reg offset, and the two loss words
+// What is skipped contributes nothing: a user out of range or behind a broken pointer owns no pairs (user_pairs, read by
+// both sides, so the item side follows a pair only where the user side wrote its dr), a pair whose item is out of range
+// is skipped alone, and an item none of whose pairs is followed gets no row and no l2 term.
 // Rows are 64 floats (256 bytes).  A wavefront reads them as four rows side by side: 16 lanes x float4 per row, so one
 // load instruction has four rows in flight; the four partial sums are combined at the end, (g0 + g1) + (g2 + g3).
 // Columns beyond `dim` are held at zero: h is masked there (sigmoid(0) would put 0.5 into them).
@@ -93,6 +96,17 @@ inline Work work_layout(int n, int64_t n_pairs) {
     return w;
 }
 
+// The pairs [p0, p1) that batch position b owns, as the user side walks them and the item side follows them: empty for a
+// user outside [0, n_users) and for a broken pointer (below the batch's first pair, descending, or past n_pairs), so
+// that the item side never reads a dr the user side did not write.
+__device__ __forceinline__ void user_pairs(const int32_t* __restrict__ users, const int32_t* __restrict__ uptr, int b,
+                                           int64_t pair0, int64_t n_pairs, int n_users, int64_t& p0, int64_t& p1) {
+    p0 = uptr[b];
+    p1 = uptr[b + 1];
+    const int u = users[b];
+    if (u < 0 || u >= n_users || p0 < pair0 || p1 < p0 || p1 - pair0 > n_pairs) p0 = p1 = pair0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // user side
 // ------------------------------------------------------------------------------------------------
@@ -109,10 +123,10 @@ __global__ __launch_bounds__(UW * 64) void cdae_user_kernel(
     if (b >= n) return;
     const int g = lane >> 4, c4 = lane & 15;
     const int64_t pair0 = uptr[0];
-    int64_t p0 = uptr[b], p1 = uptr[b + 1];
-    if (p0 < pair0 || p1 < p0 || p1 - pair0 > n_pairs) p0 = p1 = pair0;     // a broken pointer: an empty row
+    int64_t p0, p1;
+    user_pairs(users, uptr, b, pair0, n_pairs, n_users, p0, p1);           // a skipped user, a broken pointer: an empty row
     const int u = users[b];
-    const bool valid = u >= 0 && u < n_users;
+    const bool valid = u >= 0 && u < n_users;                              // a skipped user: no U row, no l2, no gradient
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     // encoder: the kept rows of E_en
     float4 acc = zero;
@@ -168,9 +182,10 @@ __global__ __launch_bounds__(UW * 64) void cdae_user_kernel(
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(HW * 64) void cdae_item_kernel(
     const float* __restrict__ E_en, const float* __restrict__ E_de, const float* __restrict__ bias,
-    const int32_t* __restrict__ uptr, const uint8_t* __restrict__ pkeep, const int32_t* __restrict__ puser,
-    const int32_t* __restrict__ ditems, const int32_t* __restrict__ iptr, const int32_t* __restrict__ ipair, int n,
-    int64_t n_pairs, int n_distinct, int n_items, float inv_keep, float reg, const float* __restrict__ h_ws,
+    const int32_t* __restrict__ users, const int32_t* __restrict__ uptr, const int32_t* __restrict__ pitem,
+    const uint8_t* __restrict__ pkeep, const int32_t* __restrict__ puser, const int32_t* __restrict__ ditems,
+    const int32_t* __restrict__ iptr, const int32_t* __restrict__ ipair, int n, int64_t n_pairs, int n_distinct, int n_users,
+    int n_items, float inv_keep, float reg, const float* __restrict__ h_ws,
     const float* __restrict__ dpre_ws, const float* __restrict__ dr_ws, float* __restrict__ gE_en, float* __restrict__ gE_de,
     float* __restrict__ gbias, float* __restrict__ l2i_ws) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -184,22 +199,33 @@ __global__ __launch_bounds__(HW * 64) void cdae_item_kernel(
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 ad = zero, ae = zero;
     float ab = 0.0f;
+    bool named = false;
 #pragma unroll 2
     for (int64_t q = q0 + g; q < q1; q += 4) {
         const int64_t lp = ipair[q];
         if (lp < 0 || lp >= n_pairs) continue;
         const int b = puser[pair0 + lp];
         if (b < 0 || b >= n) continue;
+        // A pair is followed only where the user side wrote its dr: it is a pair of this item inside its owner's range.
+        // Everything is requested before the test (all of it lies inside the arrays): the test adds no round trip.
+        int64_t p0, p1;
+        user_pairs(users, uptr, b, pair0, n_pairs, n_users, p0, p1);
+        const bool mine = pitem[pair0 + lp] == it;
+        const bool kept = pkeep[pair0 + lp] != 0;
         const float dr = dr_ws[lp];
-        ad = fma4(dr, row4(h_ws, b, c4), ad);
+        const float4 hb = row4(h_ws, b, c4), db = row4(dpre_ws, b, c4);
+        if (!mine || pair0 + lp < p0 || pair0 + lp >= p1) continue;
+        named = true;
+        ad = fma4(dr, hb, ad);
         ab += dr;
-        if (pkeep[pair0 + lp] != 0) ae = add4(ae, row4(dpre_ws, b, c4));
+        if (kept) ae = add4(ae, db);
     }
     ad = groups4(ad);
     ae = groups4(ae);
     ab = groups(ab);
+    named = __builtin_amdgcn_ballot_w64(named) != 0;      // an item none of whose pairs is followed is not named by the batch
     float l2 = 0.0f;
-    if (it >= 0 && it < n_items) {
+    if (it >= 0 && it < n_items && named) {
         const float4 en = row4(E_en, it, c4), de = row4(E_de, it, c4);
         const float bi = bias[it];
         l2 = 0.5f * (sum16(dot4(en, en)) + sum16(dot4(de, de)) + bi * bi);
@@ -310,7 +336,10 @@ static int cdae_run_step(const float* d_E_en, const float* d_E_de, const float* 
     SKR_REQUIRE(dim >= 1 && dim <= D, "skr_cdae_step: 1 <= dim <= 64 (got %d); rows are 64 floats, zero-padded", dim);
     SKR_REQUIRE(act == SKR_CDAE_IDENTITY || act == SKR_CDAE_SIGMOID, "skr_cdae_step: act = %d is neither identity nor sigmoid", act);
     SKR_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "skr_cdae_step: keep_prob = %g is not in (0, 1]", keep_prob);
-    if (n == 0) return SKR_OK;
+    if (n == 0) {                                   // the empty batch: both loss words are written, nothing else is touched
+        SKR_HIP(hipMemsetAsync(d_loss, 0, 2 * sizeof(float), skr::as_stream(stream)));
+        return SKR_OK;
+    }
     const Work W = work_layout(n, n_pairs);
     SKR_REQUIRE(work_bytes >= static_cast<size_t>(W.total) * sizeof(float),
                 "skr_cdae_step: d_work holds %zu bytes, skr_cdae_workspace(%d, %lld) asks for %zu", work_bytes, n,
@@ -332,8 +361,9 @@ static int cdae_run_step(const float* d_E_en, const float* d_E_de, const float* 
 #undef SKR_CDAE_USER
     SKR_HIP(mk.mark());
     if (n_distinct > 0)
-        hipLaunchKernelGGL(cdae_item_kernel, dim3((n_distinct + HW - 1) / HW), dim3(HW * 64), 0, st, d_E_en, d_E_de, d_bias, d_uptr,
-                           d_pkeep, d_puser, d_ditems, d_iptr, d_ipair, n, n_pairs, n_distinct, n_items, inv_keep, reg, w + W.h,
+        hipLaunchKernelGGL(cdae_item_kernel, dim3((n_distinct + HW - 1) / HW), dim3(HW * 64), 0, st, d_E_en, d_E_de, d_bias, d_users,
+                           d_uptr, d_pitem, d_pkeep, d_puser, d_ditems, d_iptr, d_ipair, n, n_pairs, n_distinct, n_users, n_items,
+                           inv_keep, reg, w + W.h,
                            w + W.dpre, w + W.dr, d_gE_en, d_gE_de, d_gbias, w + W.l2i);
     SKR_HIP(mk.mark());
     hipLaunchKernelGGL(cdae_finish_kernel, dim3(1), dim3(1024), 0, st, d_offset, n, n_distinct, reg, w + W.dpre, w + W.bce,

@@ -568,7 +568,10 @@ static int run_step(const float* d_WqT, const float* d_bq, const float* d_Wp, co
     SKR_REQUIRE(dim >= 1 && dim <= D, "skr_multvae_step: 1 <= dim <= 64 (got %d); rows are 64 floats, zero-padded", dim);
     SKR_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "skr_multvae_step: keep_prob = %g is not in (0, 1]", keep_prob);
     SKR_REQUIRE((d_keep == nullptr) == (d_eps == nullptr), "skr_multvae_step: d_keep and d_eps come together or not at all");
-    if (n == 0) return SKR_OK;
+    if (n == 0) {                                   // the empty batch: both loss words are written, nothing else is touched
+        SKR_HIP(hipMemsetAsync(d_loss, 0, 2 * sizeof(float), skr::as_stream(stream)));
+        return SKR_OK;
+    }
     const int n_wg = n_workgroups(n_items), tiles = (n_items + TI - 1) / TI, n4 = static_cast<int>(round4(n));
     const Layout L = layout(n, n_wg);
     SKR_REQUIRE(work_bytes >= static_cast<size_t>(L.total) * sizeof(float),

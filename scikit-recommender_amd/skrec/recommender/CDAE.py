@@ -329,9 +329,15 @@ class CDAE(DeviceRecommender):
         (user after user, items ascending over pos + unique(neg); default: device draws).  Recorded negatives and flags
         replay a reference run.  -> device tensor (bce sum, l2)"""
         users = np.ascontiguousarray(users.cpu().numpy() if torch.is_tensor(users) else users, dtype=np.int32)
+        self._q_current = False
+        if users.size == 0:
+            # the empty batch: a zero loss pair and the zero gradient through Adam (nothing moves while the moments are
+            # zero); there is nothing to lay out, and skr_cdae_step would write the same pair
+            self.optimizer.step()
+            self.update_count += 1
+            return torch.zeros(2, dtype=torch.float32, device=self.device)
         B = self._prepare([users], negatives, keep)
         loss = torch.empty(2, dtype=torch.float32, device=self.device)
-        self._q_current = False
         _hip.check(self._launch(B, 0, _hip.ptr(loss)))
         self.optimizer.step()
         self.update_count += 1

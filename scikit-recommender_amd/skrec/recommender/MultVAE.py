@@ -178,6 +178,10 @@ class MultVAE(DeviceRecommender):
         n = int(users.shape[0])
         if n > _hip.SKR_MULTVAE_MAX_BATCH:
             raise ValueError(f"MultVAE: a batch holds at most {_hip.SKR_MULTVAE_MAX_BATCH} users (got {n})")
+        if n == 0:
+            # the empty batch is no step: a zero loss pair (what skr_multvae_step writes for n == 0), and neither
+            # optimiser runs -- opt_w's weight decay would move the weights on a zero gradient -- nor does the annealing
+            return torch.zeros(2, dtype=torch.float32, device=self.device)
         need = int(L.skr_multvae_workspace(n, self.num_items))
         if need > self._work.numel():
             self._work = torch.empty(need, dtype=torch.uint8, device=self.device)

@@ -29,19 +29,34 @@ def _act(x, act):
     return torch.sigmoid(x) if act == "sigmoid" else x
 
 
-def losses_f64(par, users, puser, pitem, plabel, keep, keep_prob, act):
+def losses_f64(par, users, puser, pitem, plabel, keep, keep_prob, act, pair_ok=None, user_ok=None, l2_items=None, detail=None):
     """(bce sum, l2) of a batch; ``par``: float64 tensors in the reference's shapes, PARAMS order; ``keep``: one flag per
-    pair.  l2 = 0.5 (|E_en[J]|^2 + |offset|^2 + |U[users]|^2 + |E_de[J]|^2 + |b[J]|^2), J the distinct items"""
+    pair.  l2 = 0.5 (|E_en[J]|^2 + |offset|^2 + |U[users]|^2 + |E_de[J]|^2 + |b[J]|^2), J the distinct items.
+    The skipped entries of skr_cdae_step's contract: ``pair_ok`` (bool per pair): a pair that is not ok goes into neither
+    the encoder's sum nor the BCE, whatever its item; ``user_ok`` (bool per batch position): a user that is not ok has no U
+    row, in h or in l2 (its pairs are masked by the caller); J is the distinct items of the ok pairs unless ``l2_items``
+    names them.  The BCE is a sum: no divisor.  ``detail`` (a dict) receives enc [n, d], h [n, d] and r [ok pairs], enc and
+    r keeping their gradients, and ``rows``, the ok pairs' numbers"""
     en, off, de, b, U = par
-    users = torch.as_tensor(np.asarray(users, np.int64))
-    pu, pi = torch.as_tensor(puser), torch.as_tensor(pitem)
-    kept = torch.as_tensor(np.asarray(keep) != 0)
-    enc = torch.zeros((len(users), en.shape[1]), dtype=torch.float64).index_add(0, pu[kept], en[pi[kept]] / keep_prob)
-    h = _act(enc + U[users] + off, act)
+    n = len(users)
+    ok = np.ones(len(puser), bool) if pair_ok is None else np.asarray(pair_ok, bool)
+    uok = np.ones(n, bool) if user_ok is None else np.asarray(user_ok, bool)
+    assert uok[np.asarray(puser)[ok]].all()
+    users = torch.as_tensor(np.where(uok, np.asarray(users, np.int64), 0))
+    pu, pi = torch.as_tensor(np.asarray(puser, np.int64)[ok]), torch.as_tensor(np.asarray(pitem, np.int64)[ok])
+    kept = torch.as_tensor(np.asarray(keep)[ok] != 0)
+    enc = torch.zeros((n, en.shape[1]), dtype=torch.float64).index_add(0, pu[kept], en[pi[kept]] / keep_prob)
+    urow = U[users] * torch.as_tensor(uok, dtype=torch.float64).unsqueeze(1)
+    h = _act(enc + urow + off, act)
     r = (h[pu] * de[pi]).sum(1) + b[pi, 0]
-    bce = torch.nn.functional.binary_cross_entropy_with_logits(r, torch.as_tensor(plabel, dtype=torch.float64), reduction="sum")
-    J = torch.unique(pi)
-    l2 = 0.5 * sum((w ** 2).sum() for w in (en[J], off, U[users], de[J], b[J]))
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(r, torch.as_tensor(np.asarray(plabel, np.float64)[ok]), reduction="sum")
+    J = torch.unique(pi) if l2_items is None else torch.as_tensor(np.asarray(l2_items, np.int64))
+    l2 = 0.5 * sum((w ** 2).sum() for w in (en[J], off, urow, de[J], b[J]))
+    if detail is not None:
+        if enc.requires_grad:
+            enc.retain_grad()
+            r.retain_grad()
+        detail.update(enc=enc, h=h, r=r, rows=np.flatnonzero(ok))
     return bce, l2
 
 

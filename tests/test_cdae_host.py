@@ -73,7 +73,9 @@ def test_abi_argument_checks_without_gpu():
     assert step(n_pairs=-1) == -1
     assert step(work_bytes=64) == -1 and b"skr_cdae_workspace" in L.skr_last_error()
     assert step(n_items=0) == -1
-    assert step(n=0) == 0                     # an empty batch: nothing to launch
+    # (an empty batch WRITES its zero loss pair, so it needs real device memory: tests/test_gpu_cdae.py,
+    # test_an_empty_batch_writes_a_zero_loss_and_nothing_else; its arguments are checked like any batch's)
+    assert step(n=0, dim=65) == -1 and step(n=0, act=2) == -1
     assert L.skr_cdae_queries(None, p, p, p, p, None, 4, 10, 100, 64, 1, p, None) == -1
     assert L.skr_cdae_queries(p, p, p, p, p, None, 11, 10, 100, 64, 1, p, None) == -1 and b"user list" in L.skr_last_error()
     assert L.skr_cdae_queries(p, p, p, p, p, None, 4, 10, 100, 64, 3, p, None) == -1

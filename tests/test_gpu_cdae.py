@@ -41,15 +41,15 @@ def _model(data_dir, **kw):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. the step kernel against float64 autograd
 # ---------------------------------------------------------------------------------------------------------------------
-def _case(rng, B, I, d, act, keep_prob=0.5, num_neg=2):
+def _case(rng, B, I, d, act, keep_prob=0.5, num_neg=2, lens=(2, 12), long_rows=True):
     """parameters of width d, a CSR of B + 2 users (the batch is B of them, not in id order), raw negatives and keep
     flags.  Batch position 0: a user with a single training item; 1 (B > 1): every entry dropped; 2: more than 64 pairs;
-    3: more than 256 pairs.  Item 7 is a positive of every user; the bias of the last item block is exercised by the
-    catalogue's last item, a positive of position 0's neighbour."""
+    3: more than 256 pairs (``long_rows``).  Item 7 is a positive of every user; the bias of the last item block is
+    exercised by the catalogue's last item, a positive of position 0's neighbour.  ``lens``: the rows' lengths, [lo, hi)."""
     nU = B + 2
-    lens = rng.integers(2, 12, nU)
+    lens = rng.integers(lens[0], lens[1], nU)
     lens[0] = 1
-    if B > 3:
+    if B > 3 and long_rows:
         lens[2], lens[3] = 30, min(140, I // 3)
     rows = []
     for n in lens:
@@ -92,31 +92,44 @@ def _device_tables(c):
             (pad(p["en_embeddings"]), pad(p["de_embeddings"]), bias, off, pad(p["user_embeddings"]))]
 
 
-def _step(c, tabs, reg=1e-3):
-    """one skr_cdae_step on the host layout, gradients zeroed before -> (gE_en, gE_de, gbias, goffset, gU on the host, loss)"""
+LAYOUT_KEYS = ("uptr", "pitem", "plabel", "puser", "ditems", "iptr", "ipair")
+
+
+def _launch(c, tabs, lay, users, keep, reg=1e-3, n=None, P=None, J=None, u0=0, j0=0):
+    """one skr_cdae_step on the layout ``lay`` as it stands (a test may have broken single entries of it), the workspace
+    filled with 0xFF bytes, gradients zeroed before -> (gE_en, gE_de, gbias, goffset, gU on the host, loss).  ``u0`` / ``j0``:
+    the batch starts at users[u0], uptr[u0], ditems[j0], iptr[j0] of a longer block and holds n users, P pairs, J items"""
     import torch
     from skrec import _hip
-    from skrec.recommender.CDAE import batch_layout
     L = _hip.lib()
-    lay = batch_layout(c["rowptr"], c["items"], c["users"], c["negs"])
-    assert np.array_equal(lay["pitem"], c["pi"]) and np.array_equal(lay["puser"], c["pu"])
-    dev = {k: torch.from_numpy(np.ascontiguousarray(lay[k])).cuda() for k in ("uptr", "pitem", "plabel", "puser", "ditems", "iptr", "ipair")}
-    du, dk = torch.from_numpy(c["users"]).cuda(), torch.from_numpy(c["keep"]).cuda()
+    dev = {k: torch.from_numpy(np.ascontiguousarray(lay[k])).cuda() for k in LAYOUT_KEYS}
+    assert all(dev[k].dtype == torch.int32 for k in ("uptr", "pitem", "puser", "ditems", "iptr", "ipair"))
+    du = torch.from_numpy(np.ascontiguousarray(users, dtype=np.int32)).cuda()
+    dk = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).cuda()
     grads = [torch.zeros_like(t) for t in tabs]
-    P, J = len(lay["pitem"]), len(lay["ditems"])
-    nb = int(L.skr_cdae_workspace(c["B"], P))
+    n = len(users) if n is None else n
+    P, J = len(lay["pitem"]) if P is None else P, len(lay["ditems"]) if J is None else J
+    nb = int(L.skr_cdae_workspace(n, P))
     assert nb > 0
     work = torch.full((nb + 64,), 255, dtype=torch.uint8, device="cuda")
     loss = torch.full((2,), 7.0, device="cuda")
     act = _hip.SKR_CDAE_SIGMOID if c["act"] == "sigmoid" else _hip.SKR_CDAE_IDENTITY
-    _hip.check(L.skr_cdae_step(*[_hip.ptr(t) for t in tabs], _hip.ptr(du), _hip.ptr(dev["uptr"]), _hip.ptr(dev["pitem"]),
-                               _hip.ptr(dev["plabel"]), _hip.ptr(dk), _hip.ptr(dev["puser"]), _hip.ptr(dev["ditems"]),
-                               _hip.ptr(dev["iptr"]), _hip.ptr(dev["ipair"]), c["B"], P, J, c["nU"], c["I"], c["d"], act,
-                               c["keep_prob"], reg, *[_hip.ptr(g) for g in grads], _hip.ptr(work), nb, _hip.ptr(loss),
-                               _hip.stream()))
+    _hip.check(L.skr_cdae_step(*[_hip.ptr(t) for t in tabs], du.data_ptr() + 4 * u0, dev["uptr"].data_ptr() + 4 * u0,
+                               _hip.ptr(dev["pitem"]), _hip.ptr(dev["plabel"]), _hip.ptr(dk), _hip.ptr(dev["puser"]),
+                               dev["ditems"].data_ptr() + 4 * j0, dev["iptr"].data_ptr() + 4 * j0, _hip.ptr(dev["ipair"]), n, P, J,
+                               c["nU"], c["I"], c["d"], act, c["keep_prob"], reg, *[_hip.ptr(g) for g in grads], _hip.ptr(work),
+                               nb, _hip.ptr(loss), _hip.stream()))
     torch.cuda.synchronize()
     assert (work[nb:] == 255).all()                              # nothing past the workspace
     return [g.cpu().numpy() for g in grads], loss.cpu().numpy()
+
+
+def _step(c, tabs, reg=1e-3):
+    """one skr_cdae_step on the host layout, gradients zeroed before -> (gE_en, gE_de, gbias, goffset, gU on the host, loss)"""
+    from skrec.recommender.CDAE import batch_layout
+    lay = batch_layout(c["rowptr"], c["items"], c["users"], c["negs"])
+    assert np.array_equal(lay["pitem"], c["pi"]) and np.array_equal(lay["puser"], c["pu"])
+    return _launch(c, tabs, lay, c["users"], c["keep"], reg)
 
 
 @pytest.mark.parametrize("B,I,d,act", [(1, 70, 20, "sigmoid"), (9, 459, 64, "sigmoid"), (9, 459, 20, "identity"),
@@ -499,3 +512,385 @@ def test_run_skrec_cli(tiny_dir, tmp_path):
                         "--metric", "['Recall','NDCG']", "--seed", "7"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "epoch 1:" in r.stdout and "best:" in r.stdout and "Recall@5" in r.stdout
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 10. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+REG = 1e-3
+NAMES = ("en_embeddings", "en_offset", "de_embeddings", "de_bias", "user_embeddings")
+
+
+def _layout(c):
+    from skrec.recommender.CDAE import batch_layout
+    lay = batch_layout(c["rowptr"], c["items"], c["users"], c["negs"])
+    assert np.array_equal(lay["pitem"], c["pi"]) and np.array_equal(lay["puser"], c["pu"])
+    return {k: lay[k].copy() for k in LAYOUT_KEYS}
+
+
+def _layout_of_pairs(pu, pi, n):
+    """the layout of a pair list given user-major (items ascending inside a user); the labels are the caller's"""
+    pu, pi = np.asarray(pu, np.int64), np.asarray(pi, np.int64)
+    uptr = np.concatenate([[0], np.cumsum(np.bincount(pu, minlength=n))]).astype(np.int32)
+    ditems, counts = np.unique(pi, return_counts=True)
+    return dict(uptr=uptr, pitem=pi.astype(np.int32), puser=pu.astype(np.int32), ditems=ditems.astype(np.int32),
+                iptr=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), ipair=np.argsort(pi, kind="stable").astype(np.int32))
+
+
+def _edge_compare(c, what, got, pair_ok=None, user_ok=None, l2_items=None, adjust=None, users=None, pairs=None, keep=None):
+    """The device's (gradients, loss) against float64 autograd of the twin on the pairs ``pair_ok`` and the users ``user_ok``
+    (all when None), with the suite's bounds.  ``adjust(want, detail)`` changes the expected gradients where the contract
+    has the item side leave a pair out.  Then: the rows no valid pair or user names, and the padded columns, are exactly zero.
+    Prints one ``edge-error`` line per tensor (collected into profiles/scaffold_edges_errors.txt)"""
+    import torch
+    grads, loss = got
+    d, I, nU = c["d"], c["I"], c["nU"]
+    users = c["users"] if users is None else users
+    pu, pi, pl = (c["pu"], c["pi"], c["pl"]) if pairs is None else pairs
+    keep = c["keep"] if keep is None else keep
+    ok = np.ones(len(pu), bool) if pair_ok is None else pair_ok
+    uok = np.ones(len(users), bool) if user_ok is None else user_ok
+    t64 = [torch.tensor(c["par"][k], dtype=torch.float64, requires_grad=True) for k in T.PARAMS]
+    detail = {}
+    bce, l2 = T.losses_f64(t64, users, pu, pi, pl, keep, c["keep_prob"], c["act"], pair_ok=ok, user_ok=uok, l2_items=l2_items,
+                           detail=detail)
+    (bce + REG * l2).backward()
+    want = [np.zeros(t.shape) if t.grad is None else t.grad.numpy().copy() for t in t64]
+    if adjust is not None:
+        adjust(want, detail)
+    assert np.isfinite(bce.item()) and np.isfinite(l2.item()) and all(np.isfinite(w).all() for w in want)
+    print(what, "bce", loss[0], bce.item(), "l2", loss[1], l2.item())
+    assert np.isfinite(loss).all() and all(np.isfinite(g).all() for g in grads), what
+    np.testing.assert_allclose(loss[0], bce.item(), rtol=1e-5, err_msg=what)
+    np.testing.assert_allclose(loss[1], l2.item(), rtol=1e-5, err_msg=what)
+    gen, gde, gb, goff, gU = grads
+    checks = [(NAMES[0], gen[:, :d], want[0]), (NAMES[1], goff[:d], want[1]), (NAMES[2], gde[:, :d], want[2]),
+              (NAMES[3], gb[:I], want[3][:, 0]), (NAMES[4], gU[:, :d], want[4])]
+    for name, g, w in checks:                       # every tensor is measured before the assertion
+        scale = np.abs(w).max()
+        print(f"edge-error CDAE | {what} | {name} | {np.abs(g - w).max():.3e} | {scale:.3e}")
+    for name, g, w in checks:
+        np.testing.assert_allclose(g, w, rtol=1e-4, atol=2e-5 * np.abs(w).max(), err_msg=f"{what}: {name}")
+    # the rows no valid pair (user) names, the padded columns and the padded bias entries are exactly zero
+    named = np.zeros(I, bool)
+    named[np.unique(np.asarray(pi)[ok]) if l2_items is None else l2_items] = True
+    named_u = np.zeros(nU, bool)
+    named_u[np.asarray(users)[uok]] = True
+    assert not gen[~named].any() and not gde[~named].any() and not gb[:I][~named].any(), what
+    assert not gU[~named_u].any(), what
+    assert not gen[:, d:].any() and not gde[:, d:].any() and not gU[:, d:].any() and not goff[d:].any() and not gb[I:].any(), what
+    return named, named_u, detail
+
+
+@pytest.mark.parametrize("B", [2, 4, 5, 15, 16, 17, 63, 65])
+def test_batch_sizes_around_the_workgroups(B):
+    """users below, at and above the item side's four wavefronts and the finish kernel's 16 strided parts and 64 columns"""
+    d, act = (64, "sigmoid") if B % 2 else (24, "identity")
+    c = _case(np.random.default_rng(100 + B), B, 203, d, act)
+    _edge_compare(c, f"B = {B}", _step(c, _device_tables(c), REG))
+
+
+def test_full_batch_and_the_batch_over_the_limit():
+    """B = SKR_CDAE_MAX_BATCH with rows of 2 to 4 items and one negative per positive on 1100 items: more than 1024 distinct
+    items, so the finish kernel's loops over n and over n_distinct both take a second trip; twice: the same bits.  Then
+    1025 users: refused by name, and the workspace size is 0"""
+    from skrec import _hip
+    B = _hip.SKR_CDAE_MAX_BATCH
+    assert B == 1024
+    c = _case(np.random.default_rng(1024), B, 1100, 64, "sigmoid", num_neg=1, lens=(2, 5), long_rows=False)
+    lay = _layout(c)
+    assert len(lay["ditems"]) > 1024 and len(c["users"]) == 1024 and np.bincount(c["pu"]).max() <= 8
+    tabs = _device_tables(c)
+    got = _step(c, tabs, REG)
+    _edge_compare(c, "B = 1024", got)
+    again = _step(c, tabs, REG)
+    for a, b in zip(got[0] + [got[1]], again[0] + [again[1]]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert _hip.lib().skr_cdae_workspace(B + 1, len(c["pi"])) == 0
+    over = np.concatenate([c["users"], [0]]).astype(np.int32)
+    lay["uptr"] = np.concatenate([lay["uptr"], lay["uptr"][-1:]])
+    import torch
+    args = [torch.zeros(64, device="cuda") for _ in range(3)]
+    L = _hip.lib()
+    dev = {k: torch.from_numpy(lay[k]).cuda() for k in LAYOUT_KEYS}
+    du, dk = torch.from_numpy(over).cuda(), torch.from_numpy(c["keep"]).cuda()
+    grads = [torch.zeros_like(t) for t in tabs]
+    rc = L.skr_cdae_step(*[_hip.ptr(t) for t in tabs], _hip.ptr(du), *[_hip.ptr(dev[k]) for k in ("uptr", "pitem", "plabel")],
+                         _hip.ptr(dk), *[_hip.ptr(dev[k]) for k in ("puser", "ditems", "iptr", "ipair")], B + 1, len(c["pi"]),
+                         len(lay["ditems"]), c["nU"], c["I"], 64, _hip.SKR_CDAE_SIGMOID, 0.5, REG, *[_hip.ptr(g) for g in grads],
+                         _hip.ptr(args[0]), 256, _hip.ptr(args[1]), _hip.stream())
+    with pytest.raises(ValueError, match="at most 1024"):
+        _hip.check(rc)
+    torch.cuda.synchronize()
+    assert not any(g.any() for g in grads)
+
+
+def test_a_step_inside_a_block():
+    """three batches laid out as one block (CDAE._prepare's form: uptr and iptr run on, ipair is relative to the batch's
+    first pair); the kernel entry takes the middle one: uptr[0] != 0, iptr[0] != 0, users / uptr / ditems / iptr offset"""
+    from skrec.recommender.CDAE import batch_layout
+    c = _case(np.random.default_rng(77), 27, 203, 40, "sigmoid")
+    parts = [batch_layout(c["rowptr"], c["items"], c["users"][s:s + 9], c["negs"][s:s + 9]) for s in (0, 9, 18)]
+    p0 = np.concatenate([[0], np.cumsum([len(p["pitem"]) for p in parts])])
+    blk = {k: np.concatenate([p[k] for p in parts]) for k in ("pitem", "plabel", "puser", "ditems", "ipair")}
+    blk["uptr"] = np.concatenate([parts[0]["uptr"]] + [p["uptr"][1:] + o for p, o in zip(parts[1:], p0[1:])]).astype(np.int32)
+    blk["iptr"] = np.concatenate([parts[0]["iptr"]] + [p["iptr"][1:] + o for p, o in zip(parts[1:], p0[1:])]).astype(np.int32)
+    j0 = len(parts[0]["ditems"])
+    assert blk["uptr"][9] == p0[1] > 0 and blk["iptr"][j0] == p0[1]
+    keep = c["keep"]                                        # flags in pair order: the block's pair order is the case's
+    assert np.array_equal(blk["pitem"], c["pi"])
+    mid = parts[1]
+    got = _launch(c, _device_tables(c), blk, c["users"], keep, REG, n=9, P=len(mid["pitem"]), J=len(mid["ditems"]), u0=9, j0=j0)
+    sl = slice(p0[1], p0[2])
+    named, named_u, _ = _edge_compare(c, "the middle step of a block", got, users=c["users"][9:18],
+                                      pairs=(mid["puser"], mid["pitem"], mid["plabel"]), keep=keep[sl])
+    others = np.zeros(c["I"], bool)
+    others[np.concatenate([parts[0]["ditems"], parts[2]["ditems"]])] = True
+    assert (others & ~named).sum() > 5 and not named_u[c["users"][:9]].any() and not named_u[c["users"][18:]].any()
+
+
+def _held_once_by(c, b):
+    """an item that batch position b alone holds, with the number of its pair"""
+    held = np.bincount(c["pi"], minlength=c["I"])
+    mine = np.flatnonzero((c["pu"] == b) & (held[c["pi"]] == 1))
+    assert len(mine) > 0
+    return int(c["pi"][mine[0]]), int(mine[0])
+
+
+@pytest.mark.parametrize("where", [0, 5, 16])
+@pytest.mark.parametrize("bad", ["below", "n_users"])
+def test_a_user_out_of_range_is_skipped(bad, where):
+    """its pairs are not scored, not counted in the BCE sum and not followed by the item side; no U row; the items it
+    alone holds are not named.  Positions: the first, one inside, the last"""
+    c = _case(np.random.default_rng({0: 201, 5: 200, 16: 200}[where]), 17, 203, 64, "sigmoid", long_rows=False)
+    item, _ = _held_once_by(c, where)                      # (the seeds: cases in which that position holds such an item)
+    users = c["users"].copy()
+    lost = int(users[where])
+    users[where] = -3 if bad == "below" else c["nU"]
+    ok = c["pu"] != where
+    uok = np.arange(17) != where
+    assert item not in c["pi"][ok] and lost not in users
+    named, named_u, _ = _edge_compare(c, f"user {bad} at {where}", _launch(c, _device_tables(c), _layout(c), users, c["keep"], REG),
+                                      pair_ok=ok, user_ok=uok, users=users)
+    assert not named[item] and not named_u[lost]
+
+
+@pytest.mark.parametrize("held", ["once", "by others"])
+@pytest.mark.parametrize("bad", ["below", "n_items"])
+def test_a_pair_item_out_of_range_is_skipped_alone(bad, held):
+    """a KEPT pair's d_pitem: nothing goes into the user's h, dr = 0, and the item side does not follow it (a kept pair would
+    otherwise put the user's dpre into the gradient of the encoder row that lists it)"""
+    c = _case(np.random.default_rng(300), 9, 203, 64, "sigmoid")
+    cnt = np.bincount(c["pi"], minlength=c["I"])
+    cand = np.flatnonzero((c["keep"] != 0) & ((cnt[c["pi"]] == 1) if held == "once" else (cnt[c["pi"]] > 2)) & (c["pu"] > 1))
+    p = int(cand[0])
+    item = int(c["pi"][p])
+    lay = _layout(c)
+    lay["pitem"][p] = -1 if bad == "below" else c["I"]
+    ok = np.arange(len(c["pi"])) != p
+    assert c["keep"][p] and (item in c["pi"][ok]) == (held == "by others")
+    named, _, _ = _edge_compare(c, f"pair item {bad}, held {held}", _launch(c, _device_tables(c), lay, c["users"], c["keep"], REG),
+                                pair_ok=ok)
+    assert named[item] == (held == "by others")
+
+
+def _item_side_leaves_out(c, pairs_out, rows_out=()):
+    """adjust() of _edge_compare: the item side does not follow the pairs ``pairs_out`` (numbers in the full pair list), the
+    user side does: their dr h, dr and kept dpre / keep_prob are missing from their items' rows; ``rows_out``: items that
+    get no row at all"""
+    def adjust(want, detail):
+        row = {int(p): k for k, p in enumerate(detail["rows"])}
+        dr, denc, h = detail["r"].grad.numpy(), detail["enc"].grad.numpy(), detail["h"].detach().numpy()
+        for p in pairs_out:
+            k, it, b = row[int(p)], int(c["pi"][p]), int(c["pu"][p])
+            want[2][it] -= dr[k] * h[b]
+            want[3][it, 0] -= dr[k]
+            if c["keep"][p]:
+                want[0][it] -= denc[b] / c["keep_prob"]
+        for it in rows_out:
+            want[0][it], want[2][it], want[3][it] = 0.0, 0.0, 0.0
+    return adjust
+
+
+@pytest.mark.parametrize("bad", ["below", "n_items"])
+def test_a_distinct_item_out_of_range_writes_no_row(bad):
+    """a d_ditems entry: its pairs stay in the user side's sums; the item gets no gradient row and no l2 term"""
+    c = _case(np.random.default_rng(400), 9, 203, 64, "sigmoid")
+    lay = _layout(c)
+    j = 3
+    item = int(lay["ditems"][j])
+    lay["ditems"][j] = -1 if bad == "below" else c["I"]
+    J = np.delete(np.unique(c["pi"]), j)
+    assert item not in J
+    named, _, _ = _edge_compare(c, f"distinct item {bad}", _launch(c, _device_tables(c), lay, c["users"], c["keep"], REG),
+                                l2_items=J, adjust=_item_side_leaves_out(c, (), (item,)))
+    assert not named[item]
+
+
+@pytest.mark.parametrize("which,value", [("ipair", "below"), ("ipair", "n_pairs"), ("puser", "below"), ("puser", "n")])
+def test_item_side_entries_out_of_range_are_not_followed(which, value):
+    """one d_ipair entry / the d_puser entry of one pair: the item side leaves that pair out of its item's three sums (the
+    user side needs neither array); the item, held by other pairs too, keeps its row"""
+    c = _case(np.random.default_rng(500), 9, 203, 64, "sigmoid")
+    lay = _layout(c)
+    cnt = np.bincount(c["pi"], minlength=c["I"])
+    q = int(np.flatnonzero((cnt[c["pi"][lay["ipair"]]] > 2) & (c["keep"][lay["ipair"]] != 0))[1])     # a slot of the item-major list
+    p = int(lay["ipair"][q])
+    if which == "ipair":
+        lay["ipair"][q] = -1 if value == "below" else len(c["pi"])
+    else:
+        lay["puser"][p] = -1 if value == "below" else 9
+    named, _, _ = _edge_compare(c, f"{which} {value}", _launch(c, _device_tables(c), lay, c["users"], c["keep"], REG),
+                                adjust=_item_side_leaves_out(c, (p,)))
+    assert named[c["pi"][p]]
+
+
+@pytest.mark.parametrize("how", ["descending", "past n_pairs"])
+def test_a_broken_user_pointer_is_an_empty_row(how):
+    """d_uptr[n] below d_uptr[n - 1], or beyond the pair list: the last user's row is empty -- none of its pairs is scored,
+    and the item side, which still finds them through d_ipair, does not read the dr nobody wrote (the workspace is 0xFF
+    bytes: NaN).  The user keeps its U row and its l2 term"""
+    c = _case(np.random.default_rng(600), 9, 203, 64, "sigmoid")
+    item, _ = _held_once_by(c, 8)
+    lay = _layout(c)
+    lay["uptr"][9] = lay["uptr"][8] - 1 if how == "descending" else lay["uptr"][9] + 5
+    ok = c["pu"] != 8
+    assert (~ok).sum() > 1 and item not in c["pi"][ok]
+    named, named_u, _ = _edge_compare(c, f"uptr {how}", _launch(c, _device_tables(c), lay, c["users"], c["keep"], REG), pair_ok=ok)
+    assert not named[item] and named_u[c["users"][8]]
+
+
+@pytest.mark.parametrize("how", ["descending", "past n_pairs"])
+def test_a_broken_item_pointer_is_an_empty_list(how):
+    """d_iptr[J] below d_iptr[J - 1], or beyond the pair list: the last distinct item's pairs are not followed, so it is not
+    named (no row, no l2 term); the user side still scores them"""
+    c = _case(np.random.default_rng(700), 9, 203, 64, "sigmoid")
+    lay = _layout(c)
+    J = len(lay["ditems"])
+    item = int(lay["ditems"][J - 1])
+    lay["iptr"][J] = lay["iptr"][J - 1] - 1 if how == "descending" else lay["iptr"][J] + 3
+    named, _, _ = _edge_compare(c, f"iptr {how}", _launch(c, _device_tables(c), lay, c["users"], c["keep"], REG),
+                                l2_items=lay["ditems"][:J - 1], adjust=_item_side_leaves_out(c, (), (item,)))
+    assert not named[item]
+
+
+@pytest.mark.parametrize("n", [37, 300])
+def test_one_item_in_every_row(n):
+    """every pair names item 7, a positive of the even and a negative of the odd batch positions: n_distinct = 1,
+    iptr = [0, P], one wavefront of the item side sums all P pairs"""
+    c = _case(np.random.default_rng(800 + n), n, 203, 64, "sigmoid")
+    pu, pi, pl = np.arange(n), np.full(n, 7), (np.arange(n) % 2 == 0).astype(np.uint8)
+    keep = (np.arange(n) % 3 != 0).astype(np.uint8)
+    lay = dict(_layout_of_pairs(pu, pi, n), plabel=pl)
+    assert len(lay["ditems"]) == 1 and list(lay["iptr"]) == [0, n]
+    _edge_compare(c, f"one item, n = {n}", _launch(c, _device_tables(c), lay, c["users"], keep, REG), pairs=(pu, pi, pl), keep=keep)
+
+
+def test_one_pair_for_every_item():
+    """no item is named twice: n_distinct = P, every item-side wavefront walks one pair"""
+    n, I = 37, 203
+    c = _case(np.random.default_rng(900), n, I, 64, "identity")
+    rng = np.random.default_rng(901)
+    per = rng.integers(1, 6, n)
+    P = int(per.sum())
+    assert P <= I
+    pu = np.repeat(np.arange(n), per)
+    pi = rng.permutation(I)[:P]
+    pi = np.concatenate([np.sort(pi[pu == b]) for b in range(n)])
+    pl, keep = (rng.random(P) < 0.5).astype(np.uint8), (rng.random(P) < 0.5).astype(np.uint8)
+    lay = dict(_layout_of_pairs(pu, pi, n), plabel=pl)
+    assert len(lay["ditems"]) == P
+    _edge_compare(c, "one pair per item", _launch(c, _device_tables(c), lay, c["users"], keep, REG), pairs=(pu, pi, pl), keep=keep)
+
+
+@pytest.mark.parametrize("act", ["sigmoid", "identity"])
+@pytest.mark.parametrize("what", ["dim = 1", "keep_prob = 1"])
+def test_one_column_and_no_dropout(what, act):
+    c = _case(np.random.default_rng(1000), 5, 203, 1 if what == "dim = 1" else 40, act, keep_prob=1.0 if what == "keep_prob = 1" else 0.5)
+    assert what != "keep_prob = 1" or c["keep"][c["pu"] != 1].all()       # (position 1 is the user whose every entry is dropped)
+    _edge_compare(c, f"{what}, {act}", _step(c, _device_tables(c), REG))
+
+
+def test_saturated_logits():
+    """E_de scaled until |r| passes 88 for the positives and for the negatives (expf(-|r|) underflows, sigmoid(r) rounds to 0
+    or 1): the loss stays finite and dr keeps its digits in the -sigmoid(-r) form"""
+    import torch
+    c = _case(np.random.default_rng(1100), 17, 203, 64, "sigmoid")
+    c["par"]["de_bias"][:] = 0.0
+
+    def logits():
+        detail = {}
+        with torch.no_grad():
+            bce, _ = T.losses_f64([torch.tensor(c["par"][k], dtype=torch.float64) for k in T.PARAMS], c["users"], c["pu"], c["pi"],
+                                  c["pl"], c["keep"], 0.5, "sigmoid", detail=detail)
+        return detail["r"].numpy(), bce.item()
+    r, _ = logits()
+    s = 90.0 / min(np.abs(r[c["pl"] == 1]).max(), np.abs(r[c["pl"] == 0]).max())
+    c["par"]["de_embeddings"] = (c["par"]["de_embeddings"].astype(np.float64) * s).astype(np.float32)
+    r, bce = logits()
+    print("max |r| of the positives", np.abs(r[c["pl"] == 1]).max(), "of the negatives", np.abs(r[c["pl"] == 0]).max(), "bce", bce)
+    assert np.isfinite(bce) and np.abs(r[c["pl"] == 1]).max() > 88 and np.abs(r[c["pl"] == 0]).max() > 88
+    assert r[c["pl"] == 1].min() < -88 or r[c["pl"] == 0].max() > 88            # a saturated pair on the wrong side: |dr| = 1
+    _edge_compare(c, "logits of 90", _step(c, _device_tables(c), REG))
+
+
+def test_an_empty_batch_writes_a_zero_loss_and_nothing_else():
+    import torch
+    from skrec import _hip
+    from skrec.recommender.CDAE import CDAE
+    c = _case(np.random.default_rng(1200), 5, 203, 64, "sigmoid")
+    tabs = _device_tables(c)
+    lay = _layout(c)
+    dev = {k: torch.from_numpy(lay[k]).cuda() for k in LAYOUT_KEYS}
+    du, dk = torch.from_numpy(c["users"]).cuda(), torch.from_numpy(c["keep"]).cuda()
+    grads = [torch.full_like(t, 3.0) for t in tabs]
+    work = torch.full((4096,), 255, dtype=torch.uint8, device="cuda")
+    loss = torch.full((2,), 7.0, device="cuda")
+    _hip.check(_hip.lib().skr_cdae_step(*[_hip.ptr(t) for t in tabs], _hip.ptr(du), *[_hip.ptr(dev[k]) for k in ("uptr", "pitem", "plabel")],
+                                        _hip.ptr(dk), *[_hip.ptr(dev[k]) for k in ("puser", "ditems", "iptr", "ipair")], 0, 0, 0,
+                                        c["nU"], c["I"], 64, _hip.SKR_CDAE_SIGMOID, 0.5, REG, *[_hip.ptr(g) for g in grads],
+                                        _hip.ptr(work), work.numel(), _hip.ptr(loss), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 0.0).all() and all((g == 3.0).all() for g in grads) and (work == 255).all()
+    # through the class: a zero pair, and a fresh model (zero moments) keeps its bits
+    rng = np.random.default_rng(1201)
+    m = CDAE.detached(40, 90, dict(CONFIG, hidden_dim=48), _synth_csr(rng, 40, 90), seed=9)
+    flat = m._flat.clone()
+    out = m.train_step(np.zeros(0, np.int32))
+    assert out.shape == (2,) and not out.any() and torch.equal(flat, m._flat) and m.update_count == 1
+    assert not m.optimizer.grad.any() and not m.optimizer.m.any() and not m.optimizer.v.any()
+
+
+def test_queries_skip_what_is_out_of_range():
+    """d_users with an id below 0, one at n_users and a valid id twice; a train row holding items out of range (skipped).
+    Rows nobody names, the skipped ids' would-be rows among them, keep the sentinel bit for bit; n = 0 is allowed"""
+    import torch
+    from skrec import _hip
+    rng = np.random.default_rng(1300)
+    nU, I, d = 30, 90, 24
+    rowptr, items = _synth_csr(rng, nU, I)
+    items = items.copy()
+    row5 = slice(rowptr[5], rowptr[5 + 1])
+    assert rowptr[6] - rowptr[5] >= 3
+    items[rowptr[5]], items[rowptr[5] + 1] = -1, I                  # (the row is no longer ascending: queries do not need it)
+    par = dict(en_embeddings=rng.standard_normal((I, d)) * 0.1, en_offset=rng.standard_normal(d) * 0.2,
+               de_embeddings=np.zeros((I, d)), de_bias=np.zeros((I, 1)), user_embeddings=rng.standard_normal((nU, d)) * 0.2)
+    c = dict(d=d, I=I, par={k: v.astype(np.float32) for k, v in par.items()})
+    en, _, _, off, U = _device_tables(c)
+    users = np.array([5, -1, 12, nU, 5, 0, nU - 1], np.int32)
+    Q = torch.full((nU + 1, 64), 7.0, device="cuda")
+    drp, dit, du = (torch.from_numpy(a).cuda() for a in (rowptr, items, users))
+    args = (_hip.ptr(en), _hip.ptr(off), _hip.ptr(U), _hip.ptr(drp), _hip.ptr(dit), _hip.ptr(du))
+    _hip.check(_hip.lib().skr_cdae_queries(*args, 0, nU, I, d, _hip.SKR_CDAE_SIGMOID, _hip.ptr(Q), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (Q == 7.0).all()
+    _hip.check(_hip.lib().skr_cdae_queries(*args, len(users), nU, I, d, _hip.SKR_CDAE_SIGMOID, _hip.ptr(Q), _hip.stream()))
+    got = Q.cpu().numpy()
+    valid = np.array([5, 12, 0, nU - 1])
+    assert (got[np.setdiff1d(np.arange(nU + 1), valid)] == 7.0).all()
+    p64 = {k: v.astype(np.float64) for k, v in c["par"].items()}
+    rows = [items[rowptr[u]:rowptr[u + 1]] for u in valid]
+    pre = np.stack([p64["en_embeddings"][r[(r >= 0) & (r < I)]].sum(0) for r in rows]) + p64["user_embeddings"][valid] + p64["en_offset"]
+    assert len(rows[0]) - ((rows[0] >= 0) & (rows[0] < I)).sum() == 2 and items[row5].size == len(rows[0])
+    np.testing.assert_allclose(got[valid, :d], 1 / (1 + np.exp(-pre)), rtol=1e-5, atol=2e-6)
+    assert not got[valid, d:].any()

@@ -461,3 +461,241 @@ def test_run_skrec_cli(seq_dir, tmp_path):
     assert "epoch 1:" in r.stdout and "best:" in r.stdout and "Recall@5" in r.stdout
     logs = list((tmp_path / "log").rglob("*.log"))
     assert len(logs) == 1 and "NDCG@10" in logs[0].read_text()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+NU, NI = 50, 80
+GRADS = ("P", "E", "W2", "b2", "Wi", "Wu", "bi", "bu", "wi", "Wiu")
+
+
+def _hgn_device(par, ids, L, T, pad, n=None, slots=1, loss=None):
+    """one skr_hgn_step on zeroed gradients -> ([gP, gE, gW2, gb2, gG] on the host, the loss words)"""
+    import torch
+    from skrec import _hip
+    P, E, W2, b2, Wi, bi, Wu, bu, wi, Wiu = par
+    tabs = [torch.from_numpy(_pad2(t, t.shape[0], 64)).cuda() for t in (P, E, W2)]
+    tabs += [torch.from_numpy(b2).cuda(), torch.from_numpy(_gate_block(Wi, bi, Wu, bu, wi, Wiu)).cuda()]
+    ng = _hip.hgn_gate_floats(L)
+    assert tabs[4].numel() == ng
+    grads = [torch.zeros_like(t) for t in tabs]
+    work = torch.full((_hip.SKR_HGN_MAX_BLOCKS * ng,), float("nan"), device="cuda")      # no initial contents
+    d_ids = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda() for a in ids]
+    loss = torch.zeros(2 * slots, device="cuda") if loss is None else loss
+    n = len(ids[0]) if n is None else n
+    _hip.check(_hip.lib().skr_hgn_step(*[_hip.ptr(t) for t in tabs], *[_hip.ptr(t) for t in d_ids], n, P.shape[0], E.shape[0], pad,
+                                       64, L, T, *[_hip.ptr(t) for t in grads], _hip.ptr(work), _hip.ptr(loss), slots,
+                                       _hip.stream()))
+    torch.cuda.synchronize()
+    return [g.cpu().numpy() for g in grads], loss.cpu().numpy()
+
+
+def _hgn_twin(par, ids, pad, ok):
+    """float64 autograd of the restatement on the instances ``ok`` (the loss is a sum: no divisor) -> (loss, {name: gradient});
+    the padding row of W2 and b2 gets no gradient, whatever names it"""
+    import torch
+    t64 = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in par]
+    tP, tE, tW2, tb2, tWi, tbi, tWu, tbu, twi, tWiu = t64
+    U_, S_, P_, N_ = (torch.from_numpy(np.asarray(a)[ok]).long() for a in ids)
+    q = _restated_query(tP, tE, tWi, tbi, tWu, tbu, twi, tWiu, U_, S_, pad)
+    yp = (tW2[P_] * q.unsqueeze(1)).sum(-1) + tb2[P_]
+    yn = (tW2[N_] * q.unsqueeze(1)).sum(-1) + tb2[N_]
+    bpr = -torch.nn.functional.logsigmoid(yp - yn).sum()
+    bpr.backward()
+    g = {k: (np.zeros(t.shape) if t.grad is None else t.grad.numpy().copy())
+         for k, t in zip(("P", "E", "W2", "b2", "Wi", "bi", "Wu", "bu", "wi", "Wiu"), t64)}
+    if pad >= 0:
+        g["W2"][pad], g["b2"][pad] = 0.0, 0.0
+    return bpr.item(), g
+
+
+def _hgn_edge_compare(what, par, ids, L, T, pad, ok=None, gates_only=False):
+    """the device step against the twin on the instances ``ok`` (all when None) with the suite's bounds; then the rows that
+    no instance of ``ok`` names, the padded columns and the padding rows are exactly zero.  Prints one ``edge-error`` line
+    per tensor (collected into profiles/scaffold_edges_errors.txt)"""
+    n = len(ids[0])
+    ok = np.ones(n, bool) if ok is None else ok
+    want_loss, G = _hgn_twin(par, ids, pad, ok)
+    assert np.isfinite(want_loss) and all(np.isfinite(v).all() for v in G.values())
+    (gP, gE, gW2, gb2, gG), loss = _hgn_device(par, ids, L, T, pad)
+    print(what, "loss", loss[0], want_loss)
+    np.testing.assert_allclose(loss[0], want_loss, rtol=1e-5, err_msg=what)
+    assert loss[1] == 0.0
+    gm, gv = gG[:8192].reshape(2, 64, 64), gG[8192:8384].reshape(3, 64)
+    checks = [("P", gP, G["P"]), ("E", gE, G["E"]), ("W2", gW2, G["W2"]), ("b2", gb2[:, None], G["b2"][:, None]),
+              ("Wi", gm[0], G["Wi"]), ("Wu", gm[1], G["Wu"]), ("bi", gv[0][None], G["bi"][None]), ("bu", gv[1][None], G["bu"][None]),
+              ("wi", gv[2][None], G["wi"].T), ("Wiu", gG[8384:].reshape(L, 64), G["Wiu"].T)]
+    if gates_only:
+        checks = checks[4:]
+    for name, g, w in checks:                       # every tensor is measured before the assertion
+        r, c = w.shape
+        print(f"edge-error HGN | {what} | {name} | {np.abs(g[:r, :c] - w).max():.3e} | {np.abs(w).max():.3e}")
+    for name, g, w in checks:
+        r, c = w.shape
+        assert np.isfinite(g).all(), (what, name)
+        np.testing.assert_allclose(g[:r, :c], w, rtol=1e-4, atol=2e-5 * np.abs(w).max(), err_msg=f"{what}: {name}")
+        assert not g[:, c:].any() and not g[r:].any(), (what, name)
+    u, seq, pos, neg = (np.asarray(a)[ok] for a in ids)
+    named_u, named_e, named_w = (np.zeros(k, bool) for k in (par[0].shape[0], par[1].shape[0], par[1].shape[0]))
+    named_u[u] = True
+    named_e[seq[seq != pad]] = True
+    named_w[np.concatenate([pos.ravel(), neg.ravel()])] = True
+    if pad >= 0:
+        named_w[pad] = False
+    assert not gP[~named_u].any() and not gE[~named_e].any() and not gW2[~named_w].any() and not gb2[~named_w].any(), what
+    return named_u, named_e, named_w
+
+
+@pytest.mark.parametrize("width", [64, 24])
+@pytest.mark.parametrize("L,T", [(16, 4), (17, 5), (32, 16), (3, 8)])
+def test_window_and_target_counts_at_their_edges(L, T, width):
+    """a window that exactly fills the LDS stage of 16 positions, one position past it (window_row's read from global memory),
+    both maxima at once; targets on and past load_pairs' group of four.  Past the stage the windows hold items and padding"""
+    rng = np.random.default_rng(100 * L + T + width)
+    pad, par, ids = _hgn_case(rng, NU, NI, 37, L, T, width)
+    seq = ids[1]
+    if L > 16:
+        seq[5, 16:] = rng.integers(0, NI, L - 16)
+        seq[5, 16 + (L - 16) // 2] = pad                      # padding past the stage, between items
+        seq[8, L - 1] = pad                                   # ... and in the last position
+        assert (seq[:, 16:] != pad).sum() > 20 and (seq[:, 16:] == pad).sum() >= 2
+        assert (seq[:, 16:] != pad).any(1).sum() > 30 and (seq[:, L - 1] != pad).sum() > 30
+    _hgn_edge_compare(f"L = {L}, T = {T}, width = {width}", par, ids, L, T, pad)
+
+
+@pytest.mark.parametrize("n", [1, 2, 4, 5, 4 * 256 - 1, 4 * 256, 4 * 256 + 1, 4 * 256 + 70])
+def test_instance_counts_around_the_grid(n):
+    """fewer instances than a workgroup has wavefronts, one workgroup exactly, one instance more; SKR_HGN_MAX_BLOCKS
+    workgroups less one instance, exactly, and the grid-stride loop's second trip for one and for 70 instances"""
+    from skrec import _hip
+    assert _hip.SKR_HGN_MAX_BLOCKS == 256
+    pad, par, ids = _hgn_case(np.random.default_rng(200 + n), NU, NI, n, 5, 3, 64)
+    _hgn_edge_compare(f"n = {n}", par, ids, 5, 3, pad)
+
+
+@pytest.mark.parametrize("n", [61, 64, 65, 253, 257])
+def test_partial_counts_around_the_reduction(n):
+    """16, 16, 17, 64 and 65 workgroup partials: on either side of hgn_reduce_kernel's R_WAVES wavefronts and of its
+    four-way unrolled trip; the gate block's gradients against the twin"""
+    pad, par, ids = _hgn_case(np.random.default_rng(300 + n), NU, NI, n, 5, 3, 64)
+    _hgn_edge_compare(f"{(n + 3) // 4} partials", par, ids, 5, 3, pad, gates_only=True)
+
+
+def _without(ids, users, items, rng):
+    """the batch with every occurrence of ``users`` / ``items`` replaced by other ids"""
+    u, seq, pos, neg = ids
+    u[np.isin(u, users)] = 0
+    for a in (seq, pos, neg):
+        hit = np.isin(a, items)
+        a[hit] = rng.integers(0, 60, hit.sum())
+
+
+def test_ids_out_of_range_skip_their_instance():
+    """one bad id per instance: d_u (instance 0 and n - 1), the first and the last position of a window, the first and the
+    last positive, the first and the last negative; below 0 and equal to n_users / n_rows.  The result is that of the batch
+    without those eight instances; instance 3 alone names user 49 and the items 77, 78, 79: their rows stay exactly zero"""
+    rng = np.random.default_rng(400)
+    n, L, T = 37, 5, 3
+    pad, par, ids = _hgn_case(rng, NU, NI, n, L, T, 64)
+    _without(ids, [49], [77, 78, 79], rng)
+    u, seq, pos, neg = ids
+    u[3], seq[3, 1], pos[3, 1], neg[3, 1] = 49, 79, 78, 77
+    n_rows = NI + 1
+    u[0], u[n - 1] = -1, NU
+    seq[3, 0], seq[7, L - 1] = -2, n_rows
+    pos[10, 0], pos[13, T - 1] = -1, n_rows
+    neg[20, 0], neg[25, T - 1] = n_rows, -5
+    ok = np.ones(n, bool)
+    ok[[0, n - 1, 3, 7, 10, 13, 20, 25]] = False
+    for a, lim in zip(ids, (NU, n_rows, n_rows, n_rows)):
+        assert ((a[ok] >= 0) & (a[ok] < lim)).all()
+    named_u, named_e, named_w = _hgn_edge_compare("ids out of range", par, ids, L, T, pad, ok=ok)
+    assert not named_u[49] and not named_e[79] and not named_w[78] and not named_w[77]
+
+
+def test_without_a_padding_row_a_minus_one_is_an_id_out_of_range():
+    """pad_idx = -1: a -1 in a window skips the instance, it is not read as padding"""
+    rng = np.random.default_rng(401)
+    n, L, T = 21, 5, 3
+    pad, par, ids = _hgn_case(rng, NU, NI, n, L, T, 64)
+    seq = ids[1]
+    seq[seq == pad] = rng.integers(0, NI, (seq == pad).sum())
+    seq[4, 2] = -1
+    ok = np.arange(n) != 4
+    _hgn_edge_compare("pad_idx = -1", par, ids, L, T, -1, ok=ok)
+
+
+def test_padding_in_windows_and_targets():
+    """a window of nothing but padding (den > 0, e = 0: q = p); a positive and a negative equal to pad_idx: scored against
+    the padding row's zeros, and that row gets no gradient"""
+    rng = np.random.default_rng(500)
+    n, L, T = 21, 5, 3
+    pad, par, ids = _hgn_case(rng, NU, NI, n, L, T, 64)
+    u, seq, pos, neg = ids
+    seq[2, :] = pad
+    pos[4, 0], neg[6, T - 1] = pad, pad
+    assert (seq[2] == pad).all() and (pos == pad).sum() == 1 and (neg == pad).sum() == 1
+    _hgn_edge_compare("padding everywhere", par, ids, L, T, pad)
+
+
+def test_loss_slots():
+    """loss_slots = SKR_LOSS_SLOTS: word 0 of the slots sums to the single-slot loss, word 1 of every slot is untouched"""
+    import torch
+    from skrec import _hip
+    S = _hip.SKR_LOSS_SLOTS
+    pad, par, ids = _hgn_case(np.random.default_rng(600), NU, NI, 300, 5, 3, 64)
+    _, one = _hgn_device(par, ids, 5, 3, pad)
+    loss = torch.zeros((S, 2), device="cuda")
+    loss[:, 1] = 7.0
+    _, spread = _hgn_device(par, ids, 5, 3, pad, slots=S, loss=loss.view(-1))
+    spread = spread.reshape(S, 2)
+    assert (spread[:, 1] == 7.0).all() and (spread[:, 0] != 0).all()
+    np.testing.assert_allclose(spread[:, 0].astype(np.float64).sum(), one[0], rtol=1e-6)
+
+
+def test_an_empty_batch_touches_nothing():
+    import torch
+    from skrec import _hip
+    pad, par, ids = _hgn_case(np.random.default_rng(700), NU, NI, 5, 5, 3, 64)
+    P, E, W2, b2, Wi, bi, Wu, bu, wi, Wiu = par
+    tabs = [torch.from_numpy(a).cuda() for a in (P, E, W2, b2, _gate_block(Wi, bi, Wu, bu, wi, Wiu))]
+    grads = [torch.full_like(t, 3.0) for t in tabs]
+    work = torch.full((_hip.SKR_HGN_MAX_BLOCKS * _hip.hgn_gate_floats(5),), 5.0, device="cuda")
+    loss = torch.full((2,), 7.0, device="cuda")
+    d_ids = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in ids]
+    _hip.check(_hip.lib().skr_hgn_step(*[_hip.ptr(t) for t in tabs], *[_hip.ptr(t) for t in d_ids], 0, NU, NI + 1, pad, 64, 5, 3,
+                                       *[_hip.ptr(t) for t in grads], _hip.ptr(work), _hip.ptr(loss), 1, _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and all((g == 3.0).all() for g in grads) and (work == 5.0).all()
+
+
+def test_queries_skip_users_out_of_range():
+    """d_users with an id below 0, one at n_users and a valid id twice (with the same window): rows nobody names, the skipped
+    ids' would-be rows among them, keep the sentinel bit for bit; n = 0 is allowed"""
+    import torch
+    from skrec import _hip
+    rng = np.random.default_rng(800)
+    L = 5
+    pad, par, _ = _hgn_case(rng, NU, NI, 8, L, 1, 64)
+    P, E, W2, b2, Wi, bi, Wu, bu, wi, Wiu = par
+    users = np.array([5, -1, 12, NU, 5, 0, NU - 1], np.int32)
+    win = rng.integers(0, NI, (len(users), L)).astype(np.int32)
+    win[4] = win[0]
+    win[2, :2] = pad
+    dP, dE = (torch.from_numpy(t).cuda() for t in (P, E))
+    dG = torch.from_numpy(_gate_block(Wi, bi, Wu, bu, wi, Wiu)).cuda()
+    Q = torch.full((NU + 1, 64), 7.0, device="cuda")
+    du, dw = torch.from_numpy(users).cuda(), torch.from_numpy(win).cuda()
+    args = (_hip.ptr(dP), _hip.ptr(dE), _hip.ptr(dG), _hip.ptr(du))
+    _hip.check(_hip.lib().skr_hgn_queries(*args, 0, _hip.ptr(dw), NU, NI + 1, pad, 64, L, _hip.ptr(Q), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (Q == 7.0).all()
+    _hip.check(_hip.lib().skr_hgn_queries(*args, len(users), _hip.ptr(dw), NU, NI + 1, pad, 64, L, _hip.ptr(Q), _hip.stream()))
+    got = Q.cpu().numpy()
+    rows = np.array([0, 2, 5, 6])                         # the list's entries with a valid id, the repeated one once
+    valid = users[rows]
+    assert (got[np.setdiff1d(np.arange(NU + 1), valid)] == 7.0).all()
+    t64 = [torch.tensor(a, dtype=torch.float64) for a in (P, E, Wi, bi, Wu, bu, wi, Wiu)]
+    want = _restated_query(*t64, torch.from_numpy(valid).long(), torch.from_numpy(win[rows]).long(), pad).numpy()
+    np.testing.assert_allclose(got[valid], want, rtol=1e-5, atol=2e-6)

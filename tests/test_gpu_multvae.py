@@ -404,3 +404,325 @@ def test_run_skrec_cli(tiny_dir, tmp_path):
                         "--seed", "7"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "epoch 1:" in r.stdout and "best:" in r.stdout and "Recall@5" in r.stdout
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. the edge batches
+# ---------------------------------------------------------------------------------------------------------------------
+ANNEAL = 0.15
+
+
+def _rows(rng, nU, I, lo=1, hi=30):
+    """nU ascending train rows of lo .. hi - 1 items (at most I)"""
+    return [np.sort(rng.choice(I, min(int(n), I), replace=False)).astype(np.int32) for n in rng.integers(lo, hi, nU)]
+
+
+def _edge_case(rng, rows, users, I, d, keep_prob):
+    """a case of _step's form on the CSR ``rows`` for the batch ``users`` as it stands: ids out of range and users that come
+    twice included.  A user out of range is an all-zero row of x, as an empty train row is; the keep flags follow the
+    non-zeros of the valid rows in batch order.  In every row of two or more items at least one is kept"""
+    nU, B = len(rows), len(users)
+    rowptr = np.zeros(nU + 1, np.int64)
+    rowptr[1:] = np.cumsum([len(r) for r in rows])
+    items = np.concatenate(rows + [np.zeros(1, np.int32)])[:rowptr[-1] + 1].astype(np.int32)    # never an empty array
+    x = np.zeros((B, I), np.float64)
+    keep = []
+    for r, u in enumerate(users):
+        if 0 <= u < nU:
+            x[r, rows[u]] = 1.0
+            k = (rng.random(len(rows[u])) < keep_prob).astype(np.uint8) if keep_prob < 1 else np.ones(len(rows[u]), np.uint8)
+            if len(k) > 1:
+                k[rng.integers(len(k))] = 1
+            keep.append(k)
+    keep = np.concatenate(keep + [np.zeros(0, np.uint8)])
+    c = dict(nU=nU, I=I, d=d, B=B, rowptr=rowptr, items=items, users=np.asarray(users, np.int32), keep_prob=keep_prob,
+             Wq=(rng.standard_normal((2 * d, I)) * 0.2).astype(np.float32), bq=(rng.standard_normal(2 * d) * 0.2).astype(np.float32),
+             Wp=(rng.standard_normal((I, d)) * 0.3).astype(np.float32), bp=(rng.standard_normal(I) * 0.3).astype(np.float32),
+             keep=keep, eps=rng.standard_normal((B, d)).astype(np.float32), x=x)
+    c["mask"] = T.keep_mask(x, keep)
+    return c
+
+
+def _edge_compare(c, what, got, anneal=ANNEAL, cancel=None):
+    """the device's (gradients, loss) against float64 autograd of the twin (n the divisor of both means, zero rows of x
+    included) with the suite's bounds and its per-parameter scale for the two halves of Wq and bq; the rows of WqT that no
+    kept non-zero names are exactly zero.  ``cancel`` ({"neg_ll", "Wp", "bp": size}): a case in which those three are
+    identically zero takes their scale from the terms that cancel (see _decoder_terms), as the HGN suite does at L = 1.
+    Prints one ``edge-error`` line per tensor"""
+    import torch
+    (gWqT, gbq, gWp, gbp), loss = got
+    d = c["d"]
+    t64 = [torch.tensor(c[k], dtype=torch.float64, requires_grad=True) for k in T.PARAMS]
+    neg_ll, kl = T.losses_f64(*t64, c["x"], c["mask"], c["eps"], c["keep_prob"])
+    (neg_ll + anneal * kl).backward()
+    want = [t.grad.numpy() for t in t64]
+    assert np.isfinite(neg_ll.item()) and np.isfinite(kl.item()) and all(np.isfinite(w).all() for w in want)
+    print(what, "neg_ll", loss[0], neg_ll.item(), "kl", loss[1], kl.item())
+    assert np.isfinite(loss).all() and all(np.isfinite(g).all() for g in got[0]), what
+    cancel = cancel or {}
+    np.testing.assert_allclose(loss[0], neg_ll.item(), rtol=1e-5, atol=1e-5 * cancel.get("neg_ll", 0.0), err_msg=what)
+    np.testing.assert_allclose(loss[1], kl.item(), rtol=1e-5, err_msg=what)
+    wq, wbq = want[0], want[1]
+    checks = [("Wq_mu", gWqT[:, :d], wq[:d].T), ("Wq_logvar", gWqT[:, 64:64 + d], wq[d:].T), ("bq_mu", gbq[None, :d], wbq[None, :d]),
+              ("bq_logvar", gbq[None, 64:64 + d], wbq[None, d:]), ("Wp", gWp[:, :d], want[2]), ("bp", gbp[None], want[3][None])]
+    scale = {"Wq": np.abs(wq).max(), "bq": np.abs(wbq).max()}
+    scale.update({k: max(np.abs(want[i]).max(), cancel[k]) for i, k in ((2, "Wp"), (3, "bp")) if k in cancel})
+    for name, g, w in checks:                       # every tensor is measured before the assertion
+        print(f"edge-error MultVAE | {what} | {name} | {np.abs(g - w).max():.3e} | {scale.get(name[:2], np.abs(w).max()):.3e}")
+    for name, g, w in checks:
+        np.testing.assert_allclose(g, w, rtol=1e-4, atol=2e-5 * scale.get(name[:2], np.abs(w).max()), err_msg=f"{what}: {name}")
+    assert not gWqT[:, d:64].any() and not gWqT[:, 64 + d:].any() and not gWp[:, d:].any()
+    assert not gbq[d:64].any() and not gbq[64 + d:].any()
+    untouched = ~(c["mask"] != 0).any(0)
+    assert not gWqT[untouched].any(), what
+    return untouched
+
+
+@pytest.mark.parametrize("keep_prob", [0.5, 1.0])
+@pytest.mark.parametrize("d", [64, 24])
+@pytest.mark.parametrize("B", [1, 2, 15, 16, 17, 63, 64, 65])
+def test_batch_sizes_around_the_tiles(B, d, keep_prob):
+    """users below, at and above the 16 rows of an MFMA tile and the 64 of a user chunk (load_a, sZ, sG); I = 200: three
+    full tiles and one of eight items"""
+    rng = np.random.default_rng(1000 + 10 * B + d + int(keep_prob))
+    rows = _rows(rng, B + 3, 200)
+    rows[0] = np.array([0, 199], np.int32)
+    c = _edge_case(rng, rows, rng.permutation(B + 3)[:B], 200, d, keep_prob)
+    untouched = _edge_compare(c, f"B = {B}, d = {d}, keep_prob = {keep_prob}", _step(c, _device_tables(c), ANNEAL))
+    assert B > 15 or untouched.any()
+
+
+def _decoder_terms(c):
+    """The sizes of the decoder side's terms in the float64 twin: neg_ll = mean_u (n_u lse_u - sum_{i in x_u} logit_ui),
+    d bp[i] = sum_u (n_u softmax_ui - x_ui) / B and d Wp[i] = sum_u (n_u softmax_ui - x_ui) z_u / B are differences of two
+    terms that the step computes apart (lse over the tiles, the positives' logits in the encoder launch; n_u softmax in
+    pass 2, then - x).  With ONE item softmax is 1, every row is that item, and all three are identically zero in exact
+    arithmetic: what any fp32 evaluation returns is the rounding residue of the subtraction, so max|twin| = 0 is no scale.
+    Their scale is the size of the term that is subtracted: mean_u |sum logits|, max_i sum_u x_ui / B, max sum_u x_ui |z_u| / B"""
+    import torch
+    d, B = c["d"], c["B"]
+    with torch.no_grad():
+        Wq, bq, Wp, bp = (torch.tensor(c[k], dtype=torch.float64) for k in T.PARAMS)
+        x, mask, eps = (torch.as_tensor(a, dtype=torch.float64) for a in (c["x"], c["mask"], c["eps"]))
+        e = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) * mask / c["keep_prob"] @ Wq.T + bq
+        z = e[:, :d] + eps * (0.5 * e[:, d:]).exp()
+        pos = ((z @ Wp.T + bp) * x).sum(1)
+        return {"neg_ll": float(pos.abs().mean()), "bp": float(x.sum(0).max() / B), "Wp": float((x.T @ z.abs()).max() / B)}
+
+
+@pytest.mark.parametrize("I", [1, 63, 64, 65, 128, 64 * 512, 64 * 512 + 1, 64 * (512 + 90) + 7])
+def test_catalogue_sizes_around_the_tiles(I):
+    """one item; less than a tile; the last tile exactly full (64, 128); one item into the next; and beyond 64 x
+    SKR_MULTVAE_MAX_WG items, where tile_range hands a workgroup several tiles: every workgroup exactly one, the first
+    workgroup two, a ragged split of 603 tiles.  B = 5; a row holds the first and the last item, another is long.
+    At I = 1 neg_ll, d Wp and d bp are identically zero (the twin returns exact zeros; measured on the device: neg_ll =
+    3.2e-07): their bounds take _decoder_terms' scales, 1e-5 and 2e-5 of the terms that cancel"""
+    rng = np.random.default_rng(2000 + I)                  # (SKR_MULTVAE_MAX_WG of include/skrec_hip.h is 512)
+    rows = _rows(rng, 7, I, 1, 40)
+    rows[1] = np.unique(np.array([0, I - 1], np.int32))
+    if I > 128:
+        rows[2] = np.sort(rng.choice(I, 700, replace=False)).astype(np.int32)
+        # pass 2's cursor has to move on only where a workgroup owns a second tile (tile_range: workgroup b of wg owns the
+        # tiles [b tiles / wg, (b + 1) tiles / wg)): a row holding every item of both tiles of such a workgroup, so that the
+        # second tile's entries lie 64 entries past the cursor the workgroup started from
+        tiles, wg = (I + 63) // 64, 512
+        if tiles > wg:
+            b = next(b for b in range(wg) if (b + 1) * tiles // wg - b * tiles // wg == 2)
+            t = b * tiles // wg
+            rows[3] = np.arange(64 * t, min(64 * (t + 2), I), dtype=np.int32)
+            assert len(rows[3]) > 64
+    c = _edge_case(rng, rows, [1, 2, 0, 5, 3], I, 64 if I % 2 else 40, 0.5)
+    cancel = None
+    if I == 1:
+        assert c["x"].all()
+        cancel = _decoder_terms(c)
+        print("the terms that cancel at I = 1:", cancel)
+        assert min(cancel.values()) > 1e-2
+    _edge_compare(c, f"I = {I}", _step(c, _device_tables(c), ANNEAL), cancel=cancel)
+
+
+def test_rows_that_fill_a_tile():
+    """pass 2 reads one CSR entry per lane and tile and moves the cursor on by a ballot count: a row that is exactly the 64
+    items of tile 1, a row that is the whole catalogue (every lane of every tile, the last tile ragged), a row of the two
+    items on either side of a tile boundary"""
+    I = 200
+    rng = np.random.default_rng(3000)
+    rows = _rows(rng, 6, I)
+    rows[0], rows[1], rows[2] = np.arange(64, 128, dtype=np.int32), np.arange(I, dtype=np.int32), np.array([63, 64], np.int32)
+    users = [3, 0, 1, 2, 4]
+    c = _edge_case(rng, rows, users, I, 64, 0.5)
+    assert [int(c["x"][r].sum()) for r in (1, 2, 3)] == [64, I, 2]
+    assert c["x"][1, 64:128].all() and c["x"][3, 63] == c["x"][3, 64] == 1
+    _edge_compare(c, "rows that fill a tile", _step(c, _device_tables(c), ANNEAL))
+
+
+def _draws_of(c, seed, step):
+    """skr_multvae_draws for the batch of ``c``, users out of range included -> (keep, eps [B, 64])"""
+    import torch
+    from skrec import _hip
+    n, nnz = c["B"], int(c["x"].sum())
+    drp, dit, du = (torch.from_numpy(np.ascontiguousarray(c[k])).cuda() for k in ("rowptr", "items", "users"))
+    off = torch.full((n + 2,), -5, dtype=torch.int32, device="cuda")
+    keep = torch.full((nnz + 1,), 9, dtype=torch.uint8, device="cuda")
+    eps = torch.empty((n, 64), device="cuda")
+    _hip.check(_hip.lib().skr_multvae_draws(_hip.ptr(drp), _hip.ptr(dit), _hip.ptr(du), n, c["nU"], c["d"], c["keep_prob"], seed,
+                                            step, _hip.ptr(off), _hip.ptr(keep), _hip.ptr(eps), _hip.stream()))
+    k, o = keep.cpu().numpy(), off.cpu().numpy()
+    assert k[nnz] == 9 and o[n] == nnz and o[n + 1] == -5 and np.array_equal(np.diff(o[:n + 1]), c["x"].sum(1).astype(np.int64))
+    return k[:nnz], eps.cpu().numpy()
+
+
+def _with_zero_rows(seed):
+    """B = 6 on 9 users: batch positions 1, 2 and 4 are a user with an empty train row, an id below 0 and the id n_users;
+    no row holds item 5"""
+    rng = np.random.default_rng(seed)
+    I = 200
+    rows = [np.setdiff1d(r, [5]).astype(np.int32) for r in _rows(rng, 9, I, 2, 30)]
+    rows[4] = np.zeros(0, np.int32)
+    users = [2, 4, -1, 7, 9, 0]
+    c = _edge_case(rng, rows, users, I, 40, 0.5)
+    assert [int(s) for s in c["x"].sum(1)][1:5:1] == [0, 0, len(rows[7]), 0] and not c["x"][:, 5].any()
+    return c
+
+
+def test_empty_rows_and_users_out_of_range_are_rows_of_the_batch():
+    """n stays the divisor of both means; such a row adds nothing to neg_ll, the KL of bq to kl, and that term's gradient
+    to gbq alone (h = 0: nothing for Wq, and (n_u softmax - x) = 0: nothing for the decoder)"""
+    import torch
+    c = _with_zero_rows(4000)
+    tabs = _device_tables(c)
+    got = _step(c, tabs, ANNEAL)
+    untouched = _edge_compare(c, "empty rows, recorded draws", got)
+    assert untouched[5]
+    # the same batch without the three rows, the means over 6 still: the device's own result, scaled
+    live = c["x"].any(1)
+    assert live.sum() == 3
+    c3 = dict(c, B=3, users=c["users"][live], x=c["x"][live], mask=c["mask"][live], eps=c["eps"][live])
+    g3, l3 = _step(c3, tabs, ANNEAL)
+    t64 = [torch.tensor(c[k], dtype=torch.float64) for k in T.PARAMS]
+    zero = np.zeros((3, c["I"]))
+    kl0 = T.losses_f64(*t64, zero, zero, np.zeros((3, c["d"])), 0.5)[1].item()           # the KL of bq, per row
+    np.testing.assert_allclose(got[1][0], l3[0] * 3 / 6, rtol=1e-5)
+    np.testing.assert_allclose(got[1][1], (l3[1] * 3 + kl0 * 3) / 6, rtol=1e-5)
+    for k in (0, 2, 3):                                     # Wq, Wp, bp: nothing from the three rows
+        np.testing.assert_allclose(got[0][k], g3[k] * np.float32(0.5), rtol=1e-4, atol=2e-5 * np.abs(got[0][k]).max())
+
+
+def test_empty_rows_and_users_out_of_range_under_device_draws():
+    """d_keep = d_eps = NULL: two calls give the same bits on the decoder side, and the step equals the explicit-draw step
+    fed with skr_multvae_draws' output, which equals the twin"""
+    c = _with_zero_rows(4001)
+    tabs = _device_tables(c)
+    (ga, la), (gb, lb) = (_step(c, tabs, ANNEAL, draws=False, seed=5, step=9) for _ in range(2))
+    assert np.array_equal(la.view(np.uint32), lb.view(np.uint32))
+    for k in (1, 2, 3):
+        assert np.array_equal(ga[k].view(np.uint32), gb[k].view(np.uint32))
+    c["keep"], e = _draws_of(c, 5, 9)
+    c["eps"], c["mask"] = e[:, :c["d"]], T.keep_mask(c["x"], c["keep"])
+    assert not e[:, c["d"]:].any() and np.isfinite(e).all()
+    ge, le = _step(c, tabs, ANNEAL)
+    assert np.array_equal(la, le) and np.array_equal(ga[2], ge[2]) and np.array_equal(ga[3], ge[3])
+    np.testing.assert_allclose(ga[0], ge[0], rtol=1e-5, atol=1e-7)
+    _edge_compare(c, "empty rows, device draws", (ga, la))
+
+
+def test_the_same_user_twice_is_two_rows():
+    rng = np.random.default_rng(5000)
+    rows = _rows(rng, 8, 200, 2, 30)
+    c = _edge_case(rng, rows, [3, 6, 3, 1, 3], 200, 64, 0.5)
+    assert np.array_equal(c["x"][0], c["x"][2]) and not np.array_equal(c["mask"][0], c["mask"][2])
+    _edge_compare(c, "one user three times", _step(c, _device_tables(c), ANNEAL))
+
+
+def test_one_column_and_no_annealing():
+    """dim = 1; anneal = 0: kl is still written, the gradient is that of neg_ll alone"""
+    rng = np.random.default_rng(6000)
+    rows = _rows(rng, 8, 200, 2, 30)
+    c = _edge_case(rng, rows, [3, 6, 0, 1, 5], 200, 1, 0.5)
+    _edge_compare(c, "dim = 1", _step(c, _device_tables(c), ANNEAL))
+    c = _edge_case(rng, rows, [3, 6, 0, 1, 5], 200, 40, 0.5)
+    got = _step(c, _device_tables(c), 0.0)
+    assert got[1][1] > 0
+    _edge_compare(c, "anneal = 0", got, anneal=0.0)
+
+
+def test_full_batch_and_the_batch_over_the_limit():
+    """B = SKR_MULTVAE_MAX_BATCH on 129 items (two full tiles and one item) with rows of 1 to 3 items: 16 user chunks per
+    workgroup; twice: the same bits on the decoder side.  Then 1025 users: refused by name, the workspace size is 0"""
+    import torch
+    from skrec import _hip
+    B = _hip.SKR_MULTVAE_MAX_BATCH
+    assert B == 1024
+    rng = np.random.default_rng(7000)
+    rows = _rows(rng, B + 6, 129, 1, 4)
+    c = _edge_case(rng, rows, rng.permutation(B + 6)[:B], 129, 64, 0.5)
+    tabs = _device_tables(c)
+    got = _step(c, tabs, ANNEAL)
+    _edge_compare(c, "B = 1024", got)
+    again = _step(c, tabs, ANNEAL)
+    for k in (1, 2, 3):
+        assert np.array_equal(got[0][k].view(np.uint32), again[0][k].view(np.uint32))
+    assert np.array_equal(got[1].view(np.uint32), again[1].view(np.uint32))
+    L = _hip.lib()
+    assert L.skr_multvae_workspace(B + 1, 129) == 0
+    dev = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (c["rowptr"], c["items"], np.zeros(B + 1, np.int32))]
+    grads = [torch.zeros_like(t) for t in tabs]
+    work, loss = torch.zeros(1024, device="cuda"), torch.full((2,), 7.0, device="cuda")
+    rc = L.skr_multvae_step(*[_hip.ptr(t) for t in tabs], *[_hip.ptr(t) for t in dev], B + 1, c["nU"], 129, 64, 0.5, ANNEAL, None,
+                            None, 0, 0, *[_hip.ptr(t) for t in grads], _hip.ptr(work), 4096, _hip.ptr(loss), _hip.stream())
+    with pytest.raises(ValueError, match="at most 1024"):
+        _hip.check(rc)
+    torch.cuda.synchronize()
+    assert (loss == 7.0).all() and not any(g.any() for g in grads)
+
+
+def test_an_empty_batch_writes_a_zero_loss_and_nothing_else():
+    import torch
+    from skrec import _hip
+    from skrec.recommender.MultVAE import MultVAE
+    rng = np.random.default_rng(8000)
+    rows = _rows(rng, 8, 200, 2, 30)
+    c = _edge_case(rng, rows, [3], 200, 64, 0.5)
+    tabs = _device_tables(c)
+    dev = [torch.from_numpy(np.ascontiguousarray(c[k])).cuda() for k in ("rowptr", "items", "users")]
+    grads = [torch.full_like(t, 3.0) for t in tabs]
+    work = torch.full((4096,), 255, dtype=torch.uint8, device="cuda")
+    loss = torch.full((2,), 7.0, device="cuda")
+    _hip.check(_hip.lib().skr_multvae_step(*[_hip.ptr(t) for t in tabs], *[_hip.ptr(t) for t in dev], 0, c["nU"], 200, 64, 0.5,
+                                           ANNEAL, None, None, 0, 0, *[_hip.ptr(t) for t in grads], _hip.ptr(work), work.numel(),
+                                           _hip.ptr(loss), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (loss == 0.0).all() and all((g == 3.0).all() for g in grads) and (work == 255).all()
+    # through the class: zeros, and a fresh model keeps its bits (the weights' decay included: an empty batch is no step)
+    m = MultVAE.detached(8, 200, dict(CONFIG, p_dims=[48]), (c["rowptr"], c["items"]), seed=9)
+    w, b = m._weights.clone(), m._biases.clone()
+    out = m.train_step(np.zeros(0, np.int32))
+    assert out.shape == (2,) and not out.any() and torch.equal(w, m._weights) and torch.equal(b, m._biases)
+    assert m.update_count == 0 and not m.step_losses
+
+
+def test_queries_skip_users_out_of_range():
+    """d_users with an id below 0, one at n_users and a valid id twice: rows nobody names, the skipped ids' would-be rows
+    among them, keep the sentinel bit for bit; n = 0 is allowed"""
+    import torch
+    from skrec import _hip
+    rng = np.random.default_rng(9000)
+    nU, I, d = 30, 200, 24
+    rows = _rows(rng, nU, I)
+    c = _edge_case(rng, rows, [0], I, d, 1.0)
+    wqt, bq, _, _ = _device_tables(c)
+    users = np.array([5, -1, 12, nU, 5, 0, nU - 1], np.int32)
+    Q = torch.full((nU + 1, 64), 7.0, device="cuda")
+    drp, dit, du = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (c["rowptr"], c["items"], users))
+    args = (_hip.ptr(wqt), _hip.ptr(bq), _hip.ptr(drp), _hip.ptr(dit), _hip.ptr(du))
+    _hip.check(_hip.lib().skr_multvae_queries(*args, 0, nU, I, _hip.ptr(Q), _hip.stream()))
+    torch.cuda.synchronize()
+    assert (Q == 7.0).all()
+    _hip.check(_hip.lib().skr_multvae_queries(*args, len(users), nU, I, _hip.ptr(Q), _hip.stream()))
+    got = Q.cpu().numpy()
+    valid = np.array([5, 12, 0, nU - 1])
+    assert (got[np.setdiff1d(np.arange(nU + 1), valid)] == 7.0).all()
+    x = T.dense_rows(c["rowptr"], c["items"], valid, I)
+    want = x / np.linalg.norm(x, axis=1, keepdims=True) @ c["Wq"][:d].astype(np.float64).T + c["bq"][:d].astype(np.float64)
+    np.testing.assert_allclose(got[valid, :d], want, rtol=1e-5, atol=2e-6)
+    assert not got[valid, d:].any()

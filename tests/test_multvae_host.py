@@ -61,7 +61,9 @@ def test_abi_argument_checks_without_gpu():
     assert step(keep=p) == -1 and b"together" in L.skr_last_error()
     assert step(work_bytes=64) == -1 and b"skr_multvae_workspace" in L.skr_last_error()
     assert step(n_items=0) == -1
-    assert step(n=0) == 0                     # an empty batch: nothing to launch
+    # (an empty batch WRITES its zero loss pair, so it needs real device memory: tests/test_gpu_multvae.py,
+    # test_an_empty_batch_writes_a_zero_loss_and_nothing_else; its arguments are checked like any batch's)
+    assert step(n=0, dim=65) == -1 and step(n=0, keep=p) == -1
     assert L.skr_multvae_queries(None, p, p, p, None, 4, 10, 100, p, None) == -1
     assert L.skr_multvae_queries(p, p, p, p, None, 11, 10, 100, p, None) == -1 and b"user list" in L.skr_last_error()
     assert L.skr_multvae_draws(p, p, p, 4, 10, 64, 0.5, 1, 0, None, p, p, None) == -1
