@@ -170,20 +170,28 @@ int skr_eval_scores(const float* d_scores, int n_users, int n_items, int64_t ld,
 /* Fused scoring + masking + top-K, no [B, I] matrix in HBM:
  *   score(b, i) = dot(d_user_table[d_users[b]], d_item_table[i]) (+ d_item_bias[i] if non-NULL),
  *   train positives of user d_users[b] excluded, K best (score desc, id asc) written per row.
- *   d_user_table [*, dim], d_item_table [n_items, dim] fp32 row-major, dim == 64
+ *   d_user_table [*, dim], d_item_table [n_items, dim] fp32 row-major, 16-byte aligned; dim is 64, 128, 192 or 256
+ *                (anything else: SKR_EINVAL naming the four widths).  Narrower factors live in rows zero-padded by the
+ *                caller to the next of these widths; the padding adds exact zeros and does not change a score.
  *   d_users      int32[B] user ids (also index the train CSR rows)
  *   d_train_rowptr/d_train_items  CSR over ALL users, items sorted ascending (may be NULL: no mask)
  *   d_topk_ids int32[B, top_k], d_topk_scores float[B, top_k] (may be NULL)
- *   d_work / work_bytes   scratch from skr_eval_fused_workspace(B, top_k)
+ *   d_work / work_bytes   scratch from skr_eval_fused_workspace(B, top_k): the same size at every width (the candidate
+ *                lists are per user; at 64 C columns a wavefront holds 64 / C users of them, 16 at C = 3)
  * Arithmetic (environment SKR_FUSED_MODE, read per call).  "f16x2" (default): every operand, scaled by a power of two
  * per table, is split into TWO fp16 pieces and a product formed from three fp16 MFMA products with fp32 accumulation;
  * fp32-level accuracy (measured error vs float64 below the plain chain's) holds while the scores that decide a list
  * lie well above an absolute floor set by the largest elements of the two tables -- checked per user on the device,
  * and every user that fails is recomputed by the bf16x3 kernel inside the same call (skr_eval_fused_rejected counts
- * them).  "bf16x3": three bf16 pieces, six MFMA products, no condition on the operands (fused_topk_kernel_v6, 16-item
+ * them).  The guard accepts a user whose smallest returned |score| is at least 2^19 * 2^ceil(log2(dim / 64)) / (s_u s_v),
+ * s_u, s_v being the two tables' scales: the floor grows with the length of the dot product, the constant with it, and at
+ * dim == 64 it is the 2^19 it has always been.  "bf16x3": three bf16 pieces, six MFMA products, no condition on the operands (fused_topk_kernel_v6, 16-item
  * steps on v_mfma_f32_16x16x32_bf16).
- * "fp32": exact fp32 FMA chains on the FP32 MFMA.  The split modes keep library-owned device buffers for the split
- * item table (n_items*64*6 bytes, f16x2: + n_items*64*4), one set per process: calls in a split mode must be issued
+ * "fp32": exact fp32 FMA chains on the FP32 MFMA, built for dim == 64 only: with dim > 64 the call is refused with
+ * SKR_EINVAL (the message names the mode and the width) before any device call, and the caller ranks through
+ * skr_score_matrix / skr_mask_train / skr_eval_scores.  Within a row the summation order is fixed (64-column slices in
+ * ascending order, the bias first), so two calls give the same bits; no floating-point atomic is used.  The split modes keep library-owned device buffers for the split
+ * item table (n_items*dim*6 bytes, f16x2: + n_items*dim*4), one set per process: calls in a split mode must be issued
  * on ONE stream at a time (calls on the same stream queue behind each other, which is what the evaluator does).
  * Requires n_items - max train row length >= top_k (else SKR_EINVAL: use skr_eval_scores). */
 size_t skr_eval_fused_workspace(int B, int top_k);

@@ -3,6 +3,11 @@
 // first: the reference arithmetic); and two SPLIT arithmetics on the 16-bit MFMAs, written once as split_sweep<Arith> in the
 // second half of the file -- "bf16x3" (fused_topk_kernel_v6: three bf16 pieces per operand, good for any operands, and the
 // only path for rows the guard rejects) and "f16x2" (fused_topk_kernel_v7, the DEFAULT: two fp16 pieces behind a guard).
+// Those three kernels rank rows of 64 floats.  Rows of 128 / 192 / 256 floats (C = 2, 3, 4 slices of 64 columns) are ranked by
+// split_sweep_wide<Arith, HAS_BIAS, G> in both split arithmetics (fused_topk_wide_f16x2 / _bf16x3, behind the 64-column sweep
+// below); the fp32 mode is not built beyond 64 columns and the entry refuses it there.  Summation order at every width: the
+// seed (the bias, or -inf for rows beyond the catalogue) enters the first MFMA of slice 0 only, within a slice the order is
+// the arithmetic's slot table, and the slices are added in ascending order -- that fixes the bits; no floating-point atomic.
 //
 // Replaces, in one launch and without ever writing the [B, I] score matrix to HBM:
 //   recommender/BPRMF.py:84-88 / LightGCN.py:102-107   U[b] @ V.T (+ bias)         (torch.matmul)
@@ -104,7 +109,8 @@ struct FusedArgs {
     // --- the fp16x2 sweep and its fall-back (fused_topk_kernel_v7 / the bf16x3 kernel over the rows it flagged) -------------
     const int32_t* row_map;     // nullable: logical row r of this launch is row row_map[r] of users / outputs
     const int32_t* n_rows_dev;  // nullable: number of logical rows, read on the device (<= B)
-    const float* guard_s_inv;   // device: 1 / (s_u s_v); a user whose smallest returned |score| is below 2^19 of it is flagged
+    const float* guard_s_inv;   // device: 2^ceil(log2 C) / (s_u s_v) at rows of 64 C floats (F7Scales::S_inv at C = 1, ::guard_inv beyond);
+                                // a user whose smallest returned |score| is below 2^19 of it is flagged
     int32_t* flag_list;
     int32_t* flag_count;
 };
@@ -124,6 +130,7 @@ struct WaveCtx {
     int* row_len;        // LDS: its length (0 when no train mask was given)
     int* rowbuf;         // LDS: scratch for one staged row
     int rowbuf_len;      // its capacity in ints (a multiple of 64, at most FE_ROWBUF)
+    int uw;              // users of this wave: FE_UW, or 32 / 16 in the wide sweeps (the LDS arrays keep FE_UW entries; the rest stay 0)
 };
 
 // The user's train row, fetched into registers when it is short enough to be staged in LDS: issued TOGETHER with the loads
@@ -249,7 +256,7 @@ __device__ __forceinline__ void final_user(const FusedArgs& a, const WaveCtx& w,
 template <int NR>
 __device__ __forceinline__ void final_compactions_n(const FusedArgs& a, const WaveCtx& w) {
     const int64_t left = static_cast<int64_t>(rows_of(a)) - w.ubase;
-    const int n_users = left < FE_UW ? static_cast<int>(left) : FE_UW;
+    const int n_users = left < w.uw ? static_cast<int>(left) : w.uw;
     if (n_users <= 0) return;
     __threadfence_block();   // the wave's appends, re-read below by other lanes of the same wave
     uint64_t kn[NR];
@@ -519,6 +526,7 @@ __global__ __launch_bounds__(FE_WAVES * 64, 2) void fused_topk_kernel_v3(FusedAr
     w.row_len = s_row_len[wv];
     w.rowbuf = s_rowbuf[wv];
     w.rowbuf_len = FE_ROWBUF;
+    w.uw = FE_UW;
     {   // lane l caches the train-row extent of the wave's l-th user
         const int64_t row = w.ubase + lane;
         int64_t rb = 0;
@@ -762,6 +770,7 @@ struct F7Scales {
     int32_t n_flagged;                 // users the guard sent to the bf16x3 kernel
     int32_t pad;
     float s_u, s_v, S, S_inv;          // the power-of-two scales, their product and its inverse
+    float guard_inv;                   // S_inv * 2^ceil(log2 C): what the guard of a sweep over 64 C columns compares against
 };
 
 // ================================================================================================
@@ -847,19 +856,20 @@ struct F16x2 {
     static __device__ __forceinline__ void split(const float* v, float s, uint4 (&p)[PIECES]) { split2x8(v, s, p[0], p[1]); }
 };
 
-// largest |x| over whole rows of FE_D floats (rows picked by ids when given): a fixed grid strides over the (row, 16-byte
+// largest |x| over whole rows of D floats (rows picked by ids when given): a fixed grid strides over the (row, 16-byte
 // piece) pairs, one atomic per WORKGROUP (one per wavefront on a single address serialised: 0.29 / 0.75 ms for the two tables)
 constexpr int ABSMAX_BLOCKS = 1024;
+template <int D>
 __global__ __launch_bounds__(256) void absmax_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ ids,
                                                           int64_t n_rows, uint32_t* __restrict__ out_bits) {
     __shared__ uint32_t red[4];
-    const int64_t n = n_rows * (FE_D / 4);
+    const int64_t n = n_rows * (D / 4);
     uint32_t m = 0;
     for (int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; t < n; t += static_cast<int64_t>(gridDim.x) * 256) {
-        const int64_t r = t / (FE_D / 4);
-        const int q = static_cast<int>(t - r * (FE_D / 4));
+        const int64_t r = t / (D / 4);
+        const int q = static_cast<int>(t - r * (D / 4));
         const int64_t row = ids ? ids[r] : r;
-        const float4 v = reinterpret_cast<const float4*>(table + row * FE_D)[q];
+        const float4 v = reinterpret_cast<const float4*>(table + row * D)[q];
         const uint32_t a0 = __float_as_uint(v.x) & 0x7fffffffu, a1 = __float_as_uint(v.y) & 0x7fffffffu;
         const uint32_t a2 = __float_as_uint(v.z) & 0x7fffffffu, a3 = __float_as_uint(v.w) & 0x7fffffffu;
         m = max(m, max(max(a0, a1), max(a2, a3)));
@@ -884,12 +894,13 @@ __device__ __forceinline__ float f7_scale_of(uint32_t max_bits) {
     e = e < -40 ? -40 : (e > 40 ? 40 : e);
     return ldexpf(1.0f, e);
 }
-__global__ void f7_scales_kernel(F7Scales* sc) {
+__global__ void f7_scales_kernel(F7Scales* sc, float guard_width) {
     if (threadIdx.x == 0) {
         sc->s_u = f7_scale_of(sc->max_u_bits);
         sc->s_v = f7_scale_of(sc->max_v_bits);
         sc->S = sc->s_u * sc->s_v;
         sc->S_inv = 1.0f / sc->S;     // a power of two: exact
+        sc->guard_inv = sc->S_inv * guard_width;
         sc->n_flagged = 0;
     }
 }
@@ -1060,6 +1071,7 @@ __device__ __forceinline__ void split_sweep(const FusedArgs& a, const uint4* __r
     w.row_len = s_row_len[wv];
     w.rowbuf = s_rowbuf[wv];
     w.rowbuf_len = SPLIT_ROWBUF;
+    w.uw = FE_UW;
     {   // lane l caches the train-row extent of the wave's l-th user
         const int64_t row = w.ubase + lane;
         int64_t rb = 0;
@@ -1241,6 +1253,350 @@ __global__ __launch_bounds__(FE_WAVES * 64, 2) void fused_topk_kernel_v7(FusedAr
     split_sweep<F16x2, HAS_BIAS>(a, frags, bias_s, sc);
 }
 
+// ================================================================================================
+// The wide sweeps (rows of dim = 64 C floats, C = 2, 3, 4 SLICES of 64 columns; zero-padded by the caller): split_sweep_wide
+// <Arith, HAS_BIAS, G>, the same arithmetics, item-group step and candidate path as split_sweep, with user groups traded for
+// slices.  The 64-column kernels above are NOT instantiations of it: they stay the code (and the bits) they are.
+//   * A wavefront holds G = 4 / C user groups of 16 users (G = 2: 32 users, C = 2; G = 1: 16 users, C = 3 or 4 by a run-time
+//     slice count, so there are two templates per arithmetic and bias, eight kernels in all); a workgroup covers 64 G users.
+//     The user fragments bp[PIECES][G][4 / G][2] take the registers they take at 64 columns (64 / 96), a step is
+//     SLOTS x C x G MFMAs per wavefront (C = 3: three quarters of it), and an item group is C times larger: DMA bytes per
+//     matrix cycle are those of the 64-column kernels.  Holding 64 users per wavefront at C slices fits neither the
+//     registers (bf16x3, C = 4: 384) nor LDS.
+//   * An item group in fragment order is C x FRAGS 1 KB blocks, slice-major (slice x k-step x piece; split_items_wide_kernel),
+//     and the workgroup's ring holds SPLIT_RING = 3 of them at a fixed stride of (4 / G) x FRAGS KB: 24 / 36 KB (G = 2), 48 / 72 KB
+//     (G = 1) for f16x2 / bf16x3.  Block b of a group is brought by wavefront b mod 4 (up to C FRAGS / 4 rounded up: 2..6 DMAs);
+//     the group's 16 bias values travel with wavefront 3, which has the smallest share.
+//   * The ring is used one group later than in split_sweep, because a step reads its group's slices 1 .. C-1 from LDS while it
+//     runs (slice by slice, double-buffered in two sets of FRAGS quads: a pair of C FRAGS quads would be 128 VGPRs at C = 4):
+//     at step hs the slot of group hs is being read, hs + 1 has landed (its slice 0 is fetched during the last slice of hs) and
+//     hs + 2 is in flight into the slot of hs - 1.  So when a wavefront waits for its share of group hs + 1 at the top of
+//     step hs, that share is the ONLY DMA it has in flight, and the wait is vmcnt(0) by derivation, not by loosening: the counted
+//     waits of split_sweep exist because two groups are in flight there.  The group has had one whole step to land, and a
+//     step is C times as long as a 64-column one, i.e. the same two 64-column steps of lead at C = 2 and more beyond.
+//   * Bits: the seed (the bias, or -inf for rows beyond the catalogue) enters the first MFMA of slice 0 only; within a slice the
+//     order is T::SLOT's, and slices are added in ascending order, all into one accumulator chain.
+//   * Candidate path: lane l holds, per user group g < G, user 16 g + (l & 15) against items 4 (l >> 4) + i -- every lane holds a
+//     user in every group it has, users beyond B have threshold +inf and never reserve a slot.  The LDS arrays keep FE_UW
+//     entries per wavefront; entries >= 16 G stay 0 and never trigger a compaction.  The lists stay [user][cap] and a
+//     workgroup's users are 64 G consecutive rows, so the workspace of skr_eval_fused_workspace(B, top_k) (whole 64s) is enough:
+//     wavefronts beyond ceil(B / 64) * 64 hold no user and touch no scratch.
+// ================================================================================================
+template <class T>
+__global__ __launch_bounds__(256) void split_items_wide_kernel(const float* __restrict__ table, const float* __restrict__ bias,
+                                                               int n_items, int n_tiles, int nsl, const F7Scales* __restrict__ sc,
+                                                               uint4* __restrict__ frags, float* __restrict__ bias_s,
+                                                               const int32_t* __restrict__ n_rows) {
+    if (n_rows && *n_rows <= 0) return;
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;   // (group, slice, k-step, lane)
+    if (g >= static_cast<int64_t>(n_tiles) * 2 * nsl * 2 * 64) return;
+    float s_v = 1.0f;
+    if constexpr (T::SCALED) {
+        s_v = sc->s_v;
+        if (bias && g < static_cast<int64_t>(n_tiles) * FE_TI) bias_s[g] = (g < n_items ? bias[g] : 0.0f) * sc->S;
+    }
+    const int lane = static_cast<int>(g & 63), ks = static_cast<int>((g >> 6) & 1);
+    const int64_t gs = g >> 7;                       // group * nsl + slice
+    const int64_t G = gs / nsl;
+    const int c = static_cast<int>(gs - G * nsl);
+    int64_t item = G * SPLIT_GI + (lane & 15);
+    if (item >= n_items) item = n_items - 1;
+    const float4* src = reinterpret_cast<const float4*>(table + item * (static_cast<int64_t>(nsl) * FE_D) + c * FE_D + ks * 32 + 8 * (lane >> 4));
+    const float4 v0 = src[0], v1 = src[1];
+    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    uint4 p[T::PIECES];
+    T::split(v, s_v, p);
+    uint4* dst = frags + gs * (T::FRAGS * 64) + (ks * T::PIECES) * 64 + lane;
+#pragma unroll
+    for (int pc = 0; pc < T::PIECES; ++pc) dst[64 * pc] = p[pc];
+}
+
+template <int G>
+struct GroupTestsW {
+    bool any;
+    bool pass[G][4];        // [user group][accumulator register]
+    uint64_t mask[G][4];    // the tests' lane masks (BATCHED_RESERVE only)
+};
+template <class T, int G>
+__device__ __forceinline__ void group_test_w(GroupTestsW<G>& t, const f32x4 (&prv)[G], const float (&thr)[G], int g, int i) {
+    t.pass[g][i] = prv[g][i] > thr[g];
+    if constexpr (T::BATCHED_RESERVE) t.mask[g][i] = __builtin_amdgcn_ballot_w64(prv[g][i] > thr[g]);
+}
+
+// group_candidates for G user groups per wavefront (see there for the why of each form)
+template <class T, int G>
+__device__ __forceinline__ void group_candidates_w(const FusedArgs& a, const WaveCtx& w, const f32x4 (&acc)[G], const GroupTestsW<G>& t,
+                                                   int base, float (&thr)[G], float S, float S_inv) {
+    const int qd = w.lane >> 4, c16 = w.lane & 15;
+    if constexpr (T::BATCHED_RESERVE) {
+        unsigned pos[G][4];
+        const unsigned one = 1u;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const uint32_t cnt_addr = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_ptr_t)&w.cnt[16 * g + c16]));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                pos[g][i] = 0u;
+                uint64_t saved;
+                asm volatile("s_and_saveexec_b64 %1, %2\n\tds_add_rtn_u32 %0, %3, %4\n\ts_mov_b64 exec, %1"
+                             : "+v"(pos[g][i]), "=&s"(saved)
+                             : "s"(t.mask[g][i]), "v"(cnt_addr), "v"(one)
+                             : "memory");
+            }
+        }
+        // one wait for all reservations; every position is an operand of it
+        if constexpr (G == 2)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos[0][0]), "+v"(pos[0][1]), "+v"(pos[0][2]), "+v"(pos[0][3]),
+                         "+v"(pos[G - 1][0]), "+v"(pos[G - 1][1]), "+v"(pos[G - 1][2]), "+v"(pos[G - 1][3])
+                         :
+                         : "memory");
+        else
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos[0][0]), "+v"(pos[0][1]), "+v"(pos[0][2]), "+v"(pos[0][3]) : : "memory");
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            uint64_t* list = w.my_cand + static_cast<int64_t>(16 * g + c16) * a.cap;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (t.pass[g][i]) list[pos[g][i]] = skr::rank_key(T::SCALED ? acc[g][i] * S_inv : acc[g][i], base + 4 * qd + i);
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            int* cnt_p = &w.cnt[16 * g + c16];
+            uint64_t* list = w.my_cand + static_cast<int64_t>(16 * g + c16) * a.cap;
+            unsigned pos[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (t.pass[g][i]) pos[i] = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(cnt_p), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (t.pass[g][i]) list[pos[i]] = skr::rank_key(T::SCALED ? acc[g][i] * S_inv : acc[g][i], base + 4 * qd + i);   // pos < trigger + 16 <= cap
+        }
+    }
+    uint64_t need = __ballot(w.cnt[w.lane] > a.trigger);   // entries of lanes >= 16 G are 0
+    if (need) {
+        while (need) {
+            const int ul = __ffsll(static_cast<long long>(need)) - 1;
+            need &= need - 1;
+            float nt = compact_user(a, w, ul);
+            if constexpr (T::SCALED) nt *= S;   // -inf stays -inf
+            const int ug = ul >> 4;   // wave-uniform
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g == ug && c16 == (ul & 15)) thr[g] = nt;
+        }
+        if constexpr (!T::BATCHED_RESERVE) __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
+}
+
+template <class T, bool HAS_BIAS, int G>
+__device__ __forceinline__ void split_sweep_wide(const FusedArgs& a, int n_slices, const uint4* __restrict__ frags,
+                                                 const float* __restrict__ bias_s, const F7Scales* __restrict__ sc) {
+    constexpr int CMAX = 4 / G;                                // slices the kernel has room for
+    constexpr int UW = 16 * G;                                 // users per wavefront
+    constexpr int SLICE_U4 = T::FRAGS * 64;                    // uint4 per slice of an item group
+    constexpr int SLOT_U4 = CMAX * SLICE_U4;                   // ring stride
+    constexpr int SHARE = (CMAX * T::FRAGS + FE_WAVES - 1) / FE_WAVES;   // DMA blocks per wavefront and group, at most
+    static_assert(G == 1 || G == 2, "one or two user groups per wavefront");
+    __shared__ uint4 s_tile[SPLIT_RING * SLOT_U4];
+    __shared__ float4 s_bias[SPLIT_RING][16];                  // a GROUP's bias row per ring slot (16 items, written four times over)
+    __shared__ int s_cnt[FE_WAVES][FE_UW];
+    __shared__ int64_t s_row_beg[FE_WAVES][FE_UW];
+    __shared__ int s_row_len[FE_WAVES][FE_UW];
+    __shared__ int s_rowbuf[FE_WAVES][SPLIT_ROWBUF];
+    WaveCtx w;
+    w.lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = w.lane, c16 = w.lane & 15, qd = w.lane >> 4;
+    const int nsl = CMAX == 2 ? 2 : n_slices;                  // wave-uniform; 3 or 4 in the G = 1 kernels
+    const int dim = nsl * FE_D;                                // floats per row of both tables
+    w.ubase = (static_cast<int64_t>(blockIdx.x) * FE_WAVES + wv) * UW;
+    int nB = a.B;
+    auto user_of = [&](int64_t row) { return a.users[T::ROW_MAPPED ? src_row(a, row) : row]; };
+    if constexpr (T::ROW_MAPPED) {
+        nB = rows_of(a);
+        if (static_cast<int64_t>(blockIdx.x) * FE_WAVES * UW >= nB) return;   // the whole workgroup: nothing to do
+    }
+    w.cnt = s_cnt[wv];
+    w.cnt[lane] = 0;
+    w.my_cand = a.cand + w.ubase * a.cap;
+    w.row_beg = s_row_beg[wv];
+    w.row_len = s_row_len[wv];
+    w.rowbuf = s_rowbuf[wv];
+    w.rowbuf_len = SPLIT_ROWBUF;
+    w.uw = UW;
+    {
+        const int64_t row = w.ubase + lane;
+        int64_t rb = 0;
+        int len = 0;
+        if (a.train_rowptr && lane < UW && row < nB) {
+            const int u = user_of(row);
+            rb = a.train_rowptr[u];
+            len = static_cast<int>(a.train_rowptr[u + 1] - rb);
+        }
+        w.row_beg[lane] = rb;
+        w.row_len[lane] = len;
+    }
+    float s_u = 1.0f, S = 1.0f, S_inv = 1.0f;
+    if constexpr (T::SCALED) {
+        s_u = sc->s_u;
+        S = sc->S;
+        S_inv = sc->S_inv;
+    }
+    // user fragments: B[k = 8 qd + j][col c16] of user group g, slice c and k-step ks, one register quad per piece
+    uint4 bp[T::PIECES][G][CMAX][2];
+    float thr[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int64_t row = w.ubase + 16 * g + c16;
+        const bool ok = row < nB;
+        const int uid = user_of(ok ? row : (nB - 1));
+        thr[g] = (ok && a.ablate != 1) ? -INFINITY : INFINITY;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;
+                if (c < nsl) {   // the fourth slice of a 192-column row does not exist
+                    const float4* up = reinterpret_cast<const float4*>(a.user_table + static_cast<int64_t>(uid) * dim + c * FE_D + ks * 32 + 8 * qd);
+                    v0 = up[0];
+                    v1 = up[1];
+                }
+                const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                uint4 p[T::PIECES];
+                T::split(v, s_u, p);
+#pragma unroll
+                for (int pc = 0; pc < T::PIECES; ++pc) bp[pc][g][c][ks] = p[pc];
+            }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)   // retire the loads here (see the fp32 kernel: hidden DMA vs counted vmcnt)
+#pragma unroll
+                for (int pc = 0; pc < T::PIECES; ++pc)
+                    asm volatile("" : "+v"(bp[pc][g][c][ks].x), "+v"(bp[pc][g][c][ks].y), "+v"(bp[pc][g][c][ks].z), "+v"(bp[pc][g][c][ks].w));
+    const int n_tiles = (a.n_items + FE_TI - 1) / FE_TI;
+    const int n_half = 2 * n_tiles;
+    const int nblk = nsl * T::FRAGS;                // 1 KB blocks per item group
+    const uint32_t lt = lds_addr_of(&s_tile[0]);
+    const uint32_t lb0 = lds_addr_of(&s_bias[0][0]);
+    const uint32_t lane16 = static_cast<uint32_t>(lane) * 16u;
+    auto issue_group = [&](int hs, int slot) {      // group hs and its bias row -> ring slot
+        const char* sbase = reinterpret_cast<const char*>(frags) + static_cast<int64_t>(hs) * nblk * 1024;   // wave-uniform
+        const uint32_t dst = lt + static_cast<uint32_t>(slot) * (SLOT_U4 * 16);
+#pragma unroll
+        for (int j = 0; j < SHARE; ++j) {
+            const int b = j * FE_WAVES + wv;
+            if (b < nblk) glds_b128_s(lane16, sbase + b * 1024, dst + b * 1024);   // b < CMAX * FRAGS: inside the slot
+        }
+        if (HAS_BIAS && wv == 3) {
+            int bi = hs * SPLIT_GI + (lane & 15);
+            if constexpr (!T::SCALED) bi = bi < a.n_items ? bi : a.n_items - 1;    // (the scaled row is padded to whole tiles)
+            glds_b32((T::SCALED ? bias_s : a.item_bias) + bi, lb0 + static_cast<uint32_t>(slot) * 256u);
+        }
+    };
+    issue_group(0, 0);
+    issue_group(1, 1);                              // n_half >= 2 always
+    FE2_WAIT();
+    __syncthreads();
+    uint4 afA[T::FRAGS], afB[T::FRAGS];
+#pragma unroll
+    for (int i = 0; i < T::FRAGS; ++i) afA[i] = s_tile[i * 64 + lane];
+    f32x4 accA[G], accB[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) accB[g][i] = -INFINITY;   // "group -1": nothing passes
+    int slot = 0;                                   // ring slot of group hs
+    // One step = one item group hs.  Slice 0 is in X; slice c + 1 (behind the last slice: slice 0 of group hs + 1) is fetched
+    // into the other set while slice c's MFMAs run.  Behind a step of an odd slice count the next group's slice 0 is in Y.
+    auto step = [&](uint4 (&X)[T::FRAGS], uint4 (&Y)[T::FRAGS], int hs, f32x4 (&acc)[G], const f32x4 (&prv)[G])
+                    __attribute__((always_inline)) {
+        FE3_PIN();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // slice 0 has landed in registers
+        FE3_PIN();
+        const int nslot = slot == SPLIT_RING - 1 ? 0 : slot + 1;
+        const int islot = slot == 0 ? SPLIT_RING - 1 : slot - 1;
+        FE2_WAIT();                                 // my share of group hs + 1: the only DMA I have in flight (header)
+        __syncthreads();                            // ... and everybody's; and every wavefront is done reading group hs - 1
+        FE3_PIN();
+        if (hs + 2 < n_half) issue_group(hs + 2, islot);
+        f32x4 seed;
+        if (HAS_BIAS) {
+            const float4 b4 = s_bias[slot][qd];
+            seed[0] = b4.x; seed[1] = b4.y; seed[2] = b4.z; seed[3] = b4.w;
+        } else {
+            seed[0] = 0.0f; seed[1] = 0.0f; seed[2] = 0.0f; seed[3] = 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)                 // rows beyond the catalogue start from -inf and stay there (no branch: see split_sweep)
+            seed[i] = (hs * SPLIT_GI + 4 * qd + i >= a.n_items) ? -INFINITY : seed[i];
+        GroupTestsW<G> t = {};
+        FE3_PIN();
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            if (c < 3 || nsl > 3) {
+                const uint4 (&cur)[T::FRAGS] = (c & 1) ? Y : X;
+                uint4 (&nxt)[T::FRAGS] = (c & 1) ? X : Y;
+                const int noff = (c + 1 < nsl) ? slot * SLOT_U4 + (c + 1) * SLICE_U4 : nslot * SLOT_U4;   // scalar select
+#pragma unroll
+                for (int i = 0; i < T::FRAGS; ++i) nxt[i] = s_tile[noff + i * 64 + lane];
+#pragma unroll
+                for (int s = 0; s < T::SLOTS; ++s) {
+                    const int frag = T::SLOT[s][0], piece = T::SLOT[s][1];
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        acc[g] = T::mfma(cur[frag], bp[piece][g][c][frag / T::PIECES], (c == 0 && s == 0) ? seed : acc[g]);
+                        if (c == 0 && s * G + g < 4 * G) {   // the 4 G threshold tests of group hs - 1, one behind each of the first MFMAs
+                            group_test_w<T, G>(t, prv, thr, (s * G + g) >> 2, (s * G + g) & 3);
+                            FE3_PIN();
+                        }
+                    }
+                    FE3_PIN();
+                }
+            }
+        }
+        bool any = false;
+#pragma unroll
+        for (int g = 0; g < G; ++g) any |= (t.pass[g][0] | t.pass[g][1]) | (t.pass[g][2] | t.pass[g][3]);
+        t.any = any;
+        if (__any(t.any)) group_candidates_w<T, G>(a, w, prv, t, (hs - 1) * SPLIT_GI, thr, S, S_inv);
+        slot = nslot;
+    };
+    for (int t = 0; t < n_tiles; ++t) {
+        step(afA, afB, 2 * t, accA, accB);
+        if (CMAX == 4 && nsl == 3) step(afB, afA, 2 * t + 1, accB, accA);
+        else step(afA, afB, 2 * t + 1, accB, accA);
+    }
+    {
+        GroupTestsW<G> t = {};
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                group_test_w<T, G>(t, accB, thr, g, i);
+                t.any |= t.pass[g][i];
+            }
+        if (__any(t.any)) group_candidates_w<T, G>(a, w, accB, t, (n_half - 1) * SPLIT_GI, thr, S, S_inv);
+    }
+    __threadfence_block();
+    final_compactions(a, w);
+}
+
+template <bool HAS_BIAS, int G>
+__global__ __launch_bounds__(FE_WAVES * 64, 2) void fused_topk_wide_bf16x3(FusedArgs a, int n_slices, const uint4* __restrict__ frags) {
+    split_sweep_wide<Bf16x3, HAS_BIAS, G>(a, n_slices, frags, nullptr, nullptr);
+}
+template <bool HAS_BIAS, int G>
+__global__ __launch_bounds__(FE_WAVES * 64, 2) void fused_topk_wide_f16x2(FusedArgs a, int n_slices, const uint4* __restrict__ frags,
+                                                                          const float* __restrict__ bias_s,
+                                                                          const F7Scales* __restrict__ sc) {
+    split_sweep_wide<F16x2, HAS_BIAS, G>(a, n_slices, frags, bias_s, sc);
+}
+
 // list capacity per user.  Measured on MI355X (K = 10..100, 262 144 users): 512-entry lists with a
 // trigger of 480 were no faster than 256 / 224 once the mid-sweep compaction selects instead of sorting
 // (profiles/r01_eval_history.txt), so the smaller scratch footprint stays.
@@ -1272,6 +1628,7 @@ int grow(DeviceBuf& b, size_t need, hipStream_t st) {
 
 // the instantiation of a kernel template <bool HAS_BIAS> that a call with / without an item bias runs
 #define FE_PICK_BIAS(KERNEL, BIAS) ((BIAS) ? KERNEL<true> : KERNEL<false>)
+#define FE_PICK_BIAS_G(KERNEL, BIAS, G) ((BIAS) ? KERNEL<true, G> : KERNEL<false, G>)
 
 }  // namespace
 
@@ -1299,13 +1656,19 @@ int skr_eval_fused_topk(const float* d_user_table, const int32_t* d_users, int B
                         const int32_t* d_train_items, int top_k, int32_t* d_topk_ids, float* d_topk_scores, void* d_work,
                         size_t work_bytes, void* stream) {
     SKR_REQUIRE(d_user_table && d_users && d_item_table && d_topk_ids, "skr_eval_fused_topk: NULL argument");
-    SKR_REQUIRE(dim == FE_D, "skr_eval_fused_topk: dim must be 64 (got %d)", dim);
+    SKR_REQUIRE(dim == 64 || dim == 128 || dim == 192 || dim == 256,
+                "skr_eval_fused_topk: dim must be 64, 128, 192 or 256 (got %d); pad the rows with zeros", dim);
     SKR_REQUIRE(B >= 0 && n_items > 0, "skr_eval_fused_topk: bad shape");
     SKR_REQUIRE(top_k >= 1 && top_k <= SKR_MAX_TOPK, "top_k %d outside [1, %d]", top_k, SKR_MAX_TOPK);
     SKR_REQUIRE(top_k <= n_items, "top_k %d larger than the catalogue (%d items)", top_k, n_items);
     SKR_REQUIRE((d_train_rowptr == nullptr) == (d_train_items == nullptr), "train CSR: both pointers or neither");
     SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_user_table) | reinterpret_cast<uintptr_t>(d_item_table) |
                   reinterpret_cast<uintptr_t>(d_item_bias)) & 15) == 0, "tables must be 16-byte aligned");
+    {   // the FP32-MFMA kernel exists at 64 columns only; refused before any device call (the caller then takes the score-matrix route)
+        const char* m = getenv("SKR_FUSED_MODE");
+        SKR_REQUIRE(!(dim > FE_D && m && std::string(m) == "fp32"),
+                    "skr_eval_fused_topk: SKR_FUSED_MODE=fp32 is not built for dim %d (64 only); use f16x2 or bf16x3", dim);
+    }
     g_f7_scales = nullptr;             // set again below if this call runs the fp16x2 sweep
     if (B == 0) return SKR_OK;
     if (work_bytes < skr_eval_fused_workspace(B, top_k) || !d_work)
@@ -1324,7 +1687,12 @@ int skr_eval_fused_topk(const float* d_user_table, const int32_t* d_users, int B
     // SKR_FUSED_ABLATE=1 (timing experiment): every threshold starts at +inf, so the sweep is a pure GEMM and returns nothing
     static const int ablate = [] { const char* e = getenv("SKR_FUSED_ABLATE"); return e ? atoi(e) : 0; }();
     a.ablate = ablate == 1 ? 1 : 0;
-    const int64_t waves = (static_cast<int64_t>(B) + FE_UW - 1) / FE_UW;
+    // width: C slices of 64 columns; the wide sweeps hold 64 / C users per wavefront (C = 3 runs in the C = 4 kernel)
+    const int C = dim / FE_D;
+    const int wide_g = C == 2 ? 2 : 1;                       // user groups per wavefront of the wide kernel
+    const int uw = C == 1 ? FE_UW : 16 * wide_g;
+    const float guard_width = C == 1 ? 1.0f : C == 2 ? 2.0f : 4.0f;   // 2^ceil(log2 C): the guard's floor grows with the dot product's length
+    const int64_t waves = (static_cast<int64_t>(B) + uw - 1) / uw;
     const dim3 grid(static_cast<unsigned>((waves + FE_WAVES - 1) / FE_WAVES)), block(FE_WAVES * 64);
     hipStream_t st = skr::as_stream(stream);
     // arithmetic mode, read per call: "f16x2" (default: two fp16 pieces behind a guard, rejected rows through bf16x3),
@@ -1348,12 +1716,22 @@ int skr_eval_fused_topk(const float* d_user_table, const int32_t* d_users, int B
     }
     const int n_tiles = (n_items + FE_TI - 1) / FE_TI;
     const dim3 split_grid(static_cast<unsigned>((static_cast<int64_t>(n_tiles) * 256 + 255) / 256));
+    const dim3 wide_split_grid(static_cast<unsigned>(static_cast<int64_t>(n_tiles) * C));   // n_tiles * 2 groups * C slices * 128 threads
     // the bf16x3 sweep over the rows of `args` (a mode of its own, and the fall-back of f16x2's guard: then n_rows is the device's
     // count of flagged rows, and an empty list makes both launches return at once)
     auto bf16x3_sweep = [&](const FusedArgs& args, const int32_t* n_rows) -> int {
         static DeviceBuf frag;   // the split item table (38 MB at 100 k items)
-        if (int rc = grow(frag, static_cast<size_t>(n_tiles) * 2 * Bf16x3::FRAGS * 64 * sizeof(uint4), st)) return rc;
+        if (int rc = grow(frag, static_cast<size_t>(n_tiles) * 2 * C * Bf16x3::FRAGS * 64 * sizeof(uint4), st)) return rc;
         uint4* frags = reinterpret_cast<uint4*>(frag.p);
+        if (C > 1) {
+            hipLaunchKernelGGL(split_items_wide_kernel<Bf16x3>, wide_split_grid, dim3(256), 0, st, d_item_table, static_cast<const float*>(nullptr),
+                               n_items, n_tiles, C, static_cast<const F7Scales*>(nullptr), frags, static_cast<float*>(nullptr), n_rows);
+            SKR_LAUNCH_CHECK();
+            if (wide_g == 2) hipLaunchKernelGGL(FE_PICK_BIAS_G(fused_topk_wide_bf16x3, d_item_bias, 2), grid, block, 0, st, args, C, frags);
+            else hipLaunchKernelGGL(FE_PICK_BIAS_G(fused_topk_wide_bf16x3, d_item_bias, 1), grid, block, 0, st, args, C, frags);
+            SKR_LAUNCH_CHECK();
+            return SKR_OK;
+        }
         hipLaunchKernelGGL(split_items_kernel<Bf16x3>, split_grid, dim3(256), 0, st, d_item_table, static_cast<const float*>(nullptr),
                            n_items, n_tiles, static_cast<const F7Scales*>(nullptr), frags, static_cast<float*>(nullptr), n_rows);
         SKR_LAUNCH_CHECK();
@@ -1364,7 +1742,7 @@ int skr_eval_fused_topk(const float* d_user_table, const int32_t* d_users, int B
     if (mode == "bf16x3") return bf16x3_sweep(a, nullptr);
     // the fp16x2 sweep, its guard, and the bf16x3 sweep over the rows the guard flagged (the F16x2 traits' header)
     static DeviceBuf f7;       // [scales | fp16 fragments | scaled bias | flagged rows]
-    const size_t frag16_bytes = static_cast<size_t>(n_tiles) * 2 * F16x2::FRAGS * 64 * sizeof(uint4);
+    const size_t frag16_bytes = static_cast<size_t>(n_tiles) * 2 * C * F16x2::FRAGS * 64 * sizeof(uint4);
     const size_t bias_bytes = static_cast<size_t>(n_tiles) * FE_TI * sizeof(float);
     const size_t flag_bytes = (static_cast<size_t>(B) + 63) / 64 * 64 * sizeof(int32_t);
     if (int rc = grow(f7, 256 + frag16_bytes + bias_bytes + flag_bytes, st)) return rc;
@@ -1374,25 +1752,39 @@ int skr_eval_fused_topk(const float* d_user_table, const int32_t* d_users, int B
     float* bias_s = reinterpret_cast<float*>(f7.p + 256 + frag16_bytes);
     int32_t* flags = reinterpret_cast<int32_t*>(f7.p + 256 + frag16_bytes + bias_bytes);
     SKR_HIP(hipMemsetAsync(sc, 0, sizeof(F7Scales), st));
-    const int64_t it_thr = static_cast<int64_t>(n_items) * (FE_D / 4), us_thr = static_cast<int64_t>(B) * (FE_D / 4);
-    hipLaunchKernelGGL(absmax_rows_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((it_thr + 255) / 256, ABSMAX_BLOCKS))), dim3(256), 0, st, d_item_table,
+    const int64_t it_thr = static_cast<int64_t>(n_items) * (dim / 4), us_thr = static_cast<int64_t>(B) * (dim / 4);
+    const dim3 it_grid(static_cast<unsigned>(std::min<int64_t>((it_thr + 255) / 256, ABSMAX_BLOCKS)));
+    const dim3 us_grid(static_cast<unsigned>(std::min<int64_t>((us_thr + 255) / 256, ABSMAX_BLOCKS)));
+    auto absmax_of = [&](int d) { return d == 64 ? absmax_rows_kernel<64> : d == 128 ? absmax_rows_kernel<128> : d == 192 ? absmax_rows_kernel<192> : absmax_rows_kernel<256>; };
+    hipLaunchKernelGGL(absmax_of(dim), it_grid, dim3(256), 0, st, d_item_table,
                        static_cast<const int32_t*>(nullptr), static_cast<int64_t>(n_items), &sc->max_v_bits);
-    hipLaunchKernelGGL(absmax_rows_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((us_thr + 255) / 256, ABSMAX_BLOCKS))), dim3(256), 0, st, d_user_table,
+    hipLaunchKernelGGL(absmax_of(dim), us_grid, dim3(256), 0, st, d_user_table,
                        d_users, static_cast<int64_t>(B), &sc->max_u_bits);
-    hipLaunchKernelGGL(f7_scales_kernel, dim3(1), dim3(64), 0, st, sc);
-    hipLaunchKernelGGL(split_items_kernel<F16x2>, split_grid, dim3(256), 0, st, d_item_table, d_item_bias, n_items, n_tiles,
-                       static_cast<const F7Scales*>(sc), frag16, bias_s, static_cast<const int32_t*>(nullptr));
+    hipLaunchKernelGGL(f7_scales_kernel, dim3(1), dim3(64), 0, st, sc, guard_width);
+    if (C == 1)
+        hipLaunchKernelGGL(split_items_kernel<F16x2>, split_grid, dim3(256), 0, st, d_item_table, d_item_bias, n_items, n_tiles,
+                           static_cast<const F7Scales*>(sc), frag16, bias_s, static_cast<const int32_t*>(nullptr));
+    else
+        hipLaunchKernelGGL(split_items_wide_kernel<F16x2>, wide_split_grid, dim3(256), 0, st, d_item_table, d_item_bias, n_items, n_tiles, C,
+                           static_cast<const F7Scales*>(sc), frag16, bias_s, static_cast<const int32_t*>(nullptr));
     SKR_LAUNCH_CHECK();
     FusedArgs a7 = a;
     // SKR_F7_GUARD=0 (diagnosis only: tests/test_gpu_eval.py probes the kernel's own error floor with it) accepts every row
     static const bool guard = [] { const char* e = getenv("SKR_F7_GUARD"); return !(e && atoi(e) == 0); }();
     if (guard) {
-        a7.guard_s_inv = &sc->S_inv;
+        a7.guard_s_inv = C == 1 ? &sc->S_inv : &sc->guard_inv;
         a7.flag_list = flags;
         a7.flag_count = &sc->n_flagged;
     }
-    hipLaunchKernelGGL(FE_PICK_BIAS(fused_topk_kernel_v7, d_item_bias), grid, block, 0, st, a7, static_cast<const uint4*>(frag16),
-                       static_cast<const float*>(bias_s), static_cast<const F7Scales*>(sc));
+    if (C == 1)
+        hipLaunchKernelGGL(FE_PICK_BIAS(fused_topk_kernel_v7, d_item_bias), grid, block, 0, st, a7, static_cast<const uint4*>(frag16),
+                           static_cast<const float*>(bias_s), static_cast<const F7Scales*>(sc));
+    else if (wide_g == 2)
+        hipLaunchKernelGGL(FE_PICK_BIAS_G(fused_topk_wide_f16x2, d_item_bias, 2), grid, block, 0, st, a7, C, static_cast<const uint4*>(frag16),
+                           static_cast<const float*>(bias_s), static_cast<const F7Scales*>(sc));
+    else
+        hipLaunchKernelGGL(FE_PICK_BIAS_G(fused_topk_wide_f16x2, d_item_bias, 1), grid, block, 0, st, a7, C, static_cast<const uint4*>(frag16),
+                           static_cast<const float*>(bias_s), static_cast<const F7Scales*>(sc));
     SKR_LAUNCH_CHECK();
     FusedArgs a6 = a;
     a6.row_map = flags;

@@ -17,8 +17,9 @@ to torch's draws in law only.  ``keep_in`` (uint8 [instances of the coming steps
 order, consumed step by step) replays recorded flags; ``keep_out = []`` collects the flags every step used.
 
 Scoring collapses to one query row per user, x_u = [z_u, p_u] in eval mode from the user's last seq_L training items, with
-y = <x_u, W2[t]> + b2[t]: the rows are computed once per evaluation (``skr_caser_queries``) and ranked through the dense
-score rows of ``skr_score_matrix`` at 128 columns (the fused top-K evaluator ranks 64).
+y = <x_u, W2[t]> + b2[t]: the rows are computed once per evaluation (``skr_caser_queries``) and ranked by the fused
+top-K evaluator at 128 columns (``predict_factors``); ``score_rows`` stays as the dense hook (``skr_score_matrix``), which
+the evaluator takes under ``SKR_FUSED_MODE=fp32`` or when K leaves too few unmasked items.
 
 Limits: embed_size <= 64 (zero-padded to 64), 1 <= seq_L <= 8, 1 <= seq_T <= 16, 1 <= nv <= 8, 1 <= nh <= 32,
 batch_size <= 2048, one GPU.

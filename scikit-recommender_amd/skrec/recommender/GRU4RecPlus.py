@@ -520,7 +520,7 @@ class GRU4RecPlus(AbstractRecommender):
 
     def predict_factors(self):
         """fused evaluator: a strictly increasing final activation does not change the ranking"""
-        if self.config.final_act == "relu" or self.config.layers[-1] != 64:
+        if self.config.final_act == "relu" or self.config.layers[-1] not in (64, 128, 192, 256):
             return None
         return self.cur_user_embeddings, self.net.E_out, self.net.b_out
 

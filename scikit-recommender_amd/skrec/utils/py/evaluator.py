@@ -4,9 +4,11 @@ Same constructor, same ``evaluate(model, test_users=None) -> MetricReport``, sam
 column order.  Three device paths, all through libskrec_hip.so:
 
 * **fused** -- taken when the model exposes ``predict_factors() -> (user_table, item_table, bias|None)``
-  (fp32 device tensors, 64 columns): ``skr_eval_fused_topk`` scores every test user against the whole
-  catalogue on FP32 MFMA, masks train items and keeps the top-K without ever forming the [B, I]
-  score matrix; ``skr_rank_metrics`` turns the lists into metric rows.
+  (fp32 device tensors of the same width, 64, 128, 192 or 256 columns, narrower rows zero-padded by the model):
+  ``skr_eval_fused_topk`` scores every test user against the whole catalogue on the matrix cores, masks train
+  items and keeps the top-K without ever forming the [B, I] score matrix; ``skr_rank_metrics`` turns the lists
+  into metric rows.  ``fused_route`` is the routing decision; ``SKR_FUSED_MODE=fp32`` exists at 64 columns only,
+  wider tables then take the score-matrix route.
 * **device scores** -- taken when the model exposes ``score_rows(d_users, out)`` (FPMC, TransRec): the model
   writes dense fp32 score rows of a chunk of users into a device buffer of about 256 MB, which is then masked and
   ranked in place by the generic path's tail.
@@ -19,6 +21,7 @@ Up to ``_HOST_MEAN_MAX`` users we do exactly that on the (bit-identical) rows; b
 summed in fp64 on the device, which is what the 1e-5 parity at 1 M users is defined against.
 """
 import itertools
+import os
 from collections import OrderedDict
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -26,7 +29,23 @@ import numpy as np
 
 from ... import _hip
 
-__all__ = ["MetricReport", "RankingEvaluator", "EarlyStopping"]
+__all__ = ["MetricReport", "RankingEvaluator", "EarlyStopping", "fused_route"]
+
+FUSED_WIDTHS = (64, 128, 192, 256)   # row widths (floats) of skr_eval_fused_topk
+_FUSED_MODES = ("f16x2", "bf16x3", "fp32")
+
+
+def fused_route(user_cols: int, item_cols: int, n_items: int, max_train: int, K: int, mode: Optional[str] = None) -> bool:
+    """Whether factor tables of these column counts are ranked by ``skr_eval_fused_topk`` (else: the score-matrix
+    route).  ``mode`` is the value of ``SKR_FUSED_MODE`` (None or "": the default, f16x2).  Pure: no device, no library."""
+    mode = mode or "f16x2"
+    if user_cols != item_cols or item_cols not in FUSED_WIDTHS:
+        return False
+    if not (n_items - max_train >= K and K <= _hip.SKR_MAX_TOPK):
+        return False
+    if mode == "fp32" and item_cols > 64:     # the FP32-MFMA kernel is built for 64 columns only
+        return False
+    return True
 
 _HOST_MEAN_MAX = 1 << 18
 _FUSED_CHUNK = 1 << 18     # users per fused launch (512 MB of candidate scratch): 4 workgroups per CU
@@ -200,8 +219,8 @@ class RankingEvaluator(object):
             du = d_users[sel].contiguous()
             sc = torch.empty((du.numel(), n_items), dtype=torch.float32, device=ids.device)
             L = _hip.lib()
-            _hip.check(L.skr_score_matrix(_hip.ptr(ut), _hip.ptr(du), du.numel(), _hip.ptr(it), _hip.ptr(bias), n_items, 64,
-                                          _hip.ptr(sc), n_items, _hip.stream()))
+            _hip.check(L.skr_score_matrix(_hip.ptr(ut), _hip.ptr(du), du.numel(), _hip.ptr(it), _hip.ptr(bias), n_items,
+                                          int(it.shape[1]), _hip.ptr(sc), n_items, _hip.stream()))
             _hip.check(L.skr_mask_train(_hip.ptr(sc), du.numel(), n_items, n_items, _hip.ptr(du), _hip.ptr(st["tr_ptr"]),
                                         _hip.ptr(st["tr_items"]), _hip.stream()))
             fixed = torch.empty((du.numel(), K), dtype=torch.int32, device=ids.device)
@@ -242,7 +261,8 @@ class RankingEvaluator(object):
         if factors is not None:
             ut, it, bias = factors
             n_items = int(it.shape[0])
-            fused_ok = (it.shape[1] == 64 and ut.shape[1] == 64 and n_items - st["max_train"] >= K and K <= _hip.SKR_MAX_TOPK)
+            width = int(it.shape[1])
+            fused_ok = fused_route(int(ut.shape[1]), width, n_items, st["max_train"], K, os.environ.get("SKR_FUSED_MODE"))
         if factors is not None and fused_ok:
             # pass 1: top-K lists of every user, chunk after chunk without touching the host.  One more entry than needed
             # is asked for where possible (Kq = K + 1): with the (K+1)-th score in hand, a tie that exists ONLY between the
@@ -256,7 +276,7 @@ class RankingEvaluator(object):
             for s in range(0, n, _FUSED_CHUNK):
                 b = min(_FUSED_CHUNK, n - s)
                 _hip.check(_hip.lib().skr_eval_fused_topk(
-                    _hip.ptr(ut), _hip.ptr(d_users[s:s + b]), b, _hip.ptr(it), _hip.ptr(bias), n_items, 64,
+                    _hip.ptr(ut), _hip.ptr(d_users[s:s + b]), b, _hip.ptr(it), _hip.ptr(bias), n_items, width,
                     _hip.ptr(st["tr_ptr"]), _hip.ptr(st["tr_items"]), Kq, _hip.ptr(ids_q[s:s + b]), _hip.ptr(top_sc[s:s + b]),
                     _hip.ptr(work), work.numel(), _hip.stream()))
             ids = ids_q if Kq == K else ids_q[:, :K].contiguous()

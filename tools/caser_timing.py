@@ -11,8 +11,10 @@ reference's defaults (seq_L 5, seq_T 3, nv 4, nh 16, dropout 0.5), device draws.
 Reported, as one JSON document: ms per training step with one dense skr_adam_step_wd per step and with the temporally
 blocked Adam; the step's launch groups one by one (skr_caser_step_timed), the two MFMA products (the horizontal filters'
 [n L, 64] x [64, rows] and fc1's [n, Fp] x [Fp, 64]) as a fraction of the 157.3 TF fp32 matrix peak -- of the launch that
-holds them, which also gathers, pools and writes; skr_caser_queries over all users; evaluation users/s through the dense
-score rows at 128 columns, and HGN's fused 64-column evaluation on the same data for comparison.
+holds them, which also gathers, pools and writes; skr_caser_queries over all users; evaluation users/s through the fused
+top-K evaluator at 128 columns (the route RankingEvaluator takes), the same users through the dense score rows
+(skr_score_matrix at 128 columns, behind a wrapper that exposes score_rows only: the route taken before the evaluator
+ranked wide rows) and HGN's fused 64-column evaluation on the same data, all in one session.
 
 Beside it, in the same session: the reference's step written with torch-ROCm ops (embedding lookups, conv2d, relu,
 max_pool1d, dropout, linear, baddbmm, binary_cross_entropy_with_logits, backward, torch.optim.Adam(weight_decay) over every
@@ -137,7 +139,7 @@ def main():
     res["speedup_vs_torch"] = round(res["torch_step_ms"]["median"] / min(res["step_ms_dense"]["median"], res["step_ms_blocked"]["median"]), 2)
     del ref, bt
     torch.cuda.empty_cache()
-    # query rows of all users, and the evaluation through the dense score rows
+    # query rows of all users, the fused evaluation at 128 columns and the dense score rows of the same users
     te_ptr = torch.arange(nU + 1, dtype=torch.int64, device=dev)
     counts = ds["rowptr"][1:] - ds["rowptr"][:-1]
     ev = RankingEvaluator({0: np.array([0])}, {0: np.array([1])}, metric=["Precision", "Recall", "NDCG"], top_k=(10, 20))
@@ -155,7 +157,21 @@ def main():
     res["eval_users"] = n_eval
     res["eval_ms"] = ms
     res["eval_users_per_s"] = round(n_eval / (ms["median"] * 1e-3))
-    del m
+
+    class ScoreRowsOnly(object):                     # the dense score-row route of the same model and users
+        num_items = m.num_items
+
+        def predict(self, users):
+            raise NotImplementedError
+
+        def score_rows(self, d_users, out):
+            return m.score_rows(d_users, out)
+    dense = ScoreRowsOnly()
+    ev.per_user_rows(dense, users)
+    ms = _spread([_time(lambda: ev.per_user_rows(dense, users)) for _ in range(args.repeats)])
+    res["eval_dense_ms"] = ms
+    res["eval_dense_users_per_s"] = round(n_eval / (ms["median"] * 1e-3))
+    del m, dense
     torch.cuda.empty_cache()
     # HGN's fused 64-column evaluation on the same data, same session
     h = HGN.detached(nU, nI, dict(lr=1e-3, reg=1e-3, seq_L=L, seq_T=T, embed_size=e, batch_size=b), win_host)
