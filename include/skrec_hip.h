@@ -482,6 +482,31 @@ int skr_adam_block_cold(float* d_p, float* d_m, float* d_v, int64_t n, float lr,
 int skr_adam_block_hot(float* d_p, float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                        float eps, int64_t step_t0, int64_t step_t, const int32_t* d_ids, int64_t n_ids, int64_t offset_floats,
                        int stride_floats, int32_t* d_claim, void* stream);
+/* skr_adam_block_cold with a state word per row that carries what one pass established into the next (torch's plain
+ * arithmetic only; results are those of skr_adam_block_cold, bit for bit).
+ *   d_rest    int32[(n + 63) / 64], zero-initialised by the caller and from then on written by these calls only.  A cold
+ *             row's word is (pass_id << 2) | state, written for EVERY cold row of EVERY pass; rows tagged hot are skipped,
+ *             so their words go stale by themselves: nothing ever clears a word.
+ *   pass_id   1 <= pass_id < 2^29.  A row's recorded state is trusted only if its word carries pass_id - 1.
+ *             pass_id = previous + 1 is the caller's PROMISE that, since the previous call on these buffers, (a) the rows
+ *             that call left cold have received nothing but zero-gradient Adam updates (in effect: nothing wrote them),
+ *             (b) lr, beta1, beta2 and eps are that call's, and (c) step_t0 is that call's step_t0 + k.  Any other
+ *             pass_id (use previous + 2) means "trust nothing": every row is examined from scratch.
+ *   states    0 unknown: handled as by skr_adam_block_cold.
+ *             1 quiet: when p was last read, every lane had v >= +0 and not NaN, |p| >= 2^-60 and
+ *               |nss * m| < 2^-28 * |p| * eps; under the promise that stays true (|m| and torch's |nss| only fall), so the
+ *               row is at rest again: only m and v are loaded, decayed and stored.
+ *             2 zero: additionally (or with eps > 0 and no NaN in p) every lane of m and v is +0: nothing is loaded.
+ *             No state is set with eps == 0 or with lr / betas outside the at-rest test's range; the tail block
+ *             (n % 64 != 0) has no word.
+ * With SKR_COLD_STATS=1, skr_cold_rest_census returns h_counts2 = {rows trusted as quiet, rows trusted as zero} (they are
+ * also counted as "at rest" by skr_cold_pass_census); either census function's reset clears both.  The variable is read
+ * at the first cold pass and again at every call of skr_cold_rest_census, so a process can switch the census on and off
+ * between passes.  Synchronises the device.  (Measurement hook.) */
+int skr_adam_block_cold_rest(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                             int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, int32_t* d_rest, int32_t pass_id,
+                             void* stream);
+int skr_cold_rest_census(uint64_t* h_counts2, int reset);
 /* The same three entry points with tf.train.AdamOptimizer's arithmetic (GRU4RecPlus.py:192): p -= lr_t * m / (sqrt(v) + eps)
  * with lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) -- the second bias correction sits in the step size, eps is added to
  * the raw sqrt(v).  |lr_t| falls and then rises again with t, so the at-rest test of a run of zero-gradient updates uses

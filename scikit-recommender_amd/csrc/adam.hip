@@ -388,10 +388,36 @@ __global__ __launch_bounds__(256) void selftest_step_chain_kernel(uint64_t n_gro
 // hence |fl(n/d)| < 2^-27 |p| < spacing(p)/4 and p is unchanged, bit for bit, by each of the k updates.  m and v still get
 // their k decays in the arithmetic of adam_elem (v*b2 + (c2*0)*0 == v*b2 because v*b2 carries a + sign).  The thresholds
 // are zero (tests off) unless 0 < beta1, beta2 < 1, lr > 0, eps >= 0.  Blocks not at rest take adam_elem as before.
-template <int U>
-__global__ __launch_bounds__(256) void adam_cold_rows_kernel(float* __restrict__ p, float* __restrict__ m,
+//
+// REST (skr_adam_block_cold_rest): a word per row carries what an earlier pass established into the next one, so that a row
+// whose answer is known is not read again to find it out.  word[b] = (pass_id << 2) | state, written by lane 0 for EVERY cold
+// row of EVERY pass; a pass c trusts a word only when it carries c - 1 (a row that was hot in between was skipped by that
+// pass: its word is stale and the row is examined from scratch -- nothing ever clears a word).  The caller promises for
+// pass_id = previous + 1 that the rows the previous pass left cold have seen nothing but zero-gradient updates since, and
+// that lr, betas and eps are the previous pass's and step_t0 is where it ended.  States:
+//   1 QUIET  at the pass that read p every lane passed the sign / NaN test on v, |p| >= 2^-60 and the eps alternative
+//            |nss[0]*m| < 2^-28 * |p| * eps.  That test stays true from pass to pass: p is fixed, |m| only decays (fl is
+//            monotone: |fl(m + fl(c1 * -m))| <= |m|), torch's |nss| = lr / (1 - beta1^t) only shrinks with t, and v keeps
+//            its sign.  So the pass would find the row at rest again -- without reading p: only m and v are loaded, decayed
+//            and stored.  (The v alternative is NOT carried over: v decays, and with it the bound.)
+//   2 ZERO   every lane of m and v is +0 (bits), and the row is quiet or (eps > 0 and no lane of p is NaN).  Then a
+//            zero-gradient update is m = +0 + c1 * (+0 - +0) = +0, v = +0 * b2 + (c2 * 0) * 0 = +0, q = (nss * +0) / (+0 / bc2
+//            + eps) = -0 / eps = -0 and p + (-0) = p for every p that is not NaN, +-0 and +-inf included: nothing changes,
+//            nothing is loaded.  (|p| < 2^-60 is allowed here: the zero-initialised bias rows.)
+// No state is set while the thresholds are off (rest_eps == 0: eps == 0, eps * 2^-28 underflows, or lr / betas out of range).
+// The tail (n not a multiple of 64) has no word.  Census: stats[4] / stats[5] count the rows trusted as quiet / as zero.
+__device__ __forceinline__ bool lane_quiet(float pp, float mm, float vv, const AdamBlockArgs& a) {   // lane_at_rest, eps alternative only
+    const float ap = fabsf(pp), n0 = a.nss_bound[0] * fabsf(mm);
+    return __float_as_uint(vv) <= 0x7f800000u && ap >= 0x1p-60f && n0 < ap * a.rest_eps;
+}
+
+// (at most 96 SGPRs, 8 wavefronts' worth per SIMD: the pass shares its CUs with the step and planning launches, whose workgroups
+//  must find registers beside six workgroups of this kernel -- with the state words' scalars it would otherwise take 106)
+template <int U, bool REST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void adam_cold_rows_kernel(float* __restrict__ p, float* __restrict__ m,
                                                              float* __restrict__ v, int64_t n, AdamBlockArgs a,
-                                                             const int32_t* __restrict__ tag, int32_t hot_value) {
+                                                             const int32_t* __restrict__ tag, int32_t hot_value,
+                                                             int32_t* __restrict__ word, int32_t pass_id) {
     const int lane = threadIdx.x & 63;
     const int64_t nb = n >> 6;
     const int64_t n_waves = static_cast<int64_t>(gridDim.x) * 4;
@@ -422,9 +448,39 @@ __global__ __launch_bounds__(256) void adam_cold_rows_kernel(float* __restrict__
     for (int64_t b0 = wave0; b0 < nb; b0 += n_waves * U) {
         float pp[U], mm[U], vv[U];
         bool cold[U];
+        int trust[U];      // REST: what the previous pass left in the row's word, if it is that pass's (0: nothing)
+        // REST: lane u fetches row u's tag and word -- the U rows' tags and words in ONE round trip -- and the rows read them
+        // from its registers; then only the loads a row's state needs
+        int32_t tg_l = hot_value;
+        uint32_t w_l = 0;
+        if (REST && lane < U) {
+            const int64_t b = b0 + lane * n_waves;
+            if (b < nb) {
+                tg_l = tag[b];
+                w_l = static_cast<uint32_t>(word[b]);
+            }
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t b = b0 + u * n_waves;
+            trust[u] = 0;
+            if (REST) {
+                const int32_t tg = __builtin_amdgcn_readlane(tg_l, u);
+                const uint32_t w = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(w_l), u));
+                cold[u] = tg != hot_value;
+                if (cold[u] && a.rest_eps > 0.0f && (w >> 2) == static_cast<uint32_t>(pass_id - 1) && (w & 3u) != 3u)
+                    trust[u] = static_cast<int>(w & 3u);
+                pp[u] = 1.0f, mm[u] = 0.0f, vv[u] = 0.0f;
+                if (cold[u]) {
+                    const int64_t i = (b << 6) + lane;
+                    if (trust[u] == 0) pp[u] = __builtin_nontemporal_load(&p[i]);
+                    if (trust[u] != 2) {
+                        mm[u] = __builtin_nontemporal_load(&m[i]);
+                        vv[u] = __builtin_nontemporal_load(&v[i]);
+                    }
+                }
+                continue;
+            }
             cold[u] = b < nb && tag[b] != hot_value;
             if (cold[u]) {
                 const int64_t i = (b << 6) + lane;
@@ -439,8 +495,30 @@ __global__ __launch_bounds__(256) void adam_cold_rows_kernel(float* __restrict__
         // (never touched) has nothing to decay.
         bool rest[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            rest[u] = cold[u] && __builtin_amdgcn_ballot_w64(!lane_at_rest(pp[u], mm[u], vv[u], a.nss_bound[0], a)) == 0;
+        for (int u = 0; u < U; ++u) {
+            if (REST && trust[u] != 0) {
+                // known to be at rest (a trusted ZERO row holds m = v = +0 here: nothing to decay, nothing to store)
+                rest[u] = true;
+                if (a.stats && lane == 0) atomicAdd(&a.stats[3 + trust[u]], 1ull);
+            } else {
+                rest[u] = cold[u] && __builtin_amdgcn_ballot_w64(!lane_at_rest(pp[u], mm[u], vv[u], a.nss_bound[0], a)) == 0;
+            }
+            if (REST && cold[u]) {
+                // the row's state for the next pass, from the values this pass starts from (zero moments stay zero)
+                int state = trust[u];
+                if (state != 2 && a.rest_eps > 0.0f) {
+                    const bool zero = __builtin_amdgcn_ballot_w64((__float_as_uint(mm[u]) | __float_as_uint(vv[u])) != 0) == 0;
+                    if (state == 1) {
+                        state = zero ? 2 : 1;
+                    } else {
+                        const bool quiet = __builtin_amdgcn_ballot_w64(!lane_quiet(pp[u], mm[u], vv[u], a)) == 0;
+                        const bool p_ok = quiet || __builtin_amdgcn_ballot_w64(pp[u] != pp[u]) == 0;
+                        state = (zero && p_ok) ? 2 : (quiet ? 1 : 0);
+                    }
+                }
+                if (lane == 0) word[b0 + u * n_waves] = static_cast<int32_t>((static_cast<uint32_t>(pass_id) << 2) | static_cast<uint32_t>(state));
+            }
+        }
         auto store_rest = [&](int64_t i, float m0, float v0, float m1, float v1) {
             if (__builtin_amdgcn_ballot_w64(__float_as_uint(m1) != __float_as_uint(m0)) != 0) __builtin_nontemporal_store(m1, &m[i]);
             if (__builtin_amdgcn_ballot_w64(__float_as_uint(v1) != __float_as_uint(v0)) != 0) __builtin_nontemporal_store(v1, &v[i]);
@@ -469,6 +547,7 @@ __global__ __launch_bounds__(256) void adam_cold_rows_kernel(float* __restrict__
             const int64_t i = ((b0 + u * n_waves) << 6) + lane;
             if (rest[u]) {
                 if (a.stats && lane == 0) atomicAdd(&a.stats[0], 1ull);
+                if (REST && trust[u] == 2) continue;
                 float m1 = mm[u], v1 = vv[u];
                 for (int s = 0; s < a.k; ++s) {
                     m1 = m1 + a.one_minus_b1 * (0.0f - m1);
@@ -589,18 +668,26 @@ __global__ __launch_bounds__(256) void adam_hot_kernel(float* __restrict__ p, fl
 
 }  // namespace
 
-// SKR_COLD_STATS=1: a device census of how the cold passes sorted their blocks (read with skr_cold_pass_census)
-unsigned long long* skr::cold_stats_buffer() {
-    static unsigned long long* buf = [] {
-        unsigned long long* p = nullptr;
+// SKR_COLD_STATS=1: a device census of how the cold passes sorted their blocks (read with skr_cold_pass_census /
+// skr_cold_rest_census): [0..2] at rest / ordinary / general, [4] / [5] rows trusted as quiet / as zero ([3], [6], [7] unused)
+static constexpr int COLD_COUNTERS = 8;
+// The environment is read at the first launch and again whenever skr_cold_rest_census is called (reread), so a process can
+// switch the census on and off between launches (plain function-static state, as fused_stats_buffer below).
+unsigned long long* skr::cold_stats_buffer(bool reread) {
+    static unsigned long long* buf = nullptr;
+    static bool on = false, read = false;
+    if (!read || reread) {
+        read = true;
         const char* e = getenv("SKR_COLD_STATS");
-        if (e && atoi(e) == 1 && hipMalloc(&p, 4 * sizeof(unsigned long long)) == hipSuccess) {
-            (void)hipMemset(p, 0, 4 * sizeof(unsigned long long));
-            return p;
+        on = e && atoi(e) == 1;
+        if (on && !buf) {
+            if (hipMalloc(&buf, COLD_COUNTERS * sizeof(unsigned long long)) == hipSuccess)
+                (void)hipMemset(buf, 0, COLD_COUNTERS * sizeof(unsigned long long));
+            else
+                buf = nullptr;
         }
-        return static_cast<unsigned long long*>(nullptr);
-    }();
-    return buf;
+    }
+    return on ? buf : nullptr;
 }
 
 // SKR_FUSED_STATS=1: a device census of how the fused BPR step's lazily advanced rows were evaluated.  The
@@ -692,11 +779,25 @@ int skr_cold_pass_census(uint64_t* h_counts3, int reset) {
     unsigned long long* buf = cold_stats_buffer();
     h_counts3[0] = h_counts3[1] = h_counts3[2] = 0;
     if (!buf) return SKR_OK;
-    unsigned long long h[4];
+    unsigned long long h[COLD_COUNTERS];
     SKR_HIP(hipDeviceSynchronize());
     SKR_HIP(hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost));
     if (reset) SKR_HIP(hipMemset(buf, 0, sizeof(h)));
     for (int i = 0; i < 3; ++i) h_counts3[i] = h[i];
+    return SKR_OK;
+}
+
+int skr_cold_rest_census(uint64_t* h_counts2, int reset) {
+    SKR_REQUIRE(h_counts2, "skr_cold_rest_census: NULL argument");
+    unsigned long long* buf = cold_stats_buffer(true);
+    h_counts2[0] = h_counts2[1] = 0;
+    if (!buf) return SKR_OK;
+    unsigned long long h[COLD_COUNTERS];
+    SKR_HIP(hipDeviceSynchronize());
+    SKR_HIP(hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) SKR_HIP(hipMemset(buf, 0, sizeof(h)));
+    h_counts2[0] = h[4];
+    h_counts2[1] = h[5];
     return SKR_OK;
 }
 
@@ -716,7 +817,7 @@ int skr_fused_census(uint64_t* h_counts, int n_counts, int reset) {
 
 static int adam_block_cold_impl(const char* who, float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                                 float eps, int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, bool tf, const float* wd,
-                                void* stream) {
+                                void* stream, int32_t* d_rest = nullptr, int32_t pass_id = 0) {
     SKR_REQUIRE(d_p && d_m && d_v && d_tag, "%s: NULL argument", who);
     SKR_REQUIRE(n >= 0 && step_t0 >= 0 && k >= 1 && k <= AB_KMAX, "%s: need 1 <= k <= %d", who, AB_KMAX);
     SKR_REQUIRE(((reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_m) | reinterpret_cast<uintptr_t>(d_v)) & 15) == 0,
@@ -740,6 +841,7 @@ static int adam_block_cold_impl(const char* who, float* d_p, float* d_m, float* 
     }
     static const int bpc = [] { const char* e = getenv("SKR_COLD_BPC"); const int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 8 ? 8 : v); }();   // workgroups per CU.  The pass runs beside the k-step block's small launches: round 2 settled on 4 (960 timed steps: 24.9 / 31.3 / 30.3 / 28.1 M interactions/s at 2 / 3 / 4 / 8); round 3: 5, together with the step kernel's issue priority (see bpr_fused_step_kernel)
     // SKR_COLD_REST=0 keeps every cold block on the full update (the float4 kernel): the A/B switch of tools/microbench.py
+    // (a caller that hands in state words -- skr_adam_block_cold_rest -- has asked for the row kernel and gets it)
     static const bool rest = [] { const char* e = getenv("SKR_COLD_REST"); return !(e && atoi(e) == 0); }();
     // A pass over a WHOLE block of the default length (32 steps and more) of the BPR tables takes six workgroups per CU
     // (SKR_COLD_BPC_FULL; 0: SKR_COLD_BPC for every pass): in the steady state of an epoch the pass and the step stream are
@@ -752,12 +854,16 @@ static int adam_block_cold_impl(const char* who, float* d_p, float* d_m, float* 
     const int bpc_k = (bpc_full && k >= 32 && !tf) ? bpc_full : bpc;
     adam_block_thresholds(a, lr, beta1, beta2, eps, k);
     a.stats = cold_stats_buffer();
-    if (rest) {
+    if (rest || d_rest) {
         int64_t blocks = ((n >> 6) + 4 * 4 - 1) / (4 * 4);
         if (blocks > 256 * bpc_k) blocks = 256 * bpc_k;
         if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(adam_cold_rows_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v, n, a,
-                           d_tag, hot_value);
+        if (d_rest)
+            hipLaunchKernelGGL((adam_cold_rows_kernel<4, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v,
+                               n, a, d_tag, hot_value, d_rest, pass_id);
+        else
+            hipLaunchKernelGGL((adam_cold_rows_kernel<4, false>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, d_p, d_m, d_v,
+                               n, a, d_tag, hot_value, static_cast<int32_t*>(nullptr), 0);
     } else {
         int64_t blocks = ((n >> 2) + 255) / 256;
         if (blocks > 256 * bpc) blocks = 256 * bpc;
@@ -812,6 +918,14 @@ int skr_adam_block_cold(float* d_p, float* d_m, float* d_v, int64_t n, float lr,
                         int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {
     return adam_block_cold_impl("skr_adam_block_cold", d_p, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, k, d_tag, hot_value, false,
                                 nullptr, stream);
+}
+int skr_adam_block_cold_rest(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                             int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, int32_t* d_rest, int32_t pass_id,
+                             void* stream) {
+    SKR_REQUIRE(d_rest, "skr_adam_block_cold_rest: NULL argument");
+    SKR_REQUIRE(pass_id >= 1 && pass_id < (1 << 29), "skr_adam_block_cold_rest: need 1 <= pass_id < 2^29");
+    return adam_block_cold_impl("skr_adam_block_cold_rest", d_p, d_m, d_v, n, lr, beta1, beta2, eps, step_t0, k, d_tag, hot_value,
+                                false, nullptr, stream, d_rest, pass_id);
 }
 int skr_adam_block_cold_tf(float* d_p, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
                            int64_t step_t0, int k, const int32_t* d_tag, int32_t hot_value, void* stream) {

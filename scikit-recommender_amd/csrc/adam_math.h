@@ -531,8 +531,8 @@ __device__ __forceinline__ AdamRowState chain_advance(float p, float g, float m,
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-// SKR_COLD_STATS=1: the device census of how the cold passes sorted their blocks, or NULL (defined in adam.hip)
-__attribute__((visibility("hidden"))) unsigned long long* cold_stats_buffer();
+// SKR_COLD_STATS=1: the device census of how the cold passes sorted their blocks (8 counters), or NULL (defined in adam.hip)
+__attribute__((visibility("hidden"))) unsigned long long* cold_stats_buffer(bool reread = false);
 // SKR_FUSED_STATS=1: the census of the lazy rows' evaluations (FC_COUNTERS counters), or NULL (defined in adam.hip)
 __attribute__((visibility("hidden"))) unsigned long long* fused_stats_buffer(bool reread = false);
 

@@ -41,6 +41,8 @@ SIGNATURES = {
     "skr_adam_block_mark": (i32, [vp, i64, i64, i32, vp, i32, vp, i64, vp]),
     "skr_adam_block_cold": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, i32, vp]),
     "skr_adam_block_hot": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i64, vp, i64, i64, i32, vp, vp]),
+    "skr_adam_block_cold_rest": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, i32, vp, i32, vp]),
+    "skr_cold_rest_census": (i32, [C.POINTER(u64), i32]),
     "skr_adam_step_tf": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, vp]),
     "skr_adam_block_cold_tf": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp, i32, vp]),
     "skr_adam_block_hot_tf": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i64, vp, i64, i64, i32, vp, vp]),

@@ -204,6 +204,10 @@ class DenseAdam(object):
         self.weight_decay = float(weight_decay)
         assert self.weight_decay >= 0.0 and not (self.weight_decay and self.tf_epsilon)
         self.t = 0
+        # the cold passes' state word per 64-float block and their pass counter (skr_adam_block_cold_rest): consecutive
+        # passes count 1 apart, and a pass then trusts what the one before found out about the rows both left cold;
+        # _rest_next = (lr, betas, eps, t) a pass must start from to be consecutive.  SKR_COLD_REST=0: the entry without words
+        self._rest, self._rest_pass, self._rest_next = None, 0, None
 
     def _entry(self, kind):
         """the library's entry point for ``kind`` -- "step" (one dense launch), "cold" or "hot" (the blocked form) -- in this
@@ -263,6 +267,7 @@ class DenseAdam(object):
     def launch_cold(self, tag, serial, k):
         """the cold pass of a k-step block that starts at step self.t, on the side stream (the caller has made that stream
         wait for whatever the pass depends on); records ``_ev_cold`` behind it"""
+        import os
         import torch
         from .. import _hip
         timing = getattr(self, "cold_timing", None)     # measurement hook (bench.py): a list that receives (start, end, k)
@@ -275,13 +280,40 @@ class DenseAdam(object):
         if timing is not None:
             e0, e1 = pool.pop() if pool is not None else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             e0.record(self._side)
-        _hip.check(self._entry("cold")(_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
-                                       self.betas[0], self.betas[1], self.eps, self.t, int(k), _hip.ptr(tag), int(serial),
-                                       self._side.cuda_stream))
+        if self.weight_decay or self.tf_epsilon or os.environ.get("SKR_COLD_REST", "1") == "0":
+            _hip.check(self._entry("cold")(_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(), self.lr,
+                                           self.betas[0], self.betas[1], self.eps, self.t, int(k), _hip.ptr(tag), int(serial),
+                                           self._side.cuda_stream))
+            self._rest_next = None
+        else:
+            pass_id = self._next_pass(int(k))           # (makes the words at the first pass)
+            _hip.check(_hip.lib().skr_adam_block_cold_rest(_hip.ptr(self.flat), _hip.ptr(self.m), _hip.ptr(self.v), self.flat.numel(),
+                                                           self.lr, self.betas[0], self.betas[1], self.eps, self.t, int(k),
+                                                           _hip.ptr(tag), int(serial), _hip.ptr(self._rest), pass_id,
+                                                           self._side.cuda_stream))
         if timing is not None:
             e1.record(self._side)
             timing.append((e0, e1, int(k)))
         self._ev_cold.record(self._side)
+
+    def invalidate_rest(self):
+        """the next cold pass trusts nothing the passes before it recorded.  For whoever writes ``flat``, ``m`` or ``v`` other
+        than through this optimiser's launches (``step()`` and a jump of ``t`` are noticed without it)"""
+        self._rest_next = None
+
+    def _next_pass(self, k):
+        """pass_id of a cold pass of k steps from self.t: the last one + 1 while the chain holds -- same lr, betas and eps, and
+        self.t where the last pass ended, i.e. every step since was one of the blocked form, which writes tagged rows only --
+        otherwise + 2.  The words are made on the side stream at the first pass and cleared there before the counter wraps"""
+        import torch
+        if self._rest is None or self._rest_pass + 2 >= (1 << 29):
+            with torch.cuda.stream(self._side):
+                self._rest = torch.zeros((self.flat.numel() + 63) // 64, dtype=torch.int32, device=self.flat.device)
+            self._rest_pass, self._rest_next = 0, None
+        here = (self.lr, tuple(self.betas), self.eps, self.t)
+        self._rest_pass += 1 if self._rest_next == here else 2
+        self._rest_next = (self.lr, tuple(self.betas), self.eps, self.t + k)
+        return self._rest_pass
 
     def end_blocks(self):
         """join the side stream: call after the last block, before anything else reads the parameters"""
@@ -310,6 +342,7 @@ class DenseAdam(object):
     def step(self):
         from .. import _hip
         self.t += 1
+        self._rest_next = None      # the dense launch moves every row
         _hip.check(self._entry("step")(_hip.ptr(self.flat), _hip.ptr(self.grad), _hip.ptr(self.m), _hip.ptr(self.v),
                                        self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.t, 1,
                                        _hip.ptr(self.touch), _hip.stream()))
