@@ -1712,6 +1712,80 @@ int skr_caser_queries(const float* d_U, const float* d_E, const float* d_shared,
                       int n_users, int n_rows, int pad_idx, int dim, int width, int seq_L, int nv, int nh, void* d_work,
                       size_t work_bytes, float* d_Q, void* stream);
 
+/* ============================================================================================
+ * SASRec -- self-attentive sequential recommendation (csrc/sasrec.hip)
+ * replaces: the TensorFlow graph of recommender/SASRec.py:60-87 (normalize), :174-269 (multihead_attention), :272-308
+ * (feedforward), :387-463 (_build_model) and the session runs of fit / predict (:465-498).
+ * Rows are 64 floats; `hidden` <= 64 is the model's hidden_units: narrower rows are zero-padded by the caller and the padded
+ * columns take no part in LayerNorm, receive no gradient and stay zero.  Tables: d_E (item_embeddings) [n_items + 1, 64], whose
+ * row n_items is the padding item: it is never read (a padded position is a row of zeros) and never receives a gradient;
+ * d_P (position_embeddings) [max_len, 64].
+ * d_shared: every other parameter, SKR_SASREC_SHARED_FLOATS(blocks) floats, 16-byte aligned, in rows of 64 floats, zero where
+ * padded.  A dense kernel of the reference, [in, out], is stored TRANSPOSED, row o holding the weights of output o.  Per block,
+ * SKR_SASREC_BLOCK_ROWS rows:
+ *   ln1_gamma | ln1_beta | Wq^T [64 rows] | bq | Wk^T [64] | bk | Wv^T [64] | bv | ln2_gamma | ln2_beta | W1^T [64] | b1 |
+ *   W2^T [64] | b2
+ * and behind the last block: ln_out_gamma | ln_out_beta.
+ * Per sequence (seq, pos, neg: int32 [max_len] each, left-padded with n_items), with m[t] = (seq[t] != n_items):
+ *   x = m dropout(sqrt(hidden) E[seq] + P);  per block:  q = LN1(x), Q = q Wq + bq, K = x Wk + bk, V = x Wv + bv, per head
+ *   A = dropout(softmax over the keys j <= t with m[j] of Q_h K_h^T / sqrt(hidden / heads)), y = concat_h(A V_h) + q,
+ *   f = LN2(y), x = m (dropout(dropout(relu(f W1 + b1)) W2 + b2) + f);  out = LN_out(x);
+ *   loss = sum over t with pos[t] != n_items of -log(sigmoid(y_pos) + 1e-24) - log(sigmoid(-y_neg) + 1e-24), over their number,
+ *   y_pos = sqrt(hidden) <out[t], E[pos[t]]>, y_neg likewise (0 for neg[t] == n_items).
+ * LN is the reference's normalize: (x - mean) / sqrt(var + 1e-8) gamma + beta, biased variance.  Rows with m = 0 are skipped
+ * as queries and as keys (the reference masks a key by a row sum of exactly 0, and evaluates 1 - sigmoid(x) where this takes
+ * sigmoid(-x): DESIGN.md names both deviations).
+ * Keep flags: one byte per element, per sequence SKR_SASREC_KEEP_BYTES(hidden, max_len, blocks, heads) bytes in this order:
+ *   the input [max_len][hidden] | per block: the attention weights [heads][max_len][max_len] (query, then key) |
+ *   the first feed-forward site [max_len][hidden] | the second [max_len][hidden]
+ * Limits (refused with a message): hidden <= SKR_SASREC_MAX_HIDDEN, max_len <= SKR_SASREC_MAX_LEN, blocks <=
+ * SKR_SASREC_MAX_BLOCKS, heads <= SKR_SASREC_MAX_HEADS and dividing hidden, n <= SKR_SASREC_MAX_BATCH.
+ * ========================================================================================== */
+#define SKR_SASREC_MAX_HIDDEN 64
+#define SKR_SASREC_MAX_LEN 64
+#define SKR_SASREC_MAX_BLOCKS 4
+#define SKR_SASREC_MAX_HEADS 8
+#define SKR_SASREC_MAX_BATCH 2048
+#define SKR_SASREC_WORKGROUPS 256 /* the step's persistent workgroups: sequence b belongs to workgroup b mod this */
+#define SKR_SASREC_BLOCK_ROWS 329
+#define SKR_SASREC_SHARED_FLOATS(blocks) (64 * (SKR_SASREC_BLOCK_ROWS * (blocks) + 2))
+#define SKR_SASREC_KEEP_BYTES(hidden, max_len, blocks, heads) \
+    ((max_len) * (hidden) + (blocks) * ((heads) * (max_len) * (max_len) + 2 * (max_len) * (hidden)))
+/* bytes of d_work for batches of at most n_max sequences; 0 for arguments out of range */
+int64_t skr_sasrec_workspace(int n_max, int max_len, int blocks, int heads);
+/* One training batch, forward and backward: d_seq, d_pos, d_neg int32 [n][max_len].  The mean loss is WRITTEN to word 0 of
+ * d_loss (float [2 * loss_slots], loss_slots 1 or SKR_LOSS_SLOTS) and every other word is written as zero: word 1 is the l2
+ * term's, which the caller fills in (SASRec.py adds l2_emb w to the two tables' gradients itself).  The gradients are ADDED to
+ * d_gE, d_gP and d_gshared, in the tables' layouts.  Dropout at `rate` (0: keeps everything and draws nothing): d_keep holds
+ * the flags of the n sequences in the layout above; NULL: the step draws on the device, keyed by (seed, step, the sequence's
+ * number in the batch, the element's offset in the layout), so that the backward draws them again; equal to TensorFlow's draws
+ * in law only.  d_keep_out (optional, same shape) records the flag of every element, used or not.  A sequence with an id
+ * outside [0, n_items] adds nothing to the sum or the gradients (its targets still count in the divisor) and its ids are not
+ * dereferenced.  A batch without any target gives loss 0 and zero gradients (unreachable through fit(): every training row
+ * holds a target).  No floating-point atomic: a workgroup adds its sequences' weight gradients in sequence order, the
+ * workgroups' sums are added in workgroup order, the position rows in batch order and the item rows once per distinct id of
+ * seq || pos || neg in ascending list position, so two calls on the same inputs give the same bits.  d_work:
+ * skr_sasrec_workspace(n, ...) bytes, 16-byte aligned, no initial contents, not to be shared by calls that may run at the
+ * same time. */
+int skr_sasrec_step(const float* d_E, const float* d_P, const float* d_shared, const int32_t* d_seq, const int32_t* d_pos,
+                    const int32_t* d_neg, int n, int n_items, int hidden, int max_len, int blocks, int heads, float rate,
+                    const uint8_t* d_keep, uint8_t* d_keep_out, uint64_t seed, uint64_t step, float* d_gE, float* d_gP, float* d_gshared,
+                    void* d_work, size_t work_bytes, float* d_loss, int loss_slots, void* stream);
+/* The same step with an event after each of its SKR_SASREC_LAUNCHES launch groups (the fused forward-loss-backward; the slabs'
+ * sum; the position rows; rank; ordered adds; loss): h_ms[k] (host) = milliseconds of group k; synchronises the stream. */
+#define SKR_SASREC_LAUNCHES 6
+int skr_sasrec_step_timed(const float* d_E, const float* d_P, const float* d_shared, const int32_t* d_seq, const int32_t* d_pos,
+                          const int32_t* d_neg, int n, int n_items, int hidden, int max_len, int blocks, int heads, float rate,
+                          const uint8_t* d_keep, uint8_t* d_keep_out, uint64_t seed, uint64_t step, float* d_gE, float* d_gP,
+                          float* d_gshared, void* d_work, size_t work_bytes, float* d_loss, int loss_slots, void* stream, float* h_ms);
+/* Query rows: d_Q[i][0..63] = sqrt(hidden) out[max_len - 1] of user u = d_users[i] (d_users NULL: u = i), the forward without
+ * dropout over the window d_windows[u][0..max_len) of the [n_users, max_len] table, so that the model's score of item t is
+ * <d_Q[i], E[t]> on the raw parameter rows.  An all-padding window gives sqrt(hidden) ln_out_beta, as the reference does; an
+ * id outside [0, n_items] reads as padding; a user out of range is skipped.  The last block runs for the 16-row tile of the
+ * last position alone. */
+int skr_sasrec_queries(const float* d_E, const float* d_P, const float* d_shared, const int32_t* d_users, int n, const int32_t* d_windows,
+                       int n_users, int n_items, int hidden, int max_len, int blocks, int heads, float* d_Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,10 @@ SIGNATURES = {
     "skr_caser_step": (i32, [vp] * 9 + [i32] * 10 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp]),
     "skr_caser_step_timed": (i32, [vp] * 9 + [i32] * 10 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp]),
     "skr_caser_queries": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
+    "skr_sasrec_workspace": (i64, [i32, i32, i32, i32]),
+    "skr_sasrec_step": (i32, [vp] * 6 + [i32] * 6 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, sz, vp, i32, vp]),
+    "skr_sasrec_step_timed": (i32, [vp] * 6 + [i32] * 6 + [f32, vp, vp, u64, u64, vp, vp, vp, vp, sz, vp, i32, vp, vp]),
+    "skr_sasrec_queries": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 
@@ -320,6 +324,19 @@ SKR_SLMREC_GATE_FLOATS, SKR_SLMREC_FUSION_FLOATS = 64 * 64 + 64, 64 * 192 + 64  
 SKR_DENS_GATE_FLOATS = 64 * 64 + 64     # one gate block of the flat parameter buffer: W [64 out][64 in], then b [64]
 SKR_CASER_MAX_L, SKR_CASER_MAX_T, SKR_CASER_MAX_NV, SKR_CASER_MAX_NH, SKR_CASER_MAX_BATCH = 8, 16, 8, 32, 2048   # skr_caser_step limits
 SKR_CASER_LAUNCHES = 10                  # skr_caser_step_timed: launch groups
+SKR_SASREC_MAX_HIDDEN, SKR_SASREC_MAX_LEN, SKR_SASREC_MAX_BLOCKS, SKR_SASREC_MAX_HEADS, SKR_SASREC_MAX_BATCH = 64, 64, 4, 8, 2048
+SKR_SASREC_BLOCK_ROWS, SKR_SASREC_LAUNCHES = 329, 6   # rows of 64 floats per block of the shared parameters; launch groups
+
+
+def sasrec_shared_floats(blocks):
+    """SKR_SASREC_SHARED_FLOATS(blocks): floats of SASRec's shared parameters (include/skrec_hip.h names the rows)"""
+    return 64 * (SKR_SASREC_BLOCK_ROWS * int(blocks) + 2)
+
+
+def sasrec_keep_bytes(hidden, max_len, blocks, heads):
+    """SKR_SASREC_KEEP_BYTES: keep flags per sequence -- input | per block: attention [heads][T][T] | ffn 1 | ffn 2"""
+    d, T = int(hidden), int(max_len)
+    return T * d + int(blocks) * (int(heads) * T * T + 2 * T * d)
 
 
 def hgn_gate_floats(L):
